@@ -21,7 +21,9 @@ while step k's backward is still running: a single step's host time is no longer
 bracketed region's wall time / K (MAX over ranks), value = global batch / that; the median of the per-step host times is
 reported beside it (ms_per_step_median_host).
 
-The JSON line also carries
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs DIR)
+and the JSON line (metric, value, unit, ms_per_step, the step's host times, graph cache, config).  --full adds what takes
+measurements of its own after the timed region, and the JSON line then also carries
   roofline      -- the dominant kernel (key-masked attention forward, vslt stream): algorithmic FLOPs 4*B*H*N^2*64 per
                    launch / launch duration, against the 2.5 PFLOP/s dense bf16 peak.  `achieved` / `frac` are the IN-STEP
                    figure, measured live here: after the timed region the step is re-captured with a stream-ordered time
@@ -36,6 +38,12 @@ The JSON line also carries
   cpu_baseline  -- the CPU oracle (fp32 PyTorch restatement of the reference, golden-pinned) timed on this host's
                    cores: BASELINE.md section 3 protocol (full per-GPU batch when the host has >= 32 GB of RAM, else B = 16
                    scaled linearly; 1 warm-up + 3 timed steps, median), rank 0, N = 1 only.
+  parity_bf16_vs_fp32 -- the committed parity of the benchmarked build at this size (profiles/parity_at_benchmark_size.json).
+
+--dump-outputs DIR writes what the last timed step handed back (rank 0), for comparing two builds output for output on
+the same seeded inputs: loss.npy (float64, the step's loss), params.npy and grads.npy (float32, the trainable parameters
+after the step's AdamW update and the step's gradient, from the flat buffers; a fixed seeded sample of DUMP_MAX_ELEMS
+positions when the buffer is larger).
 """
 import argparse
 import datetime
@@ -55,6 +63,7 @@ import torch  # noqa: E402  (importing torch makes no GPU call)
 import torch.distributed as dist  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0       # MI355X dense bf16 MFMA (MI355X_MICROARCH.md)
+DUMP_MAX_ELEMS = 4 * 2 ** 20    # per dumped flat buffer: params + grads stay under 32 MB of float32
 
 WORKLOADS = {
     # name: (per-GPU batch, TIE-len, layers, multiimages, n_images, ragged, missing mode, description)
@@ -119,6 +128,75 @@ def cpu_baseline(wl, shapes, budget_s: float = 300.0):
                       f"(T={T}, L={L}; host RAM {ram_gb:.0f} GB), 1 warm-up ({warm:.1f} s) + {timed} timed, median {t:.2f} s/step"}
 
 
+def full_report(a, model, flops, flops_dense, instep, probe, n_tok, world):
+    """--full: the roofline figures of the in-step and probe measurements, the committed profile figures and the CPU baseline."""
+    def roof(kind, kernel_name):
+        fl = flops[kind]
+        ins = instep.get(kind)
+        pr = probe.get(kind, 0.0)
+        ms = ins[0] if ins else pr                # in-step when measured, else (fp32 / eager runs) the probe
+        tf = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
+        d = {"bound": "mfma", "kernel": kernel_name, "achieved": tf, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+             "frac": tf / PEAK_BF16_TFLOPS, "flops_per_launch": fl, "dense_flops_per_launch": flops_dense[kind],
+             "flops_counted": ("the launch's own lengths: sum over samples of kv_len^2 (packed stream) or N * kv_len (padded); equal "
+                               "to the dense figure on the full workload"),
+             "timed_in": ("replayed steps, mtmp_timestamp in front of and behind every launch of this kernel on its stream, "
+                          "minus the stamp pair's own gap" if ins else "idle-device probe (no in-step measurement in this mode)"),
+             "avg_launch_ms": ms, "launches_timed": ins[1] if ins else (a.probe_launches if pr > 0 else 0),
+             "timestamp_gap_us": ins[2] if ins else None,
+             "probe_avg_launch_ms": pr or None, "probe_frac": (fl / (pr * 1e-3) / 1e12 / PEAK_BF16_TFLOPS) if pr > 0 else None,
+             "probe_timed_in": "back-to-back launches on the step's tensors between one HIP event pair, idle device"}
+        return d
+    # HBM traffic and the in-step rocprofv3 average of the same kernel come from separate rocprofv3 runs of this
+    # script (counters / traces cannot be read from inside it); committed under profiles/ with their method
+    traffic = traffic_src = rocprof_us = rocprof_src = None
+    tpath = os.path.join(ROOT, "profiles", "roofline_traffic.json")
+    tj = {}
+    if a.dtype == "bf16" and a.workload == "full" and os.path.exists(tpath):
+        with open(tpath) as fh:
+            tj = json.load(fh)
+        traffic, traffic_src = tj.get("traffic_bytes_per_launch"), f"profiles/roofline_traffic.json ({tj.get('round')})"
+        rocprof_us, rocprof_src = tj.get("rocprof_avg_us"), tj.get("rocprof_source")
+    # the benchmarked build's parity at THIS size (tests/test_gpu_parity.py: test_bf16_build_vs_fp32_build_at_benchmark_sizes,
+    # test_config2_full_size_fp32_step_vs_oracle), measured on the GPU by the test suite and committed with the profiles
+    parity = None
+    ppath = os.path.join(ROOT, "profiles", "parity_at_benchmark_size.json")
+    if a.dtype == "bf16" and os.path.exists(ppath):
+        with open(ppath) as fh:
+            parity = json.load(fh).get({"full": "config2", "ragged": "config2", "cfg5": "cfg5"}[a.workload])
+    rf = roof("attn_fwd", f"attn_fwd_kernel<{'bf16' if a.dtype == 'bf16' else 'float'}> (vslt stream, N={n_tok})")
+    rf.update(traffic=traffic, traffic_unit="bytes/launch", traffic_source=traffic_src, rocprof_avg_us=rocprof_us,
+              rocprof_source=rocprof_src)
+    out = {"parity_bf16_vs_fp32": parity, "roofline": rf}
+    out["roofline_more"] = [
+        roof("attn_bwd", "attn_bwd_dq_kernel + attn_bwd_dkdv_kernel (vslt stream; algorithmic flops = 2.5 x forward)"),
+        roof("gemm_tn", "gemm_tn_dma_kernel (vslt-stream QKV weight gradient, M x 768 x 256; its reduction is deferred into "
+                        "the layer's mtmp_reduce_batch launch)")]
+    for r, key in zip(out["roofline_more"], ("attn_bwd", "gemm_tn")):      # rocprofv3 averages of the committed trace, as above
+        r.update((tj.get("more") or {}).get(key) or {})
+    out["roofline_more"] = [r for r in out["roofline_more"] if r["avg_launch_ms"] > 0]
+    if world == 1 and not a.no_cpu_baseline:
+        shapes = {k: tuple(v.shape) for k, v in model.state_dict().items() if v.is_floating_point()}
+        out["cpu_baseline"] = cpu_baseline(a.workload, shapes)
+    return out
+
+
+def dump_outputs(out_dir, loss, flat):
+    """--dump-outputs: the last timed step's loss, and the flat parameter / gradient buffers (a fixed seeded sample of
+    DUMP_MAX_ELEMS positions when larger), as float .npy files."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = flat.data.numel()
+    idx = None
+    if n > DUMP_MAX_ELEMS:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randperm(n, generator=g)[:DUMP_MAX_ELEMS].sort().values.to(flat.data.device)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([loss], dtype=np.float64))
+    for name, buf in (("params", flat.data), ("grads", flat.grad)):
+        v = buf.detach() if idx is None else buf.detach()[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), v.float().cpu().numpy())
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -126,7 +204,12 @@ def parse():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--dropout", type=float, default=0.1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline kernels (in-step stamps, idle-device probe), "
+                         "report the committed profile figures and time the CPU oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss, parameters and gradients as DIR/<name>.npy (e.g. bench_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
     ap.add_argument("--hip-graph", type=int, default=1, choices=[0, 1])
     ap.add_argument("--graph-stages", type=int, default=0, help="0 = auto (one graph; with more than one rank two, cut behind the first fusion layer)")
     ap.add_argument("--workload", default="full", choices=sorted(WORKLOADS),
@@ -139,9 +222,9 @@ def parse():
     ap.add_argument("--skip-missing-images", type=int, default=1, choices=[0, 1],
                     help="0: a zero image goes through the frozen encoder for samples without one, as in the reference")
     ap.add_argument("--probe-launches", type=int, default=30,
-                    help="back-to-back launches per kernel of the idle-device probe after the timed region (0 = no probe)")
+                    help="(--full) back-to-back launches per kernel of the idle-device probe after the timed region (0 = no probe)")
     ap.add_argument("--instep-steps", type=int, default=12,
-                    help="replayed steps with time stamps around the roofline kernels (the in-step duration; 0 = off)")
+                    help="(--full) replayed steps with time stamps around the roofline kernels (the in-step duration; 0 = off)")
     ap.add_argument("--force-ddp", action="store_true",
                     help="run the RCCL reducer even with one rank (exercises the N>1 code path on a 1-GPU box)")
     ap.add_argument("--print-loss", action="store_true")
@@ -317,6 +400,8 @@ def main():
         ranks_agree = bool(torch.equal(lo, hi))
         if not ranks_agree:
             raise SystemExit(f"rank {rank}: parameters differ across ranks after {a.warmup + a.steps} steps: {lo.tolist()} vs {hi.tolist()}")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, loss, opt.flat)
 
     n_tok = TIE_LEN + 5
     flops_dense = {"attn_fwd": 4.0 * B_PER_GPU * 4 * n_tok * n_tok * 64,
@@ -334,7 +419,7 @@ def main():
                  "gemm_tn": flops_dense["gemm_tn"]}
     # ---- in-step duration of the roofline kernels: the step re-captured with time stamps around them (ops.kernel_marks)
     instep = {}
-    if a.instep_steps > 0 and graphed and a.dtype == "bf16":
+    if a.full and a.instep_steps > 0 and graphed and a.dtype == "bf16":
         ops.marks_enable(dev, 4096, only=("k.", "cal."))
         if gs is not None:
             gs.invalidate()                           # drop the captured graphs: the next steps capture the stamped step
@@ -371,7 +456,7 @@ def main():
         it0 = a.warmup + a.steps + 1
     # ---- idle-device probe: the same kernels on the step's real tensors, back to back between one HIP event pair
     probe = {}
-    if a.probe_launches > 0:
+    if a.full and a.probe_launches > 0:
         grabbed = {}
         raw = {"attn_fwd": ops.attn_fwd_grouped, "attn_bwd": ops.attn_bwd_grouped, "gemm_tn": ops.gemm_tn_grouped}
 
@@ -407,49 +492,12 @@ def main():
             dist.barrier()
 
     if rank == 0:
-        def roof(kind, kernel_name):
-            fl = flops[kind]
-            ins = instep.get(kind)
-            pr = probe.get(kind, 0.0)
-            ms = ins[0] if ins else pr                # in-step when measured, else (fp32 / eager runs) the probe
-            tf = fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0
-            d = {"bound": "mfma", "kernel": kernel_name, "achieved": tf, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                 "frac": tf / PEAK_BF16_TFLOPS, "flops_per_launch": fl, "dense_flops_per_launch": flops_dense[kind],
-                 "flops_counted": ("the launch's own lengths: sum over samples of kv_len^2 (packed stream) or N * kv_len (padded); equal "
-                                   "to the dense figure on the full workload"),
-                 "timed_in": ("replayed steps, mtmp_timestamp in front of and behind every launch of this kernel on its stream, "
-                              "minus the stamp pair's own gap" if ins else "idle-device probe (no in-step measurement in this mode)"),
-                 "avg_launch_ms": ms, "launches_timed": ins[1] if ins else (a.probe_launches if pr > 0 else 0),
-                 "timestamp_gap_us": ins[2] if ins else None,
-                 "probe_avg_launch_ms": pr or None, "probe_frac": (fl / (pr * 1e-3) / 1e12 / PEAK_BF16_TFLOPS) if pr > 0 else None,
-                 "probe_timed_in": "back-to-back launches on the step's tensors between one HIP event pair, idle device"}
-            return d
-        # HBM traffic and the in-step rocprofv3 average of the same kernel come from separate rocprofv3 runs of this
-        # script (counters / traces cannot be read from inside it); committed under profiles/ with their method
-        traffic = traffic_src = rocprof_us = rocprof_src = None
-        tpath = os.path.join(ROOT, "profiles", "roofline_traffic.json")
-        tj = {}
-        if a.dtype == "bf16" and a.workload == "full" and os.path.exists(tpath):
-            with open(tpath) as fh:
-                tj = json.load(fh)
-            traffic, traffic_src = tj.get("traffic_bytes_per_launch"), f"profiles/roofline_traffic.json ({tj.get('round')})"
-            rocprof_us, rocprof_src = tj.get("rocprof_avg_us"), tj.get("rocprof_source")
-        # the benchmarked build's parity at THIS size (tests/test_gpu_parity.py: test_bf16_build_vs_fp32_build_at_benchmark_sizes,
-        # test_config2_full_size_fp32_step_vs_oracle), measured on the GPU box by the test suite and committed with the profiles
-        parity = None
-        ppath = os.path.join(ROOT, "profiles", "parity_at_benchmark_size.json")
-        if a.dtype == "bf16" and os.path.exists(ppath):
-            with open(ppath) as fh:
-                parity = json.load(fh).get({"full": "config2", "ragged": "config2", "cfg5": "cfg5"}[a.workload])
-        rf = roof("attn_fwd", f"attn_fwd_kernel<{'bf16' if a.dtype == 'bf16' else 'float'}> (vslt stream, N={n_tok})")
-        rf.update(traffic=traffic, traffic_unit="bytes/launch", traffic_source=traffic_src, rocprof_avg_us=rocprof_us,
-                  rocprof_source=rocprof_src)
         out = {
             "metric": "tri-modal training samples/s (fwd+bwd+AdamW step, per-GPU batch %d)" % B_PER_GPU,
             "value": world * B_PER_GPU * a.steps / dt, "unit": "samples/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps, "ms_per_step_median_host": 1e3 * med,
             "host_enqueue_ms_per_step": host_ms, "hip_graph": bool(graphed), "graphs_per_step": n_graphs,
-            "graph_cache": graph_cache, "parity_bf16_vs_fp32": parity,
+            "graph_cache": graph_cache,
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": a.dtype, "data": "synthetic (SURVEY 8d recipe), random-init weights",
             "rccl_ranks": dist.get_world_size() if ddp else 1, "ranks_hold_identical_parameters": ranks_agree,
@@ -459,18 +507,9 @@ def main():
                                    + ("" if a.pack_rows else " -- padded fusion stack (--pack-rows 0)")
                                    + ("" if a.skip_missing_images else " -- zero images encoded (--skip-missing-images 0)"),
                        "global_batch": world * B_PER_GPU, "parallelism": f"dp{world}", "final_loss": loss},
-            "roofline": rf,
         }
-        out["roofline_more"] = [
-            roof("attn_bwd", "attn_bwd_dq_kernel + attn_bwd_dkdv_kernel (vslt stream; algorithmic flops = 2.5 x forward)"),
-            roof("gemm_tn", "gemm_tn_dma_kernel (vslt-stream QKV weight gradient, M x 768 x 256; its reduction is deferred into "
-                            "the layer's mtmp_reduce_batch launch)")]
-        for r, key in zip(out["roofline_more"], ("attn_bwd", "gemm_tn")):      # rocprofv3 averages of the committed trace, as above
-            r.update((tj.get("more") or {}).get(key) or {})
-        out["roofline_more"] = [r for r in out["roofline_more"] if r["avg_launch_ms"] > 0]
-        if world == 1 and not a.no_cpu_baseline:
-            shapes = {k: tuple(v.shape) for k, v in model.state_dict().items() if v.is_floating_point()}
-            out["cpu_baseline"] = cpu_baseline(a.workload, shapes)
+        if a.full:
+            out.update(full_report(a, model, flops, flops_dense, instep, probe, n_tok, world))
         print(json.dumps(out), flush=True)
     if ddp:
         dist.destroy_process_group()

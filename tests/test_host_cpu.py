@@ -563,6 +563,25 @@ def test_bench_launches_its_own_ranks(tmp_path):
     assert d == {"dry_run": True, "n_gpus": 2, "rccl_ranks": 2, "max_rank": 1}
 
 
+def test_bench_dump_outputs_float_files_and_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the loss as float64, the flat parameter / gradient buffers as float32, a buffer larger than
+    DUMP_MAX_ELEMS as the same seeded sample of positions in every run."""
+    import types
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    flat = types.SimpleNamespace(data=torch.arange(5000, dtype=torch.float32), grad=-torch.arange(5000, dtype=torch.float32))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), 0.25, flat)
+    for d in ("a", "b"):
+        assert sorted(os.listdir(tmp_path / d)) == ["grads.npy", "loss.npy", "params.npy"]
+        loss = np.load(tmp_path / d / "loss.npy")
+        assert loss.dtype == np.float64 and loss.tolist() == [0.25]
+    p, g = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "a" / "grads.npy")
+    assert p.dtype == g.dtype == np.float32 and p.shape == g.shape == (1000,)
+    assert np.array_equal(p, -g) and len(np.unique(p)) == 1000 and np.all(np.diff(p) > 0)
+    assert np.array_equal(p, np.load(tmp_path / "b" / "params.npy"))
+
+
 def test_flat_params_claim_refuses_slices_autograd_accumulated_into():
     """A backward kernel may overwrite a gradient slice only if nothing was accumulated into it since zero_grad()."""
     from medical_tri_modal_pilot_amd.optim import FlatParams

@@ -2,7 +2,7 @@
 import cProfile, io, os, pstats, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.argv = ["bench.py", "--no-cpu-baseline", "--steps", "20", "--warmup", "5"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--steps", "20", "--warmup", "5"]
 import runpy
 pr = cProfile.Profile()
 pr.enable()

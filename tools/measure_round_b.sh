@@ -2,7 +2,7 @@
 set -o pipefail
 T=$1; R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O
 for w in ragged cfg5; do
-  python bench.py --no-cpu-baseline --workload $w --steps 20 --warmup 6 > $O/${T}_bench_$w.json 2> $O/${T}_bench_$w.err || { tail -5 $O/${T}_bench_$w.err; exit 1; }
+  python bench.py --full --no-cpu-baseline --workload $w --steps 20 --warmup 6 > $O/${T}_bench_$w.json 2> $O/${T}_bench_$w.err || { tail -5 $O/${T}_bench_$w.err; exit 1; }
   tail -1 $O/${T}_bench_$w.json | cut -c1-200
 done
 python bench.py --no-cpu-baseline --workload ragged --steps 20 --warmup 6 --probe-launches 0 --instep-steps 0 --pack-rows 0 --skip-missing-images 0 > $O/${T}_bench_ragged_padded.json 2> /dev/null
