@@ -139,8 +139,14 @@ int mtmp_gemm_nt_signs_drop(int dtype, const void* a, const void* w, void* y, in
 
 /* Weight / bias gradient of the Linear and k=1 Conv1d layers (attention.py:60-62, module.py:74-78):
  * dw[N,K] (fp32) = dy[M,N]^T x[M,K];  db[N] (fp32, may be NULL) = column sums of dy.
- * N % 128 == 0, K % 128 == 0; the contraction runs over the M tokens (split over workgroups,
- * partial slabs in ws, one reduce pass).  ws: mtmp_gemm_tn_ws_floats(M,N,K) floats. */
+ * and of the trainable image encoder's Linear layers (stem, Swin blocks, patch merging):
+ * dw[N,K] (fp32) = dy[M,N]^T x[M,K];  db[N] (fp32, may be NULL) = column sums of dy.
+ * M >= 1, N % 8 == 0, K % 8 == 0, ldy >= N, ldx >= K, ldy % 8 == 0, ldx % 8 == 0, dy and x 16-byte aligned; anything else
+ * returns MTMP_ERR_ARG.  Columns past N / K of the operands are neither used nor written.  N and K both multiples of 128 run
+ * the tuned kernels of the fusion layers; every other shape runs one kernel with 128 x 128 tiles whose columns past N / K are
+ * masked.  The contraction runs over the M tokens (split over workgroups, no atomics: a call is reproducible bit for bit):
+ * partial slabs [mtmp_gemm_tn_slab_rows(dtype,M,N,K)][N K + N] in ws, then one reduce pass -- or, with dw == NULL, left in
+ * ws for mtmp_reduce_batch.  ws: mtmp_gemm_tn_ws_floats(M,N,K) floats (enough for either dtype). */
 long long mtmp_gemm_tn_ws_floats(int M, int N, int K);
 int mtmp_gemm_tn(int dtype, const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N, int K,
                  int ldy, int ldx, void* stream);

@@ -2,7 +2,8 @@
 models that TRAIN it (bi_vsltimg_mbt_v1.py:203-206, tri_mbt_v2.py:208-211 call it with gradients) take `forward_train`: the
 same blocks as autograd nodes over libmtmp_hip.so kernels (ops.LinearFn, LayerNormRowsFn, GeluFn, WindowAttnFn: mtmp_gemm_nt /
 mtmp_gemm_tn, mtmp_layernorm_rows(_bwd), mtmp_gelu_fwd / _bwd, mtmp_swin_window_attn(_bwd)); residual adds, StochasticDepth
-scaling and the 2x2 patch gather are torch glue.
+scaling and the 2x2 patch gather are torch glue.  Every matrix product of that path, the weight gradients of the 96- / 192-wide
+stages and of the 16-wide stem included, is one of those kernels: no library product.
 
 Parameter tree / state_dict keys equal the reference's torchvision fork
 (builder/models/src/swin_transformer.py:503-654: 1-channel 4x4/4 stem, depths [2,2,6,2],

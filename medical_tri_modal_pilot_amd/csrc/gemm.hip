@@ -945,6 +945,110 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(TnArgs<T> p) {
 }
 
 // ---------------------------------------------------------------------------
+// dW = dY^T X for N, K that are multiples of 8 but not both of 128 (the trainable image encoder: widths 96 x {1,2,3,4,6,8} and
+// the stem's 16).  gemm_tn_kernel with ceil-div tiles: a 128 x 128 tile that hangs over N or K fetches its missing 8-column
+// fragments from a clamped (valid) column and masks them to zero, like the rows past m_end, and the slab stores are guarded.
+// The zero columns cost MFMA cycles only, which these memory-bound products (48 flop per operand byte at N = K = 96) have to
+// spare; what counts is that dY and X are read as bf16, without fp32 copies, once per tile of the OTHER operand's width (the
+// repeats come from the L2 the tiles of one M split share).  Same slab protocol, no atomics.  Both dtypes.
+template <typename T>
+MTMP_DEV void tn_fetch_edge(TnRegs<T>& t, const T* src, int ld, int m0, int m_end, int c0, int C, int tid) {
+    const int q = (tid & 15) * 4, c = c0 + (tid >> 4) * 8;
+    const bool cok = c < C;                                // C % 8 == 0: a fragment is whole or absent
+    const T* col = src + min(c, C - 8);
+    t.ok = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int m = m0 + q + i;
+        t.f[i] = frag_load<T>(col + (size_t)min(m, max(m_end - 1, 0)) * ld);
+        t.ok |= (cok && m < m_end) ? (1u << i) : 0u;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void gemm_tn_edge_kernel(TnArgs<T> p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    T* sY = reinterpret_cast<T*>(smem_raw);   // [128 n][LDX tokens]
+    T* sX = sY + 128 * LDX;                   // [128 k][LDX tokens]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, half = lane >> 5;
+    const int tn = (p.N + 127) / 128, tk = (p.K + 127) / 128;
+    int w = xcd_remap(blockIdx.x, gridDim.x);         // the tn*tk tiles of one M split share an XCD, as in gemm_tn_kernel
+    const int split = w / (tn * tk);
+    w -= split * tn * tk;
+    const int n0 = (w / tk) * 128, k0 = (w % tk) * 128;
+    const int M = live_rows(p.M, p.m_live);
+    const int rps = p.m_live ? ((M + p.splits - 1) / p.splits + TK - 1) / TK * TK : p.rows_per_split;
+    const int m_lo = split * rps, m_end = min(M, m_lo + rps);
+    const int wn = (wave >> 1) * 64, wk = (wave & 1) * 64;
+    f32x16 acc[2][2] = {{{0}, {0}}, {{0}, {0}}};
+    float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};       // column sums of dY (bias gradient)
+    TnRegs<T> yreg, xreg;
+    tn_fetch_edge<T>(yreg, p.dy, p.ldy, m_lo, m_end, n0, p.N, tid);
+    tn_fetch_edge<T>(xreg, p.x, p.ldx, m_lo, m_end, k0, p.K, tid);
+    for (int m0 = m_lo; m0 < m_end; m0 += TK) {
+        __syncthreads();
+        tn_mask<T>(yreg);
+        tn_mask<T>(xreg);
+        tn_commit<T>(sY, yreg.f, tid);
+        tn_commit<T>(sX, xreg.f, tid);
+        if (k0 == 0) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+                csum[e] += to_f32(yreg.f[0].v[e]) + to_f32(yreg.f[1].v[e]) + to_f32(yreg.f[2].v[e]) + to_f32(yreg.f[3].v[e]);
+        }
+        __syncthreads();
+        if (m0 + TK < m_end) {
+            tn_fetch_edge<T>(yreg, p.dy, p.ldy, m0 + TK, m_end, n0, p.N, tid);
+            tn_fetch_edge<T>(xreg, p.x, p.ldx, m0 + TK, m_end, k0, p.K, tid);
+        }
+        // (a 32-row block of the tile that lies wholly past N or K holds zeros; its products are skipped, wave-uniformly)
+        const bool n1 = n0 + wn + 32 < p.N, k1 = k0 + wk + 32 < p.K;
+        if (n0 + wn < p.N && k0 + wk < p.K) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const Frag<T> a0 = frag_load<T>(sY + (wn + r) * LDX + 16 * c + 8 * half);
+                const Frag<T> b0 = frag_load<T>(sX + (wk + r) * LDX + 16 * c + 8 * half);
+                mma<T>(acc[0][0], a0, b0);
+                if (k1) {
+                    const Frag<T> b1 = frag_load<T>(sX + (wk + 32 + r) * LDX + 16 * c + 8 * half);
+                    mma<T>(acc[0][1], a0, b1);
+                    if (n1) {
+                        const Frag<T> a1 = frag_load<T>(sY + (wn + 32 + r) * LDX + 16 * c + 8 * half);
+                        mma<T>(acc[1][0], a1, b0); mma<T>(acc[1][1], a1, b1);
+                    }
+                } else if (n1) {
+                    const Frag<T> a1 = frag_load<T>(sY + (wn + 32 + r) * LDX + 16 * c + 8 * half);
+                    mma<T>(acc[1][0], a1, b0);
+                }
+            }
+        }
+    }
+    // partial slab row: [N*K] products then [N] column sums; rows >= N and columns >= K of the tile are not written
+    float* out = p.slab + (size_t)split * ((size_t)p.N * p.K + p.N);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int k = k0 + wk + 32 * j + r;
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const int n = n0 + wn + 32 * i + acc_row(t, half);
+                if (n < p.N && k < p.K) out[(size_t)n * p.K + k] = acc[i][j][t];
+            }
+        }
+    if (k0 == 0) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float s = csum[e];
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            const int n = n0 + (tid >> 4) * 8 + e;
+            if ((tid & 15) == 0 && n < p.N) out[(size_t)p.N * p.K + n] = s;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
 // bf16 build of dW = dY^T X: same tiling and slab protocol as gemm_tn_kernel, but the 64-token tiles are
 // kept in LDS in their NATURAL [token][col] layout (plain 16-byte copies, no register transposes) and the
 // MFMA fragments -- 8 consecutive TOKENS of one column -- come from the transposing LDS read
@@ -1388,9 +1492,11 @@ __global__ __launch_bounds__(256) void reduce_batch_kernel(ReduceBatch t) {
     }
 }
 
+// N or K not a multiple of 128: gemm_tn_edge_kernel
+bool tn_edge(int N, int K) { return N % 128 != 0 || K % 128 != 0; }
 int tn_splits(int M, int N, int K, int target_wgs) {
-    const int tiles = (N / 128) * (K / 128);
-    int s = target_wgs / tiles;
+    const int tiles = ((N + 127) / 128) * ((K + 127) / 128);
+    int s = target_wgs / (tiles < 1 ? 1 : tiles);
     const int max_s = (M + 4 * TK - 1) / (4 * TK);         // at least 4 token steps per split
     if (s > max_s) s = max_s;
     return s < 1 ? 1 : s;
@@ -1691,7 +1797,7 @@ int launch_gemm_lnbwd(int n, LnBwdGemmArgs<T>* segs, float* const* dgamma_dbeta,
 // partial slabs the launch writes (rows of the [splits][N K + N] workspace) -- a function of the shape only, the deferred
 // reductions ask for it through mtmp_gemm_tn_slab_rows.  mode: 0 one token group per workgroup, 1 two token groups (half the
 // slabs), 3 the LDS-DMA kernel with 128 x 128 tiles at the split count of mode 1 (bf16, large M; -DMTMP_TN_OLD: never),
-// 2 the LDS-DMA kernel with 128 x 256 tiles (-DMTMP_TN_WIDE)
+// 2 the LDS-DMA kernel with 128 x 256 tiles (-DMTMP_TN_WIDE), 4 the masked-tile kernel for N or K not a multiple of 128
 int tn_launch_splits(bool tr, int M, int N, int K, int* mode_out) {
     // two token groups per workgroup / wide tiles once the split count is not what limits the grid
     // Workgroups of the one-per-CU kernels: 192, not one per CU -- these workgroups take a whole CU's LDS, so every CU that holds
@@ -1699,11 +1805,29 @@ int tn_launch_splits(bool tr, int M, int N, int K, int* mode_out) {
     // CUs left free the launch is ~15 % longer alone and the step shorter (9.03-9.06 / 9.25-9.35 ms against 9.11-9.14 / 9.30-9.42
     // with 256, two boxes; 224: 9.08-9.11; 160 and 128: no better than 256).
     constexpr int TN_WGS = 192;
+    if (tn_edge(N, K)) {                                   // mode 4: ceil-div tiles, 512 workgroups (two per CU), both dtypes
+        if (mode_out) *mode_out = 4;
+        return tn_splits(M, N, K, 512);
+    }
     const bool two = tr && tn_splits(M, N, K, TN_WGS) * 8 * TK <= M;
     int mode = two ? 1 : 0, splits = tn_splits(M, N, K, two ? TN_WGS : (tr ? 512 : 640));
     if (two && K >= 256) mode = 3;                         // the DMA kernel with 128 x 128 tiles, split count of `two`
     if (mode_out) *mode_out = mode;
     return splits;
+}
+// the slabs of one product -> dw, db: the same kernel (and summation order) as the deferred form
+int tn_reduce_slabs(const float* ws, float* dw, float* db, int splits, int N, int K, hipStream_t st) {
+    const size_t nk = (size_t)N * K, cols = nk + N;
+    ReduceBatch t;
+    for (int i = 0; i < RB_MAX; ++i) {
+        t.slab[i] = ws; t.a[i] = dw; t.b[i] = db; t.cols[i] = (long long)cols; t.split[i] = (long long)nk; t.rows[i] = splits;
+        t.ld[i] = (long long)cols;
+    }
+    const int rlanes = splits >= 256 ? 64 : splits >= 64 ? 16 : 4;
+    const size_t blocks = (cols + 4 * (256 / rlanes) - 1) / (4 * (256 / rlanes));
+    hipLaunchKernelGGL(reduce_batch_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks), 1), dim3(256), 0, st, t);
+    MTMP_CHECK_LAUNCH("mtmp_gemm_tn(reduce)");
+    return MTMP_OK;
 }
 template <typename T>
 int launch_gemm_tn(const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N, int K, int ldy, int ldx,
@@ -1715,6 +1839,17 @@ int launch_gemm_tn(const void* dy, const void* x, float* dw, float* db, float* w
     rps = (rps + TK - 1) / TK * TK;
     TnArgs<T> a{(const T*)dy, (const T*)x, ws, M, N, K, ldy, ldx, splits, rps};
     a.m_live = m_live;
+    if (mode == 4) {
+        const size_t sm = (size_t)256 * LDX * sizeof(T);
+        if (sm > 48 * 1024 && hipFuncSetAttribute((const void*)gemm_tn_edge_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  (int)sm) != hipSuccess) {
+            mtmp_set_error("mtmp_gemm_tn: cannot raise dynamic LDS to %zu", sm);
+            return MTMP_ERR_LAUNCH;
+        }
+        hipLaunchKernelGGL(gemm_tn_edge_kernel<T>, dim3(splits * ((N + 127) / 128) * ((K + 127) / 128)), dim3(256), sm, st, a);
+        MTMP_CHECK_LAUNCH("mtmp_gemm_tn");
+        return dw ? tn_reduce_slabs(ws, dw, db, splits, N, K, st) : MTMP_OK;
+    }
     // the DMA kernel needs 16-byte aligned rows and 32-bit byte offsets; operands that are not get the register-staged kernel
     // at the same split count
     const bool dma = mode >= 2 && ldy % 8 == 0 && ldx % 8 == 0 && (uintptr_t)dy % 16 == 0 && (uintptr_t)x % 16 == 0 &&
@@ -1741,17 +1876,7 @@ int launch_gemm_tn(const void* dy, const void* x, float* dw, float* db, float* w
     }
     MTMP_CHECK_LAUNCH("mtmp_gemm_tn");
     if (!dw) return MTMP_OK;                                  // partials only: the caller reduces them (mtmp_reduce_batch)
-    const size_t nk = (size_t)N * K, cols = nk + N;
-    ReduceBatch t;                                            // the same kernel (and summation order) as the deferred form
-    for (int i = 0; i < RB_MAX; ++i) {
-        t.slab[i] = ws; t.a[i] = dw; t.b[i] = db; t.cols[i] = (long long)cols; t.split[i] = (long long)nk; t.rows[i] = splits;
-        t.ld[i] = (long long)cols;
-    }
-    const int rlanes = splits >= 256 ? 64 : splits >= 64 ? 16 : 4;
-    const size_t blocks = (cols + 4 * (256 / rlanes) - 1) / (4 * (256 / rlanes));
-    hipLaunchKernelGGL(reduce_batch_kernel, dim3((unsigned)(blocks > 4096 ? 4096 : blocks), 1), dim3(256), 0, st, t);
-    MTMP_CHECK_LAUNCH("mtmp_gemm_tn(reduce)");
-    return MTMP_OK;
+    return tn_reduce_slabs(ws, dw, db, splits, N, K, st);
 }
 
 // Grouped weight gradients (bf16, LDS-DMA kernel): the same product of up to three token streams in one launch, partial slabs
@@ -1991,12 +2116,14 @@ extern "C" int mtmp_reduce_scatter(const float* const* src, const int* rows, con
 }
 
 extern "C" long long mtmp_gemm_tn_ws_floats(int M, int N, int K) {
+    if (tn_edge(N, K)) return (long long)tn_launch_splits(false, M, N, K, nullptr) * ((long long)N * K + N);
     return (long long)tn_splits(M, N, K, 640) * ((long long)N * K + N);   // upper bound over both dtypes' split counts
 }
 
 // dW[N,K] (fp32) = dY[M,N]^T X[M,K];  db[N] (fp32, optional) = column sums of dY.  N, K multiples of
-// 128.  ws: mtmp_gemm_tn_ws_floats(M,N,K) floats.  The weight / bias gradients of the Linear and
-// k=1 Conv1d layers of attention.py:60-62 and module.py:74-78.
+// 8 (both multiples of 128: the tuned kernels; the rest: gemm_tn_edge_kernel).  ws: mtmp_gemm_tn_ws_floats(M,N,K) floats.
+// The weight / bias gradients of the Linear and k=1 Conv1d layers of attention.py:60-62 and module.py:74-78, and of the
+// trainable image encoder's Linear layers (swin_transformer.py forward_train).
 extern "C" int mtmp_gemm_tn_live(int dtype, const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N,
                                  int K, int ldy, int ldx, const int32_t* rows_live, void* stream);
 extern "C" int mtmp_gemm_tn(int dtype, const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N,
@@ -2008,7 +2135,7 @@ extern "C" int mtmp_gemm_tn(int dtype, const void* dy, const void* x, float* dw,
 extern "C" int mtmp_gemm_tn_live(int dtype, const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N,
                                  int K, int ldy, int ldx, const int32_t* rows_live, void* stream) {
     MTMP_CHECK_ARG(dy && x && ws && (dw || !db), "mtmp_gemm_tn: null pointer");
-    MTMP_CHECK_ARG(M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 128 == 0 && ldy >= N && ldx >= K && ldy % 8 == 0 &&
+    MTMP_CHECK_ARG(M > 0 && N > 0 && K > 0 && N % 8 == 0 && K % 8 == 0 && ldy >= N && ldx >= K && ldy % 8 == 0 &&
                        ldx % 8 == 0, "mtmp_gemm_tn: bad shape M=%d N=%d K=%d ldy=%d ldx=%d", M, N, K, ldy, ldx);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == 0) return launch_gemm_tn<float>(dy, x, dw, db, ws, M, N, K, ldy, ldx, rows_live, st);

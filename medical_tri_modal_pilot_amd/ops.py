@@ -287,7 +287,9 @@ def gemm_tn(dy2d, x2d, want_bias=True, out=None, defer=None, pack=None):
     """(dW[N,K], db[N] | None) in fp32: dW = dy^T x, db = column sums of dy (split over the M tokens).
     out=(dw, db): write into these fp32 buffers (slices of the flat gradient) instead of allocating.
     defer: a list -- the split-M partials are left in the workspace and the reduction is appended to it; dW / db hold the result
-    only after reduce_batch(defer) (one launch for all of a layer's reductions).  pack: row_starts() of a packed stream."""
+    only after reduce_batch(defer) (one launch for all of a layer's reductions).  pack: row_starts() of a packed stream.
+    N and K are multiples of 8; rows may be wider than N / K (column windows of wider buffers: row strides multiples of 8
+    elements, 16-byte aligned base)."""
     _gpu(dy2d, x2d)
     live = None if pack is None else pack.data_ptr() + 4 * (pack.numel() // 2)
     M, N = dy2d.shape
@@ -915,15 +917,11 @@ class LinearFn(torch.autograd.Function):
 
 
 def gemm_tn_any(dy2d, x2d):
-    """(dW [N,K], db [N]) in fp32 like gemm_tn, for any width: mtmp_gemm_tn tiles need N and K in multiples of 128 (every product of
-    the fusion layers; stages 3-4 of the image encoder).  The 96- / 192-wide stages of the image encoder, its 16-wide stem and
-    the odd-sized patch-merging products take a plain library TN product in fp32 -- weight gradients of the sibling models that
-    train the encoder only, not on the benchmarked path."""
-    N, K = dy2d.shape[1], x2d.shape[1]
-    if N % 128 == 0 and K % 128 == 0:
-        return gemm_tn(dy2d, x2d)
-    dyf = dy2d.float()
-    return dyf.t() @ x2d.float(), dyf.sum(0)
+    """(dW [N,K], db [N]) in fp32 like gemm_tn, for every width mtmp_gemm_tn takes (N and K multiples of 8; anything else raises).
+    Multiples of 128 (every product of the fusion layers; stages 3-4 of the image encoder) run the tuned kernels; the 96- /
+    192-wide stages of the image encoder, its 16-wide stem and the first patch merging run the masked-tile kernel
+    (csrc/gemm.hip gemm_tn_edge_kernel) on the operands as they are: no fp32 copies, no library product."""
+    return gemm_tn(dy2d, x2d)
 
 
 # ----------------------------------------------------------------------------- image encoder, trainable path (Swin-T backward)

@@ -35,6 +35,30 @@ def timeit(fn, rounds, inner=5):
     return ts[len(ts) // 2]
 
 
+def timeit_pair(fa, fb, rounds, inner=5):
+    """two forms of one product, alternating round by round in this process: (min ms of fa, min ms of fb)"""
+    for _ in range(2):
+        fa()
+        fb()
+    best = [float("inf"), float("inf")]
+    for _ in range(rounds):
+        for i, fn in enumerate((fa, fb)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            best[i] = min(best[i], e0.elapsed_time(e1) / inner)
+    return best[0], best[1]
+
+
+# (N = dY width, K = X width, rows at 64 images) of the weight gradients of the trainable image encoder whose widths are not
+# multiples of 128: stem, stage 1 qkv / proj / fc1 / fc2, patch merging 1, stage 2 qkv / proj / fc1 / fc2
+ENCODER_TN = ((96, 16, 200704), (288, 96, 200704), (96, 96, 200704), (384, 96, 200704), (96, 384, 200704), (192, 384, 50176),
+              (576, 192, 50176), (192, 192, 50176), (768, 192, 50176), (192, 768, 50176))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
@@ -45,6 +69,7 @@ def main():
     R = lambda *s: torch.randn(*s, generator=g, device=DEV, dtype=torch.float32).to(BF)
     M = 64 * 1005
     out = {}
+    table = ""
 
     def rec(name, ms, flops=None, bytes_=None):
         d = {"ms": round(ms, 4)}
@@ -103,6 +128,30 @@ def main():
             dy, x = R(M, n), R(M, k)
             rec(f"gemm_tn[{n},{k},M]", timeit(lambda: ops.gemm_tn(dy, x), a.rounds), 2.0 * M * n * k)
             rec(f"gemm_tn[{n},{k},M].blas", timeit(lambda: dy.t() @ x, a.rounds), 2.0 * M * n * k)
+    # ---- the same for the encoder's widths (mtmp_gemm_tn's masked-tile kernel + reduction), each next to the path these
+    #      products took before: fp32 copies of both operands, a library product and a separate column sum
+    if want("gemm_tn"):
+        lines, tot = [], [0.0, 0.0]
+        for n, k, m in ENCODER_TN:
+            dy, x = R(m, n), R(m, k)
+
+            def lib_form():
+                dyf = dy.float()
+                return dyf.t() @ x.float(), dyf.sum(0)
+
+            t_new, t_lib = timeit_pair(lambda: ops.gemm_tn(dy, x), lib_form, a.rounds)
+            rec(f"gemm_tn[{n},{k},{m}]", t_new, 2.0 * m * n * k, 2.0 * (n + k) * m)
+            rec(f"gemm_tn[{n},{k},{m}].cast_blas_sum", t_lib, 2.0 * m * n * k, 2.0 * (n + k) * m)
+            tot[0] += t_new
+            tot[1] += t_lib
+            lines.append(f"{n:4d} x {k:4d}  {m:7d}  {t_new * 1e3:9.1f}  {t_lib * 1e3:9.1f}  {2.0 * (n + k) * m / t_new / 1e9:6.2f}")
+            del dy, x
+        lines.append(f"sum                   {tot[0] * 1e3:9.1f}  {tot[1] * 1e3:9.1f}")
+        table = ("# dW = dY^T X, db = colsum(dY), bf16 operands, one process, forms alternating, min over %d rounds of 5 calls\n"
+                 "# new: ops.gemm_tn (product + reduction); before: dy.float().t() @ x.float() and dy.float().sum(0)\n"
+                 "# TB/s: 2 (N + K) M bytes / new time\n"
+                 "#  N      K        M     new us  before us    TB/s\n" % a.rounds + "\n".join(lines) + "\n")
+        print(table, end="", flush=True)
     # ---- attention
     if want("attn"):
         B, N = 64, 1005
@@ -131,6 +180,9 @@ def main():
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "bench_kernels.json"), "w") as fh:
         json.dump(out, fh, indent=1)
+    if table:                        # the encoder-width table, next to the JSON
+        with open(os.path.join(os.path.dirname(fh.name), "gemm_tn_encoder_widths.txt"), "w") as ft:
+            ft.write(table)
 
 
 if __name__ == "__main__":
