@@ -483,6 +483,25 @@ int mtmp_gelu_bwd(int dtype, const void* x, const void* dy, void* dx, long long 
 int mtmp_swin_window_attn_bwd(int dtype, const void* qkv, const void* table, const void* dout, void* dqkv, float* dtab, int n_img,
                               int H, int W, int C, int heads, int shift, float scale, void* stream);
 
+/* ---- Shifted-window attention on maps of ANY size (swin_transformer.py:150-225 pads the normalised map with zeros to whole 7x7
+ * windows in front of the qkv projection, rolls the PADDED map and crops the result): the padded map never exists in memory.
+ * qkv / out / dout / dqkv stay [n,H,W,3C | C] on the un-padded, un-shifted map.  The window grid covers Hp x Wp = ceil(H/7) 7 x
+ * ceil(W/7) 7 and the cyclic shift is modulo Hp / Wp; a token whose pixel lies at y >= H or x >= W is a PAD token: its q / k / v
+ * are qkv_bias (float[3C]) rounded to `dtype`, made in registers; it is an ordinary (unmasked) key; its output row is not
+ * stored.  The caller passes shift 0 for a padded map of one window; one axis of a single window and the other of several is
+ * refused.  rows_live as in mtmp_swin_window_attn_live (may be NULL).
+ * mtmp_swin_window_attn_pad_bwd: every element of dqkv is written once; dtab as in mtmp_swin_window_attn_bwd (caller zeroes;
+ * pad keys' columns included).  dbias float[3C], which the caller ZEROES first (float atomics): the pad tokens' dk and dv, i.e.
+ * THEIR share of the gradient of the qkv bias (a pad token's dout is zero, so its dq is: dbias[0..C) stays zero) -- the real
+ * tokens' share is the column sum of dqkv, which the backward of the projection forms as ever.
+ * H and W multiples of 7: both entries run the kernels of mtmp_swin_window_attn_live / _bwd themselves (bit-identical; dbias is
+ * left untouched). */
+int mtmp_swin_window_attn_pad(int dtype, const void* qkv, const float* qkv_bias, const void* table, void* out, int n_img, int H,
+                              int W, int C, int heads, int shift, float scale, const int32_t* rows_live, void* stream);
+int mtmp_swin_window_attn_pad_bwd(int dtype, const void* qkv, const float* qkv_bias, const void* table, const void* dout,
+                                  void* dqkv, float* dtab, float* dbias, int n_img, int H, int W, int C, int heads, int shift,
+                                  float scale, void* stream);
+
 /* Attention half of a Swin block in ONE launch (ABI 4): out = x + row_scale[image] * (proj(window_attention(qkv(norm1(x)))) + b_proj).
  * Replaces builder/models/src/swin_transformer.py:428-449 (norm1, attn, stochastic_depth, residual) with :115-225
  * (shifted_window_attention) for maps that are multiples of the 7x7 window.  bf16 only (dtype MTMP_BF16); x, out [n_img, H, W, C]

@@ -1,7 +1,7 @@
 """Swin-T chest-X-ray encoder.  The tri-modal model runs it frozen under no_grad (the forward-only kernels below); the sibling
 models that TRAIN it (bi_vsltimg_mbt_v1.py:203-206, tri_mbt_v2.py:208-211 call it with gradients) take `forward_train`: the
 same blocks as autograd nodes over libmtmp_hip.so kernels (ops.LinearFn, LayerNormRowsFn, GeluFn, WindowAttnFn: mtmp_gemm_nt /
-mtmp_gemm_tn, mtmp_layernorm_rows(_bwd), mtmp_gelu_fwd / _bwd, mtmp_swin_window_attn(_bwd)); residual adds, StochasticDepth
+mtmp_gemm_tn, mtmp_layernorm_rows(_bwd), mtmp_gelu_fwd / _bwd, mtmp_swin_window_attn(_pad)(_bwd)); residual adds, StochasticDepth
 scaling and the 2x2 patch gather are torch glue.  Every matrix product of that path, the weight gradients of the 96- / 192-wide
 stages and of the 16-wide stem included, is one of those kernels: no library product.
 
@@ -19,10 +19,12 @@ Every block runs on libmtmp_hip.so kernels over ONE un-shifted NHWC map:
 The additive table (relative-position bias + shift mask) is constant per block: built once on
 the host and cached.  Feature maps whose side is not a multiple of 7 (--image-size 512: 128 / 64 /
 32 / 16 tokens a side) take the reference's zero-padded windows (:150-152): a padded token is a zero
-vector behind norm1, so its q / k / v are the projection's bias -- the qkv map is laid into a
-bias-filled map of the padded size (two torch copies per block), the window kernel runs on that map
-and the result is cropped.  Odd-sized maps are zero-padded in front of a patch merging (:34-44).
-The present-images-only form (`slots`) needs maps that are multiples of the window at every stage.
+vector behind norm1, so its q / k / v are the projection's bias -- mtmp_swin_window_attn_pad(_bwd)
+walk the window grid of the PADDED map over the un-padded qkv map, make the pad tokens' fragments
+from the bias in registers and store nothing for them (no padded copy, forward or backward; the pad
+tokens' dk / dv are their share of the bias gradient).  Odd-sized maps are zero-padded in front of a
+patch merging (:34-44).  The present-images-only form (`slots`) is used for maps that are multiples of
+the window at every stage only (the model's choice; the padded kernel honours rows_live).
 """
 import contextlib
 from typing import List
@@ -172,12 +174,16 @@ class ShiftedWindowAttention(nn.Module):
     def forward_train(self, xn: torch.Tensor) -> torch.Tensor:
         """xn [n,H,W,C] (normalised) -> attention output BEFORE the output projection, with gradients."""
         n, H, W, C = xn.shape
-        if H % WS or W % WS:
-            raise NotImplementedError("training the image encoder needs feature maps that are multiples of the 7x7 window "
-                                      "(--image-size 224 / 448)")
-        shift = 0 if WS >= H else self.shift_size[0]
+        Hp, Wp = -(-H // WS) * WS, -(-W // WS) * WS           # zero-padded to whole windows (:150-152)
+        if (WS >= Hp) != (WS >= Wp):
+            raise NotImplementedError("maps with one side of a single window and the other of several (per-axis shift)")
+        shift = 0 if WS >= Hp else self.shift_size[0]
         qkv = ops.LinearFn.apply(xn, self.qkv.weight, self.qkv.bias, xn.dtype)
-        return ops.WindowAttnFn.apply(qkv, self.additive_table_train(shift, xn.device), self.num_heads, shift)
+        tab = self.additive_table_train(shift, xn.device)
+        if (Hp, Wp) == (H, W):
+            return ops.WindowAttnFn.apply(qkv, tab, self.num_heads, shift)
+        # the pad tokens are zero vectors BEHIND norm1: q / k / v = the bias, formed inside the kernels (no padded map)
+        return ops.WindowAttnPadFn.apply(qkv, self.qkv.bias, tab, self.num_heads, shift)
 
     def forward(self, xn: torch.Tensor, norm: nn.LayerNorm = None) -> torch.Tensor:
         """xn [n,H,W,C] (already normalised, or raw with `norm` = the block's norm1 to be fused into the qkv
@@ -195,12 +201,9 @@ class ShiftedWindowAttention(nn.Module):
         tab = self.additive_table(shift, xn.dtype, xn.device)
         if (Hp, Wp) == (H, W):
             return ops.swin_window_attn(qkv, tab, self.num_heads, shift)
-        if ops.live_rows_active():
-            raise NotImplementedError("present-images-only encoding needs maps that are multiples of the 7x7 window")
-        # the pad tokens are zero vectors BEHIND norm1 (the reference pads the normalised map): q / k / v = the bias
-        padded = self.qkv.bias.detach().to(qkv.dtype).expand(n, Hp, Wp, 3 * C).contiguous()
-        padded[:, :H, :W] = qkv
-        return ops.swin_window_attn(padded, tab, self.num_heads, shift)[:, :H, :W].contiguous()
+        # the pad tokens are zero vectors BEHIND norm1 (the reference pads the normalised map): q / k / v = the bias, formed
+        # inside the kernel -- no padded copy of the map
+        return ops.swin_window_attn_pad(qkv, self.qkv.bias.detach().float(), tab, self.num_heads, shift)
 
 
 class SwinTransformerBlock(nn.Module):

@@ -85,6 +85,18 @@ MTMP_DEV Frag<float> frag_keep(const Frag<float>& f, bool ok) {
     return r;
 }
 
+// a | b on the bits: with frag_keep, `ok ? a : b` without a branch (the padded-window kernels pick a loaded token or the bias).
+MTMP_DEV Frag<bf16> frag_or(const Frag<bf16>& a, const Frag<bf16>& b) {
+    Frag<bf16> r;
+    r.v = __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4_t, a.v) | __builtin_bit_cast(u32x4_t, b.v));
+    return r;
+}
+MTMP_DEV Frag<float> frag_or(const Frag<float>& a, const Frag<float>& b) {
+    Frag<float> r;
+    r.v = __builtin_bit_cast(f32x8, __builtin_bit_cast(u32x8_t, a.v) | __builtin_bit_cast(u32x8_t, b.v));
+    return r;
+}
+
 // All lanes of the wave agree that nothing needs masking -> skip the ANDs (interior tiles).
 MTMP_DEV bool wave_all(bool ok) { return __builtin_amdgcn_ballot_w64(!ok) == 0; }
 
@@ -279,6 +291,15 @@ template <typename A> MTMP_DEV int grp_find(const Grouped<A>& g, int w) { return
 
 // ---- streaming-kernel helpers shared by elementwise.hip and the fused dX + LayerNorm-backward GEMM (d_model = 256) ----
 MTMP_DEV f32x4 ld4f(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// 8 consecutive fp32 bias values (32-byte aligned) rounded to T: a pad token's q / k / v piece in the padded-window kernels
+template <typename T> MTMP_DEV Frag<T> frag_bias(const float* p) {
+    const f32x4 a = ld4f(p), b = ld4f(p + 4);
+    Frag<T> f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { f.v[j] = from_f32<T>(a[j]); f.v[j + 4] = from_f32<T>(b[j]); }
+    return f;
+}
 
 // sum two values across the wave at once
 MTMP_DEV void wave_sum2(float& a, float& b) {

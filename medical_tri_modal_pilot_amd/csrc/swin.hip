@@ -115,14 +115,20 @@ template <typename T> MTMP_DEV void store_pair2(T* p, T a, T b);
 template <> MTMP_DEV void store_pair2<bf16>(bf16* p, bf16 a, bf16 b) { *reinterpret_cast<bf16x2*>(p) = bf16x2{a, b}; }
 template <> MTMP_DEV void store_pair2<float>(float* p, float a, float b) { *reinterpret_cast<f32x2*>(p) = f32x2{a, b}; }
 
-template <typename T>
+// PAD: H, W need not be multiples of the window.  The window grid covers the map padded to Hp x Wp = whole windows (the cyclic
+// shift is modulo Hp / Wp), but only the H x W map exists in memory: a token whose pixel lies at y >= H or x >= W is a PAD token
+// -- its q / k / v are qkv_bias (fp32 [3C], rounded to T: the reference pads the normalised map with zeros in FRONT of the
+// projection, swin_transformer.py:150-152), it is an ordinary key, and its output row is not stored.
+template <typename T, bool PAD>
 __global__ __launch_bounds__(256) void swin_wattn_kernel(const T* qkv, const T* table, T* out, int n_img_max, int H, int W,
-                                                         int C, int heads, int shift, float scale, const int* rows_live) {
+                                                         int C, int heads, int shift, float scale, const int* rows_live,
+                                                         const float* qkv_bias) {
     const int n_img = rows_live ? min(n_img_max, *rows_live / (H * W)) : n_img_max;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, half = lane >> 5;
     T* sVt = reinterpret_cast<T*>(smem_raw) + wave * DH * LDV;          // this wave's [32 d][LDV keys]
-    const int nWh = H / WS, nWw = W / WS;
+    const int nWh = PAD ? (H + WS - 1) / WS : H / WS, nWw = PAD ? (W + WS - 1) / WS : W / WS;
+    const int Hp = PAD ? nWh * WS : H, Wp = PAD ? nWw * WS : W;
     const long long total = (long long)n_img * nWh * nWw * heads;
     const long long task = (long long)blockIdx.x * 4 + wave;
     const bool live = task < total;
@@ -137,32 +143,55 @@ __global__ __launch_bounds__(256) void swin_wattn_kernel(const T* qkv, const T* 
     auto pix = [&](int t) -> long long {
         const int ty = t / WS, tx = t - ty * WS;
         int yy = wi * WS + ty + shift, xx = wj * WS + tx + shift;
-        if (yy >= H) yy -= H;
-        if (xx >= W) xx -= W;
+        if (yy >= Hp) yy -= Hp;
+        if (xx >= Wp) xx -= Wp;
+        if (PAD && (yy >= H || xx >= W)) return -1;             // pad token: no pixel
         return ((long long)img * H + yy) * W + xx;
+    };
+    // (PAD) a token's fragment: loaded from its pixel (clamped address, masked) or, for a pad token, the bias piece
+    const bool haspad = PAD && !wave_all(lane >= L || pix(lane) >= 0);      // wave-uniform: interior windows skip the bias path
+    auto tok_frag = [&](int t, int col) -> Frag<T> {
+        const long long p = pix(t < L ? t : 0);
+        Frag<T> f = frag_keep(frag_load<T>(qkv + (PAD && p < 0 ? 0 : p) * C3 + col), live && t < L && (!PAD || p >= 0));
+        if (haspad) f = frag_or(f, frag_keep(frag_bias<T>(qkv_bias + col), live && t < L && p < 0));
+        return f;
     };
     // ---- Q (B operand: natural token order) and K (A operand: rows through swz23), straight from global
     Frag<T> qf[2][2], kf[2][2];
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
         const int tq = 32 * blk + r, tk = 32 * blk + swz23(r);
-        const T* pq = qkv + pix(tq < L ? tq : 0) * C3 + head * DH + 8 * half;
-        const T* pk = qkv + pix(tk < L ? tk : 0) * C3 + C + head * DH + 8 * half;
+        if constexpr (PAD) {
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            qf[blk][c] = frag_keep(frag_load<T>(pq + 16 * c), live && tq < L);
-            kf[blk][c] = frag_keep(frag_load<T>(pk + 16 * c), live && tk < L);
+            for (int c = 0; c < 2; ++c) {
+                qf[blk][c] = tok_frag(tq, head * DH + 8 * half + 16 * c);
+                kf[blk][c] = tok_frag(tk, C + head * DH + 8 * half + 16 * c);
+            }
+        } else {
+            const T* pq = qkv + pix(tq < L ? tq : 0) * C3 + head * DH + 8 * half;
+            const T* pk = qkv + pix(tk < L ? tk : 0) * C3 + C + head * DH + 8 * half;
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                qf[blk][c] = frag_keep(frag_load<T>(pq + 16 * c), live && tq < L);
+                kf[blk][c] = frag_keep(frag_load<T>(pk + 16 * c), live && tk < L);
+            }
         }
     }
     // ---- V -> LDS transposed: lane = (key pair, 8-dim group), two passes over the 32 dims
     {
         const int kp = (lane & 31) * 2, dg = (lane >> 5) * 8;
-        const T* pa = qkv + pix(kp < L ? kp : 0) * C3 + 2 * C + head * DH + dg;
-        const T* pb = qkv + pix(kp + 1 < L ? kp + 1 : 0) * C3 + 2 * C + head * DH + dg;
+        const T* pa = PAD ? qkv : qkv + pix(kp < L ? kp : 0) * C3 + 2 * C + head * DH + dg;
+        const T* pb = PAD ? qkv : qkv + pix(kp + 1 < L ? kp + 1 : 0) * C3 + 2 * C + head * DH + dg;
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) {
-            const Frag<T> fa = frag_keep(frag_load<T>(pa + 16 * ps), live && kp < L);
-            const Frag<T> fb = frag_keep(frag_load<T>(pb + 16 * ps), live && kp + 1 < L);
+            Frag<T> fa, fb;
+            if constexpr (PAD) {
+                fa = tok_frag(kp, 2 * C + head * DH + dg + 16 * ps);
+                fb = tok_frag(kp + 1, 2 * C + head * DH + dg + 16 * ps);
+            } else {
+                fa = frag_keep(frag_load<T>(pa + 16 * ps), live && kp < L);
+                fb = frag_keep(frag_load<T>(pb + 16 * ps), live && kp + 1 < L);
+            }
 #pragma unroll
             for (int e = 0; e < 8; ++e) store_pair2<T>(sVt + (dg + 16 * ps + e) * LDV + kp, fa.v[e], fb.v[e]);
         }
@@ -218,7 +247,7 @@ __global__ __launch_bounds__(256) void swin_wattn_kernel(const T* qkv, const T* 
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
         const int tq = 32 * qb + r;
-        if (live && tq < L) {
+        if (live && tq < L && (!PAD || pix(tq) >= 0)) {        // (a pad token's row is not stored)
             T* po = out + pix(tq) * C + head * DH + 4 * half;
 #pragma unroll
             for (int g = 0; g < 4; ++g)
@@ -842,13 +871,42 @@ extern "C" int mtmp_swin_window_attn_live(int dtype, const void* qkv, const void
     const int nb = (int)((total + 3) / 4);
     hipStream_t st = (hipStream_t)stream;
     if (dtype == 0)
-        hipLaunchKernelGGL(swin_wattn_kernel<float>, dim3(nb), dim3(256), 4 * DH * LDV * sizeof(float), st, (const float*)qkv,
-                           (const float*)table, (float*)out, n_img, H, W, C, heads, shift, scale, rows_live);
+        hipLaunchKernelGGL((swin_wattn_kernel<float, false>), dim3(nb), dim3(256), 4 * DH * LDV * sizeof(float), st, (const float*)qkv,
+                           (const float*)table, (float*)out, n_img, H, W, C, heads, shift, scale, rows_live, (const float*)nullptr);
     else if (dtype == 1)
-        hipLaunchKernelGGL(swin_wattn_kernel<bf16>, dim3(nb), dim3(256), 4 * DH * LDV * sizeof(bf16), st, (const bf16*)qkv,
-                           (const bf16*)table, (bf16*)out, n_img, H, W, C, heads, shift, scale, rows_live);
+        hipLaunchKernelGGL((swin_wattn_kernel<bf16, false>), dim3(nb), dim3(256), 4 * DH * LDV * sizeof(bf16), st, (const bf16*)qkv,
+                           (const bf16*)table, (bf16*)out, n_img, H, W, C, heads, shift, scale, rows_live, (const float*)nullptr);
     else { mtmp_set_error("mtmp_swin_window_attn: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
     MTMP_CHECK_LAUNCH("mtmp_swin_window_attn");
+    return MTMP_OK;
+}
+
+// The same attention on a map of ANY size: the window grid covers the map padded to whole windows, Hp x Wp = ceil(H / 7) 7 x
+// ceil(W / 7) 7, as swin_transformer.py:150-152 pads it, but qkv / out stay [n,H,W,3C | C] -- the pad tokens' q / k / v are
+// qkv_bias (float[3C]) rounded to `dtype`, made in registers.  The shift is modulo Hp / Wp; the caller passes shift 0 for a
+// padded map of one window.  H and W multiples of 7: the kernel of mtmp_swin_window_attn itself (no pad token exists).
+extern "C" int mtmp_swin_window_attn_pad(int dtype, const void* qkv, const float* qkv_bias, const void* table, void* out, int n_img,
+                                         int H, int W, int C, int heads, int shift, float scale, const int32_t* rows_live,
+                                         void* stream) {
+    MTMP_CHECK_ARG(qkv && qkv_bias && table && out, "mtmp_swin_window_attn_pad: null pointer");
+    MTMP_CHECK_ARG(n_img > 0 && H > 0 && W > 0 && heads > 0 && C == heads * DH && shift >= 0 && shift < WS,
+                   "mtmp_swin_window_attn_pad: bad shape n=%d H=%d W=%d C=%d heads=%d shift=%d", n_img, H, W, C, heads, shift);
+    if (H % WS == 0 && W % WS == 0)
+        return mtmp_swin_window_attn_live(dtype, qkv, table, out, n_img, H, W, C, heads, shift, scale, rows_live, stream);
+    const int nWh = (H + WS - 1) / WS, nWw = (W + WS - 1) / WS;
+    MTMP_CHECK_ARG(shift == 0 || (nWh > 1 && nWw > 1), "mtmp_swin_window_attn_pad: a padded map of one window is not shifted (H=%d W=%d shift=%d)",
+                   H, W, shift);
+    const long long total = (long long)n_img * nWh * nWw * heads;
+    const int nb = (int)((total + 3) / 4);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == 0)
+        hipLaunchKernelGGL((swin_wattn_kernel<float, true>), dim3(nb), dim3(256), 4 * DH * LDV * sizeof(float), st, (const float*)qkv,
+                           (const float*)table, (float*)out, n_img, H, W, C, heads, shift, scale, rows_live, qkv_bias);
+    else if (dtype == 1)
+        hipLaunchKernelGGL((swin_wattn_kernel<bf16, true>), dim3(nb), dim3(256), 4 * DH * LDV * sizeof(bf16), st, (const bf16*)qkv,
+                           (const bf16*)table, (bf16*)out, n_img, H, W, C, heads, shift, scale, rows_live, qkv_bias);
+    else { mtmp_set_error("mtmp_swin_window_attn_pad: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
+    MTMP_CHECK_LAUNCH("mtmp_swin_window_attn_pad");
     return MTMP_OK;
 }
 

@@ -193,17 +193,22 @@ template <typename T, bool BWD> __global__ __launch_bounds__(256) void gelu_kern
 //       row constants read back from LDS;  dV^T += dO^T P,  dK^T += Q^T dS  (contraction over queries = accumulator rows)
 // The transposed operands (K^T, Q^T, dO^T: head dims on the rows) are staged per wave in LDS like V^T in the forward.  Pad
 // tokens (49..63) are zero fragments; their keys carry -30000 in the table, their queries a zero dO: they add nothing.
-template <typename T>
+// PAD (maps of any size, swin.hip swin_wattn_kernel<T, true>): a pad token's q / k / v are the rounded qkv_bias, its dO is zero.
+// So its dq is zero and nothing of it is stored; its dk and dv are NOT zero: they are the pad tokens' share of the gradient of the
+// qkv bias.  Each wave sums them over its pad keys (DPP row sums, the two rows of a half-wave through v_readlane) and adds the
+// 2 x 32 values of its head into dbias[C..3C) with float atomics, like dtab; windows without a pad token skip all of it.
+template <typename T, bool PAD>
 __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1))
 void swin_wattn_bwd_kernel(const T* qkv, const T* table, const T* dout, T* dqkv, float* dtab, int n_img, int H, int W, int C,
-                           int heads, int shift, float scale) {
+                           int heads, int shift, float scale, const float* qkv_bias, float* dbias) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, half = lane >> 5;
     T* sKt = reinterpret_cast<T*>(smem_raw) + (size_t)wave * 3 * DH * LDV;      // this wave's [32 d][LDV tokens] images
     T* sQt = sKt + DH * LDV;
     T* sOt = sQt + DH * LDV;
     float* sRow = reinterpret_cast<float*>(reinterpret_cast<T*>(smem_raw) + (size_t)4 * 3 * DH * LDV) + wave * 2 * LP;   // lse | delta
-    const int nWh = H / WS, nWw = W / WS;
+    const int nWh = PAD ? (H + WS - 1) / WS : H / WS, nWw = PAD ? (W + WS - 1) / WS : W / WS;
+    const int Hp = PAD ? nWh * WS : H, Wp = PAD ? nWw * WS : W;
     const long long total = (long long)n_img * nWh * nWw * heads;
     const long long task = (long long)blockIdx.x * 4 + wave;
     const bool live = task < total;
@@ -217,29 +222,50 @@ void swin_wattn_bwd_kernel(const T* qkv, const T* table, const T* dout, T* dqkv,
     auto pix = [&](int t) -> long long {       // token t of this window -> its pixel in the UN-shifted map (swin.hip)
         const int ty = t / WS, tx = t - ty * WS;
         int yy = wi * WS + ty + shift, xx = wj * WS + tx + shift;
-        if (yy >= H) yy -= H;
-        if (xx >= W) xx -= W;
+        if (yy >= Hp) yy -= Hp;
+        if (xx >= Wp) xx -= Wp;
+        if (PAD && (yy >= H || xx >= W)) return -1;             // pad token: no pixel
         return ((long long)img * H + yy) * W + xx;
+    };
+    // (PAD) 8 elements of token t at column `col` of a [.., ld] map: from its pixel (clamped address, masked), or for a pad token
+    // the bias piece (the qkv map) / zero (dout)
+    const bool haspad = PAD && !wave_all(lane >= L || pix(lane) >= 0);      // wave-uniform: interior windows skip the bias path
+    auto tok_frag = [&](const T* base, int ld, int t, int col) -> Frag<T> {
+        const long long p = pix(t < L ? t : 0);
+        Frag<T> f = frag_keep(frag_load<T>(base + (PAD && p < 0 ? 0 : p) * ld + col), live && t < L && (!PAD || p >= 0));
+        if (haspad && base == qkv) f = frag_or(f, frag_keep(frag_bias<T>(qkv_bias + col), live && t < L && p < 0));
+        return f;
     };
     // operand fragments of one token set: natural order (B operands) or through swz23 (A operands)
     auto load_set = [&](const T* base, int ld, int col0, bool swz, Frag<T> (&f)[2][2]) {
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
             const int t = 32 * blk + (swz ? swz23(r) : r);
-            const T* ptr = base + pix(t < L ? t : 0) * ld + col0 + head * DH + 8 * half;
+            if constexpr (PAD) {
 #pragma unroll
-            for (int c = 0; c < 2; ++c) f[blk][c] = frag_keep(frag_load<T>(ptr + 16 * c), live && t < L);
+                for (int c = 0; c < 2; ++c) f[blk][c] = tok_frag(base, ld, t, col0 + head * DH + 8 * half + 16 * c);
+            } else {
+                const T* ptr = base + pix(t < L ? t : 0) * ld + col0 + head * DH + 8 * half;
+#pragma unroll
+                for (int c = 0; c < 2; ++c) f[blk][c] = frag_keep(frag_load<T>(ptr + 16 * c), live && t < L);
+            }
         }
     };
     // [32 d][tokens] image of one tensor in LDS (lane = token pair x 8-dim group, two passes over the 32 dims)
     auto stage_t = [&](const T* base, int ld, int col0, T* dst) {
         const int kp = (lane & 31) * 2, dg = (lane >> 5) * 8;
-        const T* pa = base + pix(kp < L ? kp : 0) * ld + col0 + head * DH + dg;
-        const T* pb = base + pix(kp + 1 < L ? kp + 1 : 0) * ld + col0 + head * DH + dg;
+        const T* pa = PAD ? base : base + pix(kp < L ? kp : 0) * ld + col0 + head * DH + dg;
+        const T* pb = PAD ? base : base + pix(kp + 1 < L ? kp + 1 : 0) * ld + col0 + head * DH + dg;
 #pragma unroll
         for (int ps = 0; ps < 2; ++ps) {
-            const Frag<T> fa = frag_keep(frag_load<T>(pa + 16 * ps), live && kp < L);
-            const Frag<T> fb = frag_keep(frag_load<T>(pb + 16 * ps), live && kp + 1 < L);
+            Frag<T> fa, fb;
+            if constexpr (PAD) {
+                fa = tok_frag(base, ld, kp, col0 + head * DH + dg + 16 * ps);
+                fb = tok_frag(base, ld, kp + 1, col0 + head * DH + dg + 16 * ps);
+            } else {
+                fa = frag_keep(frag_load<T>(pa + 16 * ps), live && kp < L);
+                fb = frag_keep(frag_load<T>(pb + 16 * ps), live && kp + 1 < L);
+            }
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 T* d = dst + (dg + 16 * ps + e) * LDV + kp;
@@ -331,7 +357,7 @@ void swin_wattn_bwd_kernel(const T* qkv, const T* table, const T* dout, T* dqkv,
                 for (int s = 0; s < 2; ++s)
                     mma<T>(dq, frag_load<T>(sKt + r * LDV + 32 * kb + 16 * s + 8 * half), frag_from_acc<T>(st[kb][qb], s));
             const int tq = 32 * qb + r;
-            if (live && tq < L) {
+            if (live && tq < L && (!PAD || pix(tq) >= 0)) {
                 T* po = dqkv + pix(tq) * C3 + head * DH + 4 * half;
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
@@ -388,7 +414,7 @@ void swin_wattn_bwd_kernel(const T* qkv, const T* table, const T* dout, T* dqkv,
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             const int tk = 32 * kb + r;
-            if (live && tk < L) {
+            if (live && tk < L && (!PAD || pix(tk) >= 0)) {
                 T* pk = dqkv + pix(tk) * C3 + C + head * DH + 4 * half;
                 T* pv = dqkv + pix(tk) * C3 + 2 * C + head * DH + 4 * half;
 #pragma unroll
@@ -396,6 +422,25 @@ void swin_wattn_bwd_kernel(const T* qkv, const T* table, const T* dout, T* dqkv,
                     store4<T>(pk + 8 * g, dk[kb][4 * g] * scale, dk[kb][4 * g + 1] * scale, dk[kb][4 * g + 2] * scale,
                               dk[kb][4 * g + 3] * scale);
                     store4<T>(pv + 8 * g, dv[kb][4 * g], dv[kb][4 * g + 1], dv[kb][4 * g + 2], dv[kb][4 * g + 3]);
+                }
+            }
+        }
+        if constexpr (PAD) {
+            if (haspad && live) {                  // (wave-uniform: dpp_row / lane_bcast need the whole wave)
+                const bool p0 = r < L && pix(r) < 0, p1 = 32 + r < L && pix(32 + r) < 0;      // this lane's two keys: pad?
+#pragma unroll
+                for (int t = 0; t < 16; ++t) {     // register t <-> head dim acc_row(t, half); lanes of a half <-> keys
+                    float sk = (p0 ? dk[0][t] : 0.f) + (p1 ? dk[1][t] : 0.f), sv = (p0 ? dv[0][t] : 0.f) + (p1 ? dv[1][t] : 0.f);
+                    sk += dpp_row<0x128>(sk); sv += dpp_row<0x128>(sv);
+                    sk += dpp_row<0x124>(sk); sv += dpp_row<0x124>(sv);
+                    sk += dpp_row<0x122>(sk); sv += dpp_row<0x122>(sv);
+                    sk += dpp_row<0x121>(sk); sv += dpp_row<0x121>(sv);
+                    const float k0 = lane_bcast(sk, 0) + lane_bcast(sk, 16), k1 = lane_bcast(sk, 32) + lane_bcast(sk, 48);
+                    const float v0 = lane_bcast(sv, 0) + lane_bcast(sv, 16), v1 = lane_bcast(sv, 32) + lane_bcast(sv, 48);
+                    if (r == 0) {
+                        atomicAdd(dbias + C + head * DH + acc_row(t, half), (half ? k1 : k0) * scale);
+                        atomicAdd(dbias + 2 * C + head * DH + acc_row(t, half), half ? v1 : v0);
+                    }
                 }
             }
         }
@@ -463,23 +508,67 @@ extern "C" int mtmp_swin_window_attn_bwd(int dtype, const void* qkv, const void*
     const int nb = (int)((tasks + 3) / 4);
     if (dtype == 0) {
         const size_t sm = (size_t)4 * 3 * DH * LDV * sizeof(float) + 4 * 2 * LP * sizeof(float);
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<float, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)sm) != hipSuccess) {
             mtmp_set_error("mtmp_swin_window_attn_bwd: hipFuncSetAttribute(%zu) failed", sm);
             return MTMP_ERR_LAUNCH;
         }
-        hipLaunchKernelGGL(swin_wattn_bwd_kernel<float>, dim3(nb), dim3(256), sm, st, (const float*)qkv, (const float*)table,
-                           (const float*)dout, (float*)dqkv, dtab, n_img, H, W, C, heads, shift, scale);
+        hipLaunchKernelGGL((swin_wattn_bwd_kernel<float, false>), dim3(nb), dim3(256), sm, st, (const float*)qkv, (const float*)table,
+                           (const float*)dout, (float*)dqkv, dtab, n_img, H, W, C, heads, shift, scale, (const float*)nullptr,
+                           (float*)nullptr);
     } else if (dtype == 1) {
         const size_t sm = (size_t)4 * 3 * DH * LDV * sizeof(bf16) + 4 * 2 * LP * sizeof(float);       // 56 KB
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<bf16>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<bf16, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)sm) != hipSuccess) {
             mtmp_set_error("mtmp_swin_window_attn_bwd: hipFuncSetAttribute(%zu) failed", sm);
             return MTMP_ERR_LAUNCH;
         }
-        hipLaunchKernelGGL(swin_wattn_bwd_kernel<bf16>, dim3(nb), dim3(256), sm, st, (const bf16*)qkv, (const bf16*)table,
-                           (const bf16*)dout, (bf16*)dqkv, dtab, n_img, H, W, C, heads, shift, scale);
+        hipLaunchKernelGGL((swin_wattn_bwd_kernel<bf16, false>), dim3(nb), dim3(256), sm, st, (const bf16*)qkv, (const bf16*)table,
+                           (const bf16*)dout, (bf16*)dqkv, dtab, n_img, H, W, C, heads, shift, scale, (const float*)nullptr,
+                           (float*)nullptr);
     } else { mtmp_set_error("mtmp_swin_window_attn_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
     MTMP_CHECK_LAUNCH("mtmp_swin_window_attn_bwd");
+    return MTMP_OK;
+}
+
+// Autograd of mtmp_swin_window_attn_pad: qkv, dqkv [n,H,W,3C] and dout [n,H,W,C] on the UN-padded map of any size; every element
+// of dqkv is written once.  dtab as above (the pad keys' columns included).  dbias float[3C], which the caller ZEROES first like
+// dtab: the pad tokens' dk and dv, i.e. their share of the gradient of the qkv bias (their dq is zero: dbias[0..C) stays zero);
+// the real tokens' share is the column sum of dqkv, which the projection's own backward forms.  H and W multiples of 7: the
+// kernel of mtmp_swin_window_attn_bwd itself, dbias is left as it is.
+extern "C" int mtmp_swin_window_attn_pad_bwd(int dtype, const void* qkv, const float* qkv_bias, const void* table, const void* dout,
+                                             void* dqkv, float* dtab, float* dbias, int n_img, int H, int W, int C, int heads,
+                                             int shift, float scale, void* stream) {
+    MTMP_CHECK_ARG(qkv && qkv_bias && table && dout && dqkv && dtab && dbias, "mtmp_swin_window_attn_pad_bwd: null pointer");
+    MTMP_CHECK_ARG(n_img > 0 && H > 0 && W > 0 && heads > 0 && C == heads * DH && shift >= 0 && shift < WS,
+                   "mtmp_swin_window_attn_pad_bwd: bad shape n=%d H=%d W=%d C=%d heads=%d shift=%d", n_img, H, W, C, heads, shift);
+    if (H % WS == 0 && W % WS == 0)
+        return mtmp_swin_window_attn_bwd(dtype, qkv, table, dout, dqkv, dtab, n_img, H, W, C, heads, shift, scale, stream);
+    const int nWh = (H + WS - 1) / WS, nWw = (W + WS - 1) / WS;
+    MTMP_CHECK_ARG(shift == 0 || (nWh > 1 && nWw > 1),
+                   "mtmp_swin_window_attn_pad_bwd: a padded map of one window is not shifted (H=%d W=%d shift=%d)", H, W, shift);
+    hipStream_t st = (hipStream_t)stream;
+    const long long tasks = (long long)n_img * nWh * nWw * heads;
+    const int nb = (int)((tasks + 3) / 4);
+    if (dtype == 0) {
+        const size_t sm = (size_t)4 * 3 * DH * LDV * sizeof(float) + 4 * 2 * LP * sizeof(float);
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<float, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
+            mtmp_set_error("mtmp_swin_window_attn_pad_bwd: hipFuncSetAttribute(%zu) failed", sm);
+            return MTMP_ERR_LAUNCH;
+        }
+        hipLaunchKernelGGL((swin_wattn_bwd_kernel<float, true>), dim3(nb), dim3(256), sm, st, (const float*)qkv, (const float*)table,
+                           (const float*)dout, (float*)dqkv, dtab, n_img, H, W, C, heads, shift, scale, qkv_bias, dbias);
+    } else if (dtype == 1) {
+        const size_t sm = (size_t)4 * 3 * DH * LDV * sizeof(bf16) + 4 * 2 * LP * sizeof(float);
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<bf16, true>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
+            mtmp_set_error("mtmp_swin_window_attn_pad_bwd: hipFuncSetAttribute(%zu) failed", sm);
+            return MTMP_ERR_LAUNCH;
+        }
+        hipLaunchKernelGGL((swin_wattn_bwd_kernel<bf16, true>), dim3(nb), dim3(256), sm, st, (const bf16*)qkv, (const bf16*)table,
+                           (const bf16*)dout, (bf16*)dqkv, dtab, n_img, H, W, C, heads, shift, scale, qkv_bias, dbias);
+    } else { mtmp_set_error("mtmp_swin_window_attn_pad_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
+    MTMP_CHECK_LAUNCH("mtmp_swin_window_attn_pad_bwd");
     return MTMP_OK;
 }

@@ -261,6 +261,19 @@ def swin_window_attn(qkv, table, heads, shift):
     return out
 
 
+def swin_window_attn_pad(qkv, bias, table, heads, shift):
+    """swin_window_attn for a map of any size: qkv [n,H,W,3C] -> [n,H,W,C] over the window grid of the map padded to whole 7x7
+    windows, whose pad tokens' q / k / v are `bias` (fp32 [3C], rounded to qkv's type in the kernel) -- the padded map is never
+    built (mtmp_swin_window_attn_pad)."""
+    _gpu(qkv)
+    n, H, W, C3 = qkv.shape
+    C = C3 // 3
+    out = torch.empty(n, H, W, C, dtype=qkv.dtype, device=qkv.device)
+    call("mtmp_swin_window_attn_pad", _dt(qkv), _p(qkv), _p(bias), _p(table), _p(out), n, H, W, C, heads, int(shift),
+         float((C // heads) ** -0.5), _live(), _stream())
+    return out
+
+
 # (the 384-wide stage, 128 windows per half batch, was instantiated and measured: 7.93 vs 7.94 ms/step -- one round of
 #  workgroups bound by their own chain of weight fetches, as long as the four launches it replaces; not kept)
 SWIN_ATTN_BLOCK_WIDTHS = (96, 192)
@@ -968,6 +981,21 @@ def swin_window_attn_bwd(qkv, table, dout, heads, shift):
     return dqkv, dtab
 
 
+def swin_window_attn_pad_bwd(qkv, bias, table, dout, heads, shift):
+    """autograd of swin_window_attn_pad: (dqkv like qkv, dtab fp32 [4][heads][64][64], dbias fp32 [3C] = the PAD tokens' share of
+    the bias gradient only; zero when the map is made of whole windows)"""
+    _gpu(qkv, dout)
+    qkv, dout = _c(qkv), _c(dout)
+    n, H, W, C3 = qkv.shape
+    C = C3 // 3
+    dqkv = torch.empty_like(qkv)
+    dtab = torch.zeros(4, heads, 64, 64, dtype=torch.float32, device=qkv.device)
+    dbias = torch.zeros(C3, dtype=torch.float32, device=qkv.device)
+    call("mtmp_swin_window_attn_pad_bwd", _dt(qkv), _p(qkv), _p(bias), _p(table), _p(dout), _p(dqkv), _p(dtab), _p(dbias), n, H, W, C,
+         heads, int(shift), float((C // heads) ** -0.5), _stream())
+    return dqkv, dtab, dbias
+
+
 class LayerNormRowsFn(torch.autograd.Function):
     """nn.LayerNorm over the last dim (swin_transformer.py:428-449 norm1 / norm2, the merge norm, the final norm) with
     gradients: mtmp_layernorm_rows forward, mtmp_layernorm_rows_bwd backward."""
@@ -1016,6 +1044,27 @@ class WindowAttnFn(torch.autograd.Function):
         qkv, tab = ctx.saved_tensors
         dqkv, dtab = swin_window_attn_bwd(qkv, tab, dout.to(qkv.dtype), ctx.heads, ctx.shift)
         return dqkv, dtab, None, None
+
+
+class WindowAttnPadFn(torch.autograd.Function):
+    """WindowAttnFn for a map that is not made of whole windows (swin_transformer.py:150-152 pads it): apply(qkv, bias, table32,
+    heads, shift), bias = the qkv projection's.  The gradient returned for the bias is the PAD tokens' share only; the real
+    tokens' share reaches the parameter through the projection's own node (LinearFn), and autograd adds the two."""
+
+    @staticmethod
+    def forward(ctx, qkv, bias, table32, heads, shift):
+        tab = _c(table32.detach().to(qkv.dtype))
+        b32 = _c(bias.detach().float())
+        out = swin_window_attn_pad(_c(qkv), b32, tab, heads, shift)
+        ctx.save_for_backward(qkv, b32, tab)
+        ctx.heads, ctx.shift, ctx.bias_dtype = heads, shift, bias.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, b32, tab = ctx.saved_tensors
+        dqkv, dtab, dbias = swin_window_attn_pad_bwd(qkv, b32, tab, dout.to(qkv.dtype), ctx.heads, ctx.shift)
+        return dqkv, dbias.to(ctx.bias_dtype), dtab, None, None
 
 
 # ----------------------------------------------------------------------------- classification head (K10)

@@ -53,6 +53,28 @@ def timeit_pair(fa, fb, rounds, inner=5):
     return best[0], best[1]
 
 
+def timeit_pair_median(fa, fb, rounds, inner=5):
+    """two forms of one product, warm, alternating round by round in this process: (median ms of fa, median ms of fb)"""
+    for _ in range(2):
+        fa()
+        fb()
+    ts = ([], [])
+    for _ in range(rounds):
+        for i, fn in enumerate((fa, fb)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(inner):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts[i].append(e0.elapsed_time(e1) / inner)
+    return sorted(ts[0])[rounds // 2], sorted(ts[1])[rounds // 2]
+
+
+# (tokens a side, C, heads) of the four stages of the image encoder at --image-size 512: no side is a multiple of the 7x7 window
+SWIN_512 = ((128, 96, 3), (64, 192, 6), (32, 384, 12), (16, 768, 24))
+
+
 # (N = dY width, K = X width, rows at 64 images) of the weight gradients of the trainable image encoder whose widths are not
 # multiples of 128: stem, stage 1 qkv / proj / fc1 / fc2, patch merging 1, stage 2 qkv / proj / fc1 / fc2
 ENCODER_TN = ((96, 16, 200704), (288, 96, 200704), (96, 96, 200704), (384, 96, 200704), (96, 384, 200704), (192, 384, 50176),
@@ -152,6 +174,52 @@ def main():
                  "# TB/s: 2 (N + K) M bytes / new time\n"
                  "#  N      K        M     new us  before us    TB/s\n" % a.rounds + "\n".join(lines) + "\n")
         print(table, end="", flush=True)
+    # ---- shifted-window attention on the 512-pixel maps: mtmp_swin_window_attn_pad(_bwd) on the un-padded map next to the recipe
+    #      it replaces -- the qkv map copied into a bias-filled map of the padded size, the window-multiple kernels on that map,
+    #      crop (backward: dout zero-padded the same way, dqkv cropped, the pad tokens' dk / dv summed into the bias gradient)
+    pad_table = ""
+    if want("swin_pad"):
+        lines, tot = [], [0.0, 0.0, 0.0, 0.0]
+        n, shift = 64, 3
+        for H, C, heads in SWIN_512:
+            Hp = -(-H // 7) * 7
+            qkv, dout = R(n, H, H, 3 * C), R(n, H, H, C)
+            bias = torch.randn(3 * C, generator=g, device=DEV) * 0.3
+            tab = (torch.randn(4, heads, 64, 64, generator=g, device=DEV) * 0.02)
+            tab[..., 49:] = -30000.0
+            tab = tab.to(BF)
+
+            def copy_fwd():
+                padded = bias.to(BF).expand(n, Hp, Hp, 3 * C).contiguous()
+                padded[:, :H, :H] = qkv
+                return ops.swin_window_attn(padded, tab, heads, shift)[:, :H, :H].contiguous()
+
+            def copy_bwd():
+                padded = bias.to(BF).expand(n, Hp, Hp, 3 * C).contiguous()
+                padded[:, :H, :H] = qkv
+                dpad = torch.zeros(n, Hp, Hp, C, dtype=BF, device=DEV)
+                dpad[:, :H, :H] = dout
+                dq, dtab = ops.swin_window_attn_bwd(padded, tab, dpad, heads, shift)
+                db = dq.sum((0, 1, 2), dtype=torch.float32) - dq[:, :H, :H].sum((0, 1, 2), dtype=torch.float32)
+                return dq[:, :H, :H].contiguous(), dtab, db
+
+            f_new, f_old = timeit_pair_median(lambda: ops.swin_window_attn_pad(qkv, bias, tab, heads, shift), copy_fwd, a.rounds)
+            b_new, b_old = timeit_pair_median(lambda: ops.swin_window_attn_pad_bwd(qkv, bias, tab, dout, heads, shift), copy_bwd, a.rounds)
+            tag = f"[{n},{H},{H},{C}]"
+            rec("swin_pad.fwd" + tag, f_new, bytes_=2.0 * n * H * H * 4 * C)
+            rec("swin_pad.fwd" + tag + ".copy_kernel_crop", f_old)
+            rec("swin_pad.bwd" + tag, b_new, bytes_=2.0 * n * H * H * 8 * C)
+            rec("swin_pad.bwd" + tag + ".copy_kernel_crop", b_old)
+            for i, v in enumerate((f_new, f_old, b_new, b_old)):
+                tot[i] += v
+            lines.append(f"{H:4d} x {H:4d} x {C:4d}  {f_new * 1e3:9.1f}  {f_old * 1e3:9.1f}  {b_new * 1e3:9.1f}  {b_old * 1e3:9.1f}")
+            del qkv, dout
+        lines.append("sum                 " + "".join(f"  {v * 1e3:9.1f}" for v in tot))
+        pad_table = ("# shifted-window attention (shift 3) of 64 images at the four stage shapes of --image-size 512, bf16, one process, warm,\n"
+                     "# forms alternating, median over %d rounds of 5 calls\n"
+                     "# new: mtmp_swin_window_attn_pad / _pad_bwd on the un-padded map; copy: bias-filled padded copy + window-multiple kernel + crop\n"
+                     "#   H      W      C     fwd new us  fwd copy us  bwd new us  bwd copy us\n" % a.rounds + "\n".join(lines) + "\n")
+        print(pad_table, end="", flush=True)
     # ---- attention
     if want("attn"):
         B, N = 64, 1005
@@ -180,6 +248,9 @@ def main():
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "bench_kernels.json"), "w") as fh:
         json.dump(out, fh, indent=1)
+    if pad_table:                    # the padded-window table, next to the JSON
+        with open(os.path.join(os.path.dirname(fh.name), "swin_padded_windows.txt"), "w") as ft:
+            ft.write(pad_table)
     if table:                        # the encoder-width table, next to the JSON
         with open(os.path.join(os.path.dirname(fh.name), "gemm_tn_encoder_widths.txt"), "w") as ft:
             ft.write(table)
