@@ -513,6 +513,16 @@ int mtmp_swin_attn_block(int dtype, const void* x, const float* ln_w, const floa
                          const float* bqkv, const void* table, const void* wproj, const float* bproj, const float* row_scale,
                          void* out, int n_img, int H, int W, int C, int heads, int shift, float scale, const int32_t* rows_live,
                          void* stream);
+/* mtmp_swin_attn_block on a map of ANY size, by the rules of mtmp_swin_window_attn_pad: the window grid covers Hp x Wp = ceil(H/7) 7
+ * x ceil(W/7) 7, the cyclic shift is modulo Hp / Wp, x / out stay [n_img, H, W, C].  A token whose pixel lies at y >= H or x >= W is
+ * a PAD token: a zero row BEHIND norm1 (swin_transformer.py:150-152 pads the normalised map), so its q / k / v are bqkv; it is an
+ * ordinary (unmasked) key; nothing is read or stored at its pixel.  Same arguments and table as mtmp_swin_attn_block.  The caller
+ * passes shift 0 for a padded map of one window; one axis of a single window and the other of several is refused.  H and W
+ * multiples of 7: the kernel of mtmp_swin_attn_block itself (bit-identical). */
+int mtmp_swin_attn_block_pad(int dtype, const void* x, const float* ln_w, const float* ln_b, float eps, const void* wqkv,
+                             const float* bqkv, const void* table, const void* wproj, const float* bproj, const float* row_scale,
+                             void* out, int n_img, int H, int W, int C, int heads, int shift, float scale, const int32_t* rows_live,
+                             void* stream);
 int mtmp_gemm_nt_live(int dtype, const void* a, const void* w, const float* bias, const void* res, void* y, int M, int N, int K,
                       int lda, int ldy, int ldr, int act, float drop_p, unsigned seed, const unsigned* seed_dev, const void* gate,
                       float gate_scale, const float* row_scale, int rows_per_scale, const int32_t* rows_live, void* stream);

@@ -295,11 +295,11 @@ class TRI_MBT_VSLTCLS(nn.Module):
         # With --multiimages 1 the image stream's key length is 4 + 1 + 49 * (images whose time is not the pad value 10), :226-231:
         # the tokens of image j >= that count are masked as keys and read by nothing -- those images are not encoded either
         # (by POSITION, as the reference masks them; an image in front of the count is encoded whatever its time says).
-        # (maps that are multiples of the 7x7 window at every stage: 224 / 448 pixels a side; other sizes take the reference's
-        #  zero-padded windows and encode every image)
+        # (image sides that are multiples of 32, 224 and 512 among them: every stage's map halves exactly, so that hw0 >> 2s is
+        #  the slot table's row count per image at stage s; other sizes -- 200 pixels: 50 -> 25 -> 13 -> 7 -- encode every image)
         skip = (bool(getattr(self.args, "skip_missing_images", 1)) and img.is_cuda
                 and self.args.img_model_type == "swin" and torch.is_tensor(missing) and missing.dim() == 1
-                and img.shape[-2] % 224 == 0 and img.shape[-1] % 224 == 0)
+                and img.shape[-2] % 32 == 0 and img.shape[-1] % 32 == 0)
 
         def encode(**kw):
             slots = None

@@ -22,9 +22,13 @@ the host and cached.  Feature maps whose side is not a multiple of 7 (--image-si
 vector behind norm1, so its q / k / v are the projection's bias -- mtmp_swin_window_attn_pad(_bwd)
 walk the window grid of the PADDED map over the un-padded qkv map, make the pad tokens' fragments
 from the bias in registers and store nothing for them (no padded copy, forward or backward; the pad
-tokens' dk / dv are their share of the bias gradient).  Odd-sized maps are zero-padded in front of a
-patch merging (:34-44).  The present-images-only form (`slots`) is used for maps that are multiples of
-the window at every stage only (the model's choice; the padded kernel honours rows_live).
+tokens' dk / dv are their share of the bias gradient).  The frozen bf16 encoder's narrow stages
+(C = 96 / 192) run the attention half of a block as ONE launch at every map size: mtmp_swin_attn_block on
+whole-window maps, mtmp_swin_attn_block_pad on the others (the pad tokens are zero rows of the normalised
+tile in LDS; q / k / v never reach memory).  Odd-sized maps are zero-padded in front of a patch merging
+(:34-44).  The present-images-only form (`slots`) needs every stage's map to halve exactly -- image sides
+that are multiples of 32, 224 and 512 among them (the model's choice); every launch of the frozen forward,
+the padded kernels included, honours rows_live.
 """
 import contextlib
 from typing import List
@@ -40,7 +44,7 @@ PAD_LOGIT = -30000.0
 # Both on in the product; tools/dbg A/B scripts flip these module attributes (no environment switches in the package).
 _SPLIT_TAIL = True     # stages 3-4 as two half batches on two streams
 _FUSED_MLP = True      # mtmp_swin_ln_linear / mtmp_swin_mlp (C = 96 / 192)
-_FUSED_ATTN = True     # mtmp_swin_attn_block: norm1 -> qkv -> window attention -> proj -> residual in one launch
+_FUSED_ATTN = True     # mtmp_swin_attn_block(_pad): norm1 -> qkv -> window attention -> proj -> residual in one launch
 
 
 def _w(p: torch.Tensor, dtype) -> torch.Tensor:
@@ -249,12 +253,16 @@ class SwinTransformerBlock(nn.Module):
         x2 = x.view(-1, C)
         s_attn, s_mlp = self.draw_scales(n, x.device) if scales is None else scales
         at = self.attn
-        if dt == torch.bfloat16 and C in ops.SWIN_ATTN_BLOCK_WIDTHS and _FUSED_ATTN and H % WS == 0 and W % WS == 0:
-            # stages 1-2: the whole attention half in one launch; the 3C-wide qkv map never exists
-            shift = 0 if WS >= H else at.shift_size[0]
-            x2 = ops.swin_attn_block(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, _w(at.qkv.weight, dt), at.qkv.bias,
-                                     at.additive_table(shift, dt, x.device, acc_order=True), at.num_heads, shift,
-                                     _w(at.proj.weight, dt), at.proj.bias, s_attn).view(-1, C)
+        Hp, Wp = -(-H // WS) * WS, -(-W // WS) * WS           # zero-padded to whole windows (:150-152)
+        if dt == torch.bfloat16 and C in ops.SWIN_ATTN_BLOCK_WIDTHS and _FUSED_ATTN and (WS >= Hp) == (WS >= Wp):
+            # stages 1-2: the whole attention half in one launch; the 3C-wide qkv map never exists.  Maps that are not whole
+            # windows: the pad tokens are zero rows behind norm1 inside the kernel (mtmp_swin_attn_block_pad).  (One side of a
+            # single window and the other of several: the chain below, which raises.)
+            shift = 0 if WS >= Hp else at.shift_size[0]
+            block = ops.swin_attn_block if (Hp, Wp) == (H, W) else ops.swin_attn_block_pad
+            x2 = block(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, _w(at.qkv.weight, dt), at.qkv.bias,
+                       at.additive_table(shift, dt, x.device, acc_order=True), at.num_heads, shift,
+                       _w(at.proj.weight, dt), at.proj.bias, s_attn).view(-1, C)
         else:
             if dt == torch.bfloat16 and C in ops.SWIN_LN_LINEAR_WIDTHS and _FUSED_MLP:
                 a = at(x, norm=self.norm1)

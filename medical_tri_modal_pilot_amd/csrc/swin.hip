@@ -603,7 +603,12 @@ __global__ __launch_bounds__(256, 3) void swin_ln_linear_kernel(const bf16* x, c
 //     key columns in accumulator-register order, so a lane reads its 16 keys of a block as two 16-byte loads;
 //   * the heads' outputs meet in the same LDS tile ([64 tokens][C], bf16 as the unfused chain rounds them), then wave w
 //     computes output channels [32 w, 32 w + 32) of the projection and writes x + scale * (proj + bias) to the token's pixel.
-template <int C>
+// PAD (mtmp_swin_attn_block_pad): H, W need not be multiples of the window -- the rules of swin_wattn_kernel<T, true>: the window grid
+// covers Hp x Wp = whole windows, the shift is modulo Hp / Wp, only the H x W map exists in memory.  A pad token (pixel at y >= H or
+// x >= W) is a ZERO row of the normalised tile, as the 15 window-pad slots are (the reference pads BEHIND norm1,
+// swin_transformer.py:150-152), so its q / k / v leave the accumulators as the qkv bias; it is an ordinary key (PAD_LOGIT belongs
+// to slots 49..63 only); its norm1 load and residual prefetch read token 0 of the map instead, and its output row is not stored.
+template <int C, bool PAD>
 __global__ __launch_bounds__(2 * C, 3) void swin_attn_block_kernel(const bf16* x, const float* ln_w, const float* ln_b, float eps,
                                                                    const bf16* wqkv, const float* bqkv, const bf16* table,
                                                                    const bf16* wproj, const float* bproj, const float* row_scale,
@@ -612,7 +617,8 @@ __global__ __launch_bounds__(2 * C, 3) void swin_attn_block_kernel(const bf16* x
     constexpr int HEADS = C / DH, KC = C / 16, LDO = C + 8, UNR = KC >= 12 ? 4 : KC;     // (UNR: unroll of the k loops)
     __shared__ __attribute__((aligned(16))) bf16 sX[LP * LDO];    // normalised tokens, later the heads' outputs
     const int n_img = rows_live ? min(n_img_max, *rows_live / (H * W)) : n_img_max;
-    const int nWh = H / WS, nWw = W / WS;
+    const int nWh = PAD ? (H + WS - 1) / WS : H / WS, nWw = PAD ? (W + WS - 1) / WS : W / WS;
+    const int Hp = PAD ? nWh * WS : H, Wp = PAD ? nWw * WS : W;
     const int img = blockIdx.x / (nWh * nWw), win = blockIdx.x - img * (nWh * nWw);
     if (img >= n_img) return;                                     // (whole workgroup: no barrier is skipped by part of it)
     const int tid = threadIdx.x, lane = tid & 63, head = tid >> 6, r = lane & 31, half = lane >> 5;
@@ -621,8 +627,9 @@ __global__ __launch_bounds__(2 * C, 3) void swin_attn_block_kernel(const bf16* x
     auto pix = [&](int t) -> long long {                          // token of this window -> its pixel on the UN-shifted map
         const int ty = t / WS, tx = t - ty * WS;
         int yy = wi * WS + ty + shift, xx = wj * WS + tx + shift;
-        if (yy >= H) yy -= H;
-        if (xx >= W) xx -= W;
+        if (yy >= Hp) yy -= Hp;
+        if (xx >= Wp) xx -= Wp;
+        if (PAD && (yy >= H || xx >= W)) return -1;               // pad token: no pixel
         return ((long long)img * H + yy) * W + xx;
     };
     // ---- norm1 of the window's tokens (waves 0 and 1: 32 tokens each, a lane pair per token) -> LDS, bf16
@@ -631,7 +638,9 @@ __global__ __launch_bounds__(2 * C, 3) void swin_attn_block_kernel(const bf16* x
     if (head < LP / TPW) {
         const int tq = TPW * head + (LPT == 2 ? r : (lane & 15)), part = LPT == 2 ? half : (lane >> 4);
         Frag<bf16> xf[KL];
-        const bf16* xrow = x + pix(tq < L ? tq : 0) * C + 8 * part;
+        const long long px = pix(tq < L ? tq : 0);
+        const bool keep = tq < L && (!PAD || px >= 0);            // (window-pad slots and map-pad tokens: zero rows)
+        const bf16* xrow = x + (PAD && px < 0 ? 0 : px) * C + 8 * part;
         float s1 = 0.f;
 #pragma unroll
         for (int c = 0; c < KL; ++c) {
@@ -661,7 +670,7 @@ __global__ __launch_bounds__(2 * C, 3) void swin_attn_block_kernel(const bf16* x
                 y.v[i] = from_f32<bf16>(fmaf((to_f32(xf[c].v[i]) - mean) * rstd, g0[i], o0[i]));
                 y.v[i + 4] = from_f32<bf16>(fmaf((to_f32(xf[c].v[i + 4]) - mean) * rstd, g1[i], o1[i]));
             }
-            frag_store<bf16>(sX + tq * LDO + k, frag_keep(y, tq < L));          // (pad tokens: zero rows)
+            frag_store<bf16>(sX + tq * LDO + k, frag_keep(y, keep));
         }
     }
     __syncthreads();
@@ -727,7 +736,7 @@ __global__ __launch_bounds__(2 * C, 3) void swin_attn_block_kernel(const bf16* x
     for (int tb = 0; tb < 2; ++tb) {
         const int tq = 32 * tb + r;
         pxv[tb] = pix(tq < L ? tq : 0);
-        const bf16* xr = x + pxv[tb] * C + head * DH + 4 * half;
+        const bf16* xr = x + (PAD && pxv[tb] < 0 ? 0 : pxv[tb]) * C + head * DH + 4 * half;
 #pragma unroll
         for (int g = 0; g < 4; ++g) resv[tb][g] = load4<bf16>(xr + 8 * g);
     }
@@ -808,7 +817,7 @@ __global__ __launch_bounds__(2 * C, 3) void swin_attn_block_kernel(const bf16* x
 #pragma unroll
     for (int tb = 0; tb < 2; ++tb) {
         const int tq = 32 * tb + r;
-        if (tq < L) {
+        if (tq < L && (!PAD || pxv[tb] >= 0)) {                   // (a pad token's row is not stored)
             bf16* yo = out + pxv[tb] * C + head * DH + 4 * half;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -984,13 +993,50 @@ extern "C" int mtmp_swin_attn_block(int dtype, const void* x, const float* ln_w,
     MTMP_CHECK_ARG(nwg < (1ll << 31), "mtmp_swin_attn_block: too many windows");
     hipStream_t st = (hipStream_t)stream;
     if (C == 96)
-        hipLaunchKernelGGL(swin_attn_block_kernel<96>, dim3((unsigned)nwg), dim3(192), 0, st, (const bf16*)x, ln_w, ln_b, eps,
+        hipLaunchKernelGGL((swin_attn_block_kernel<96, false>), dim3((unsigned)nwg), dim3(192), 0, st, (const bf16*)x, ln_w, ln_b, eps,
                            (const bf16*)wqkv, bqkv, (const bf16*)table, (const bf16*)wproj, bproj, row_scale, (bf16*)out, n_img, H,
                            W, shift, scale, rows_live);
     else
-        hipLaunchKernelGGL(swin_attn_block_kernel<192>, dim3((unsigned)nwg), dim3(384), 0, st, (const bf16*)x, ln_w, ln_b, eps,
+        hipLaunchKernelGGL((swin_attn_block_kernel<192, false>), dim3((unsigned)nwg), dim3(384), 0, st, (const bf16*)x, ln_w, ln_b, eps,
                            (const bf16*)wqkv, bqkv, (const bf16*)table, (const bf16*)wproj, bproj, row_scale, (bf16*)out, n_img, H,
                            W, shift, scale, rows_live);
     MTMP_CHECK_LAUNCH("mtmp_swin_attn_block");
+    return MTMP_OK;
+}
+
+// mtmp_swin_attn_block on a map of ANY size: the window grid covers the map padded to whole windows (Hp x Wp = ceil(H / 7) 7 x
+// ceil(W / 7) 7, swin_transformer.py:150-152) while x / out stay [n_img, H, W, C]; the pad tokens are zero rows behind norm1, made in
+// the kernel.  Same arguments; the shift is modulo Hp / Wp and the caller passes shift 0 for a padded map of one window; a map
+// with one side of a single window and the other of several is refused (per-axis shift: not built).  H and W multiples of 7:
+// mtmp_swin_attn_block itself (no pad token exists).
+extern "C" int mtmp_swin_attn_block_pad(int dtype, const void* x, const float* ln_w, const float* ln_b, float eps, const void* wqkv,
+                                        const float* bqkv, const void* table, const void* wproj, const float* bproj,
+                                        const float* row_scale, void* out, int n_img, int H, int W, int C, int heads, int shift,
+                                        float scale, const int32_t* rows_live, void* stream) {
+    MTMP_CHECK_ARG(x && ln_w && ln_b && wqkv && bqkv && table && wproj && bproj && out && out != x,
+                   "mtmp_swin_attn_block_pad: null pointer / in place");
+    MTMP_CHECK_ARG(dtype == 1 && (C == 96 || C == 192) && heads * DH == C && n_img > 0 && H > 0 && W > 0 && shift >= 0 && shift < WS,
+                   "mtmp_swin_attn_block_pad: bf16 with C = 96 or 192, heads = C / 32 only (dtype=%d C=%d heads=%d n=%d H=%d W=%d shift=%d)",
+                   dtype, C, heads, n_img, H, W, shift);
+    if (H % WS == 0 && W % WS == 0)
+        return mtmp_swin_attn_block(dtype, x, ln_w, ln_b, eps, wqkv, bqkv, table, wproj, bproj, row_scale, out, n_img, H, W, C, heads,
+                                    shift, scale, rows_live, stream);
+    const int nWh = (H + WS - 1) / WS, nWw = (W + WS - 1) / WS;
+    MTMP_CHECK_ARG((nWh == 1) == (nWw == 1), "mtmp_swin_attn_block_pad: one side of a single window and the other of several is not built "
+                   "(H=%d W=%d)", H, W);
+    MTMP_CHECK_ARG(shift == 0 || nWh > 1, "mtmp_swin_attn_block_pad: a padded map of one window is not shifted (H=%d W=%d shift=%d)", H, W,
+                   shift);
+    const long long nwg = (long long)n_img * nWh * nWw;
+    MTMP_CHECK_ARG(nwg < (1ll << 31), "mtmp_swin_attn_block_pad: too many windows");
+    hipStream_t st = (hipStream_t)stream;
+    if (C == 96)
+        hipLaunchKernelGGL((swin_attn_block_kernel<96, true>), dim3((unsigned)nwg), dim3(192), 0, st, (const bf16*)x, ln_w, ln_b, eps,
+                           (const bf16*)wqkv, bqkv, (const bf16*)table, (const bf16*)wproj, bproj, row_scale, (bf16*)out, n_img, H,
+                           W, shift, scale, rows_live);
+    else
+        hipLaunchKernelGGL((swin_attn_block_kernel<192, true>), dim3((unsigned)nwg), dim3(384), 0, st, (const bf16*)x, ln_w, ln_b, eps,
+                           (const bf16*)wqkv, bqkv, (const bf16*)table, (const bf16*)wproj, bproj, row_scale, (bf16*)out, n_img, H,
+                           W, shift, scale, rows_live);
+    MTMP_CHECK_LAUNCH("mtmp_swin_attn_block_pad");
     return MTMP_OK;
 }

@@ -292,6 +292,19 @@ def swin_attn_block(x, ln_w, ln_b, eps, wqkv, bqkv, table, heads, shift, wproj, 
     return out
 
 
+def swin_attn_block_pad(x, ln_w, ln_b, eps, wqkv, bqkv, table, heads, shift, wproj, bproj, row_scale=None):
+    """swin_attn_block for a map of any size (mtmp_swin_attn_block_pad): the window grid covers the map padded to whole 7x7 windows,
+    whose pad tokens are zero rows behind norm1 made inside the kernel -- x and the result stay [n,H,W,C].  The same table; shift 0
+    for a padded map of one window; a map with one side of a single window and the other of several is refused."""
+    _gpu(x)
+    x = _c(x)
+    n, H, W, C = x.shape
+    out = torch.empty_like(x)
+    call("mtmp_swin_attn_block_pad", _dt(x), _p(x), _p(ln_w), _p(ln_b), float(eps), _p(_c(wqkv)), _p(bqkv), _p(table), _p(_c(wproj)),
+         _p(bproj), _p(row_scale), _p(out), n, H, W, C, heads, int(shift), float((C // heads) ** -0.5), _live(), _stream())
+    return out
+
+
 REDUCE_BATCH_MAX = 8
 # (scheduling switches -- LATE_REDUCTIONS, FOLD_DROPOUT_BWD, DEFER_REDUCTIONS, GROUP_MODE ... -- live in tuning.py)
 
