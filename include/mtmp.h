@@ -535,6 +535,33 @@ int mtmp_gemm_nt_live(int dtype, const void* a, const void* w, const float* bias
  * mtmp_stream_lengths); out: int32[2 B + 1] device -- the `row_start` argument of the packed forms is this whole array. */
 int mtmp_row_starts(const int32_t* kv_len, int32_t* out, int B, int n_max, void* stream);
 
+/* ---- Chest X-ray input chain (additive; ABI stays 6): the reference's loader runs, per image and on CPU workers, PIL's
+ * ImageOps.equalize and one of the torchvision chains of builder/data/dataset_new.py:91-160 (antialiased bilinear Resize,
+ * RandomAffine, CenterCrop, ToTensor; :2094-2096, :2110-2112).  All of it is integer arithmetic in PIL and is reproduced here bit
+ * for bit from the decoded uint8 pixels.
+ *   pixels: uint8 device buffer, the batch's images back to back at arbitrary byte offsets.
+ *   desc:   int32 [n][24] device, one row per image: 0 source byte offset, 1 h, 2 w, 3 Rh, 4 Rw (resized map), 5 / 6 / 7 word offset
+ *           of the horizontal bounds table, of the horizontal weights, taps per weight row (ksize), 8 / 9 / 10 the same for the
+ *           vertical pass, 11 flags (bit 0: apply the affine map), 12..17 the 16.16 words a0..a5 of PIL's nearest-neighbour affine
+ *           (xin = (a2 + a0 x + a1 y) >> 16, yin = (a5 + a3 x + a4 y) >> 16), 18 / 19 crop top / left, 20 output slot, 21 byte offset
+ *           of the resized map in `scratch`, 22..23 zero.
+ *   tables: int32 device; per axis bounds [out][2] = (first source index, taps) and weights [out][ksize] with 22 fractional bits
+ *           (PIL's precompute_coeffs / normalize_coeffs_8bpc), built on the host.
+ * mtmp_cxr_hist: hist uint32 [n][256] += the images' histograms (the caller ZEROES it; integer atomics, order-independent);
+ *   max_pixels = the largest h w of the batch.
+ * mtmp_cxr_resize: scratch uint8 <- equalised (ImageOps.equalize's table from hist, saturated at 255) and resized maps, horizontal
+ *   pass rounded to uint8 before the vertical one.  max_rh / max_rw: the largest Rh / Rw; lds_rows: the most source rows any tile of
+ *   32 resized rows reads (<= 960), i.e. the maximum over images and tiles [r0, r1) of vbounds[r1-1].first + vbounds[r1-1].taps -
+ *   vbounds[r0].first.  The entry point cannot see the tables: a smaller lds_rows than that is a broken precondition (the kernel
+ *   then writes past its LDS rows; the output is undefined).  builder/data/cxr_transform.py computes it with the tables.
+ * mtmp_cxr_affine_crop: out float [n_slots][S][S]; slot_map int32 [n_slots] = image of the slot or -1 (written as zeros).  Per
+ *   pixel: crop offset, affine map if flagged, fetch from scratch (0 outside the map), float / 255 with IEEE division. */
+int mtmp_cxr_hist(const uint8_t* pixels, const int32_t* desc, uint32_t* hist, int n, int max_pixels, void* stream);
+int mtmp_cxr_resize(const uint8_t* pixels, const int32_t* desc, const int32_t* tables, const uint32_t* hist, uint8_t* scratch,
+                    int n, int max_rh, int max_rw, int lds_rows, void* stream);
+int mtmp_cxr_affine_crop(const uint8_t* scratch, const int32_t* desc, const int32_t* slot_map, float* out, int n_slots, int S,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,9 @@ SIGNATURES = {
     "mtmp_adamw_step": (c_int, [c_void_p] * 5 + [c_longlong] + [c_float] * 5 + [c_int, c_float, c_void_p]),
     "mtmp_bottleneck_exchange_fwd": (c_int, [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mtmp_bottleneck_exchange_bwd": (c_int, [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mtmp_cxr_hist": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p]),
+    "mtmp_cxr_resize": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
+    "mtmp_cxr_affine_crop": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),
     "mtmp_dropout_bwd": (c_int, [c_int, c_void_p, c_void_p, c_longlong, c_uint, c_void_p, c_float, c_void_p]),
 }
 

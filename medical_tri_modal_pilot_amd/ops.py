@@ -434,6 +434,32 @@ def image_slots(pattern, present_below: int, hw0: int):
     return out
 
 
+# ---- chest X-ray input chain (csrc/image_prep.hip): equalise, resize, affine, crop, / 255 ------------------------------
+def cxr_hist(pixels, desc, max_pixels: int):
+    """256-bin histograms uint32 [n, 256] (returned as int32 bits) of the n images that `desc` places in the uint8 buffer."""
+    _gpu(pixels, desc)
+    n = desc.shape[0]
+    hist = torch.zeros(n, 256, dtype=torch.int32, device=pixels.device)
+    call("mtmp_cxr_hist", _p(pixels), _p(desc), _p(hist), n, int(max_pixels), _stream())
+    return hist
+
+
+def cxr_prepare(raw):
+    """RawCxrBatch (device) -> float32 [B, 1, S, S] or [B, K, 1, S, S]: the reference loader's equalize + transform chain for
+    every present image, zeros for the slots without one (builder/data/cxr_transform.py holds the plan).  Three launches behind
+    the zero-fill of the histogram table: mtmp_cxr_hist, mtmp_cxr_resize, mtmp_cxr_affine_crop."""
+    _gpu(raw.pixels, raw.desc, raw.tables, raw.slot_map)
+    dev, S = raw.pixels.device, raw.image_size
+    out = torch.empty(raw.out_shape, dtype=torch.float32, device=dev)
+    scratch = torch.empty(max(raw.scratch_bytes, 1), dtype=torch.uint8, device=dev)
+    if raw.n > 0:
+        hist = cxr_hist(raw.pixels, raw.desc, raw.max_pixels)
+        call("mtmp_cxr_resize", _p(raw.pixels), _p(raw.desc), _p(raw.tables), _p(hist), _p(scratch), raw.n, raw.max_rh,
+             raw.max_rw, raw.lds_rows, _stream())
+    call("mtmp_cxr_affine_crop", _p(scratch), _p(raw.desc), _p(raw.slot_map), _p(out), raw.slot_map.numel(), S, _stream())
+    return out
+
+
 # ---- packed token streams (the ragged vital-sign stream without its pad rows) ------------------------------------------
 # A stream is PACKED when its samples' valid rows (bottleneck prefix + CLS + events = kv_len[b]) sit back to back in the
 # [B * N_max, 256] buffers instead of N_max rows apart: `pack` = row_starts(kv_len, N_max), int32[2 B + 1] on the device --

@@ -5,7 +5,8 @@ measures); ``fill_tensor`` / ``fill_state_dict`` overwrite every float tensor of
 ``scale * hash(name, i)`` (exact integer hash -> uniform [-1,1)), so that the golden generator (build
 container, real reference), the tests (CPU restatement, HIP path) and the benchmark can all rebuild the exact
 same 42 M parameters from nothing -- weights are never committed.  tests/golden/filler.py re-exports
-this module.
+this module.  ``make_raw_cxr`` makes decoded-JPEG stand-ins (uint8 arrays of varying size) for the image slots of a
+batch, which ``builder/data/cxr_transform.collate_raw_cxr`` packs for the GPU input chain.
 """
 import zlib
 
@@ -108,3 +109,29 @@ def make_batch(seed: int, B: int, T: int, *, ragged: bool = True, missing_mode: 
     missing = torch.stack([torch.zeros(B), img_missing.float(), txt_missing.float()], 1)
     return dict(x=x, age=age, gen=gen, input_lengths=lens, txt=txt, txt_lengths=txt_len, img=img,
                 img_time=img_time, txt_time=txt_time, y=y, missing=missing, missing_num=mnum)
+
+
+RAW_CXR_SIZES = ((256, 311), (311, 256), (256, 256), (300, 256))     # h x w of the stand-ins (MIMIC-CXR-JPG resized to ~256)
+
+
+def make_raw_cxr(seed: int, img_time: torch.Tensor, sizes=RAW_CXR_SIZES):
+    """Seeded uint8 [h, w] images for the slots of ``make_batch``'s ``img_time`` that hold an image (multi-image batches
+    [B, K]: time != 10; single-image batches [B]: time != -1).  Returns one ``(images, times)`` pair per sample, present
+    images first as the reference's loader lists them (dataset_new.py:2102-2118)."""
+    rng = np.random.default_rng(seed)
+    multi = img_time.dim() == 2
+    t = img_time if multi else img_time.view(-1, 1)
+    samples = []
+    for b in range(t.shape[0]):
+        images, times = [], []
+        for j in range(t.shape[1]):
+            if float(t[b, j]) == (10.0 if multi else -1.0):
+                continue
+            h, w = sizes[int(rng.integers(len(sizes)))]
+            y, x = np.mgrid[0:h, 0:w]
+            a = (70 + 90 * rng.random() + 60 * np.sin(x / (20 + 40 * rng.random())) * np.cos(y / (15 + 30 * rng.random()))
+                 + 40 * (x / w) + rng.normal(0, 10, (h, w)))
+            images.append(np.clip(a, 0, 255).astype(np.uint8))
+            times.append(float(t[b, j]))
+        samples.append((images, times))
+    return samples

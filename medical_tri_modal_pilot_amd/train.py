@@ -9,6 +9,8 @@ build-only flags wired in:
                       rank-seeded batches, initial broadcast from rank 0, ``--batch-size`` is per rank
     --fused-adamw 1   optim.FusedAdamW over the flat buffers (0: torch.optim.AdamW(model.parameters()) as in the reference)
     --hip-graph 1     hipGraph replay of zero_grad + forward + backward (needs --fused-adamw 1)
+    --raw-images 1    the synthetic batches carry uint8 images of varying size (synthetic.make_raw_cxr) as a RawCxrBatch; the
+                      trainer runs the reference loader's equalize / resize / affine / crop chain on the GPU (ops.cxr_prepare)
 
     python -m medical_tri_modal_pilot_amd.train --input-types vslt_img_txt --model tri_mbt_vsltcls \\
         --modality-inclusion train-missing_test-missing --lr-init 1e-5 --batch-size 64 --epochs 1 \\
@@ -51,6 +53,13 @@ def synthetic_loader(args, n_iters: int, rank: int, epoch: int):
                         missing_mode="mixed" if "missing" in args.modality_inclusion else "none", multiimages=multi,
                         img_size=int(args.image_size), n_images=int(getattr(args, "n_images", 3)))
         static = torch.stack([bt["gen"], bt["age"]], 1)
+        if int(getattr(args, "raw_images", 0)) == 1:
+            from .builder.data.cxr_transform import CxrTransform, collate_raw_cxr
+            from .synthetic import make_raw_cxr
+            g = torch.Generator().manual_seed(4241 + 7919 * rank + 104729 * epoch + it)
+            raw = collate_raw_cxr(make_raw_cxr(g.initial_seed(), bt["img_time"]), CxrTransform.from_args(args, train=True),
+                                  int(getattr(args, "n_images", 3)) if multi else 0, generator=g)
+            bt["img"], bt["img_time"] = raw, raw.img_time.half().float()
         yield (bt["x"], static, bt["y"], bt["input_lengths"], bt["img"], bt["img_time"], bt["txt"], bt["txt_lengths"],
                bt["txt_time"], bt["missing"], None, None)
 
@@ -84,6 +93,8 @@ def main(argv=None):
     from .builder.utils.cosine_annealing_with_warmup_v2 import CosineAnnealingWarmupRestarts
     parser = build_parser()
     parser.add_argument("--iters-per-epoch", type=int, default=100, help="len(train_loader) for synthetic data")
+    parser.add_argument("--raw-images", type=int, default=0, choices=[0, 1],
+                        help="1: synthetic batches carry uint8 images; the transform chain runs on the GPU (ops.cxr_prepare)")
     args = parser.parse_args(argv)
     args.dir_root = os.getcwd()
     if int(args.synthetic) != 1:

@@ -220,6 +220,67 @@ def main():
                      "# new: mtmp_swin_window_attn_pad / _pad_bwd on the un-padded map; copy: bias-filled padded copy + window-multiple kernel + crop\n"
                      "#   H      W      C     fwd new us  fwd copy us  bwd new us  bwd copy us\n" % a.rounds + "\n".join(lines) + "\n")
         print(pad_table, end="", flush=True)
+    # ---- chest X-ray input chain (csrc/image_prep.hip): uint8 images -> float batch, three launches
+    cxr_table = ""
+    if want("cxr"):
+        import time
+        import numpy as np
+        from medical_tri_modal_pilot_amd import _lib
+        from medical_tri_modal_pilot_amd.builder.data.cxr_transform import CxrTransform, collate_raw_cxr
+        from medical_tri_modal_pilot_amd.ops import _p, _stream
+        rng = np.random.default_rng(0)
+
+        def source(h, w):
+            y, x = np.mgrid[0:h, 0:w]
+            return np.clip(90 + 60 * np.sin(x / 37.0) * np.cos(y / 23.0) + 40 * (x / w) + rng.normal(0, 12, (h, w)), 0, 255).astype(np.uint8)
+
+        def pil_ms(src, S):
+            """the reference loader's chain on this box's CPU, one core, decode not included; None without PIL"""
+            try:
+                from PIL import Image, ImageOps
+            except ImportError:
+                return None
+            from medical_tri_modal_pilot_amd.builder.data.cxr_transform import affine_matrix
+            tr, im = CxrTransform(S, "resize_affine_crop", True), Image.fromarray(src)
+            rh, rw = tr.resized(*src.shape)
+            top, left = tr.crop(rh, rw)
+            reps = 20
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                r = ImageOps.equalize(im).resize((rw, rh), Image.BILINEAR)
+                r = r.transform((rw, rh), Image.AFFINE, affine_matrix(rw, rh, 3.0, 10, -7, 1.05), Image.NEAREST, fillcolor=0)
+                np.asarray(r.crop((left, top, left + S, top + S)), dtype=np.float32) / 255
+            return (time.perf_counter() - t0) / reps * 1e3
+
+        lines = []
+        for (h, w), S in (((256, 311), 224), ((585, 711), 512)):
+            cpu = pil_ms(source(h, w), S)
+            for n in (64, 192):
+                srcs = [source(h, w) for _ in range(8)]
+                raw = collate_raw_cxr([([srcs[i % 8]], [-1.0]) for i in range(n)], CxrTransform(S, "resize_affine_crop", True), 0,
+                                      generator=torch.Generator().manual_seed(1)).to(DEV)
+                hist = torch.zeros(n, 256, dtype=torch.int32, device=DEV)
+                scratch = torch.empty(raw.scratch_bytes, dtype=torch.uint8, device=DEV)
+                dst = torch.empty(raw.out_shape, device=DEV)
+                t_h = timeit(lambda: _lib.call("mtmp_cxr_hist", _p(raw.pixels), _p(raw.desc), _p(hist), n, raw.max_pixels, _stream()), a.rounds)
+                hist = ops.cxr_hist(raw.pixels, raw.desc, raw.max_pixels)
+                t_r = timeit(lambda: _lib.call("mtmp_cxr_resize", _p(raw.pixels), _p(raw.desc), _p(raw.tables), _p(hist), _p(scratch), n,
+                                               raw.max_rh, raw.max_rw, raw.lds_rows, _stream()), a.rounds)
+                t_a = timeit(lambda: _lib.call("mtmp_cxr_affine_crop", _p(scratch), _p(raw.desc), _p(raw.slot_map), _p(dst), n, S, _stream()), a.rounds)
+                t_all = timeit(lambda: ops.cxr_prepare(raw), a.rounds)
+                tag = f"[{n}x{h}x{w}->{S}]"
+                rec("cxr.hist" + tag, t_h, bytes_=float(n * h * w))
+                rec("cxr.resize" + tag, t_r, bytes_=float(n * h * w + raw.scratch_bytes))
+                rec("cxr.affine_crop" + tag, t_a, bytes_=float(n * S * S * 5))
+                rec("cxr.prepare" + tag, t_all)
+                tot = t_h + t_r + t_a
+                cpu_s = "PIL not installed; 0.39 ms per 256x311 image per core was measured on a CPU-only machine" if cpu is None \
+                    else f"{cpu:7.3f} ms/image/core = {1e3 / cpu:8.0f} images/s/core (PIL {__import__('PIL').__version__}, this box's CPU)"
+                lines.append(f"{n:4d} x {h} x {w} -> {S}: hist {t_h * 1e3:7.1f}  resize {t_r * 1e3:7.1f}  affine_crop {t_a * 1e3:7.1f}  sum {tot * 1e3:8.1f} us"
+                             f"  ({n / tot * 1e3:10.0f} images/s; ops.cxr_prepare with its allocations and zero-fill {t_all * 1e3:8.1f} us); CPU chain: {cpu_s}")
+        cxr_table = ("# chest X-ray input chain, resize_affine_crop, uint8 sources already on the device, one process, warm, median over %d rounds of 5 calls\n"
+                     % a.rounds + "\n".join(lines) + "\n")
+        print(cxr_table, end="", flush=True)
     # ---- attention
     if want("attn"):
         B, N = 64, 1005
@@ -251,6 +312,9 @@ def main():
     if pad_table:                    # the padded-window table, next to the JSON
         with open(os.path.join(os.path.dirname(fh.name), "swin_padded_windows.txt"), "w") as ft:
             ft.write(pad_table)
+    if cxr_table:
+        with open(os.path.join(os.path.dirname(fh.name), "cxr_input_pipeline_table.txt"), "w") as ft:
+            ft.write(cxr_table)
     if table:                        # the encoder-width table, next to the JSON
         with open(os.path.join(os.path.dirname(fh.name), "gemm_tn_encoder_widths.txt"), "w") as ft:
             ft.write(table)
