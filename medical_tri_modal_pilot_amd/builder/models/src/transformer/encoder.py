@@ -81,12 +81,12 @@ class TransformerEncoderLayer(nn.Module):
                          ps[7].reshape(ps[7].shape[0], -1).to(dtype).contiguous())
 
     def _fused_weights(self, dtype):
-        """parts + (W2^T, Wqkv^T, W1^T) -- the K-contiguous operands of the backward's dH / dX products; rebuilt only
+        """ops.FusedWeights: parts + (W2^T, Wqkv^T, W1^T) -- the K-contiguous operands of the backward's dH / dX products; rebuilt only
         when a parameter changed (optimizer step / load_state_dict)."""
         key, parts = self._fused_parts(dtype)
         if parts is not None:
             with torch.no_grad():
-                self._fused = parts + (parts[3].t().contiguous(), parts[0].t().contiguous(), parts[2].t().contiguous())
+                self._fused = ops.FusedWeights(*parts, parts[3].t().contiguous(), parts[0].t().contiguous(), parts[2].t().contiguous())
             self._fused_key = key
         return self._fused
 
@@ -107,7 +107,7 @@ class TransformerEncoderLayer(nn.Module):
                 else:
                     w2t, wqkvt, w1t = (torch.stack([p[j] for _, _, p in stale]).transpose(1, 2).contiguous() for j in (3, 0, 2))
             for i, (blk, key, parts) in enumerate(stale):
-                blk._fused, blk._fused_key = parts + (w2t[i], wqkvt[i], w1t[i]), key
+                blk._fused, blk._fused_key = ops.FusedWeights(*parts, w2t[i], wqkvt[i], w1t[i]), key
         return [blk._fused for blk in blocks]
 
     def param_list(self):

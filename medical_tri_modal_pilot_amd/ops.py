@@ -8,6 +8,7 @@ that are not on a GPU raise.
 """
 import contextlib
 import ctypes
+from collections import namedtuple
 from typing import Optional
 
 import torch
@@ -1395,8 +1396,21 @@ class StreamInputsFn(torch.autograd.Function):
 # remaining dX products fused with the backward of the LayerNorm in front of them (mtmp_gemm_lnbwd).
 # No library GEMM is left on the path.  Activations needed by the backward
 # are kept (HBM is 288 GB; one vslt layer at B=64, T=1000 keeps ~0.4 GB in bf16).
-PARAMS_PER_LAYER = 14     # g1, b1, wq, bq, wk, bk, wv, bv, g2, b2, w1, c1, w2, c2
+PARAMS_PER_LAYER = 14
+P_G1, P_B1, P_WQ, P_BQ, P_WK, P_BK, P_WV, P_BV, P_G2, P_B2, P_W1, P_C1, P_W2, P_C2 = range(PARAMS_PER_LAYER)   # their order
 
+
+# A layer's derived weights in the compute dtype (encoder.py fused_weights_of builds them): [Wq; Wk; Wv] [768,256], its bias (fp32),
+# W1 [1024,256], W2 [256,1024] and the K-contiguous operands of the backward's dH / dX products.  The layer functions take any
+# 7-sequence in this order.
+FusedWeights = namedtuple("FusedWeights", "wqkv bqkv w1 w2 w2t wqkvt w1t")
+
+# What one layer's forward keeps of one stream for its backward; opaque to callers, who hand it to the matching backward.
+#   o, r1     cls_layer_forward: of the CLS rows only ([B,256]); r1 with ffn_rows: the gathered B * R rows the FFN ran on
+#   pack      row_starts() of a PACKED stream;  ffn_rows: layer_forward_grouped(ffn_rows=R)
+#   cls_rows  cls_layer_forward: where the backward adds the CLS rows' residual gradient;  cls_tok: their row within a sample
+LayerSaved = namedtuple("LayerSaved", "z kv_len g1 g2 wqkvt w1t w2t xn1 st1 qkv o lse r1 xn2 st2 h drop_p seeds hsign "
+                                      "pack ffn_rows cls_rows cls_tok", defaults=(None,) * 4)
 
 
 def _packed_full(rows2d, B, N):
@@ -1407,19 +1421,18 @@ def _packed_full(rows2d, B, N):
 
 
 def layer_forward(z, kv_len, P, fused, drop_p, seeds, pack=None):
-    """z [B,N,256] contiguous.  P: the 14 parameters; fused: (wqkv, bqkv, w1, w2, w2^T, wqkv^T, w1^T) in compute dtype.
-    Returns (out [B,N,256], saved tuple).
+    """z [B,N,256] contiguous.  P: the 14 parameters; fused: FusedWeights (or its seven tensors in that order).
+    Returns (out [B,N,256], LayerSaved).
     pack (row_starts(kv_len, N)): z is a PACKED stream buffer (the samples' kv_len rows back to back) and so is `out`.  This
     single-stream form (the fp32 parity build's) reads the row count on the HOST -- one sync, no hipGraph -- and runs the row
     kernels on the live rows as dense [live, C] matrices; the attention kernels address the samples through pack exactly as the
     bf16 grouped launches do (layer_forward_grouped takes the count from the device instead)."""
     B, N, D = z.shape
     M = B * N
-    g1, b1, g2, b2, c1, c2 = P[0], P[1], P[8], P[9], P[11], P[13]
-    wqkv, bqkv, w1c, w2c, w2t, wqkvt, w1t = fused
+    f = FusedWeights._make(fused)
     live = M if pack is None else int(pack[B])
     z2 = z.view(M, D)[:live]
-    qkv, xn1, st1, knorm = ln_gemm_qkv(z2, g1, b1, wqkv, bqkv)
+    qkv, xn1, st1, knorm = ln_gemm_qkv(z2, P[P_G1], P[P_B1], f.wqkv, f.bqkv)
     if pack is None:
         qkv = qkv.view(B, N, 3 * D)
         o, r1, lse = attn_fwd(qkv, kv_len, res=z, knorm=knorm)
@@ -1427,9 +1440,9 @@ def layer_forward(z, kv_len, P, fused, drop_p, seeds, pack=None):
         qkv = _packed_full(qkv, B, N)
         (o,), (r1,), (lse,) = attn_fwd_grouped([qkv], [kv_len], [z], [knorm], [pack])
     r1_2 = r1.view(M, D)[:live]
-    h, xn2, st2, hsign = ln_gemm(r1_2, g2, b2, w1c, c1, 4 * D, relu=True, drop_p=drop_p, seed=seeds[0], want_signs=True)
-    out = gemm_nt(h, w2c, c2, res2d=r1_2, drop_p=drop_p, seed=seeds[1])
-    saved = (z, kv_len, g1, g2, wqkvt, w1t, w2t, xn1, st1, qkv, o, lse, r1, xn2, st2, h, drop_p, seeds, hsign, pack)
+    h, xn2, st2, hsign = ln_gemm(r1_2, P[P_G2], P[P_B2], f.w1, P[P_C1], 4 * D, relu=True, drop_p=drop_p, seed=seeds[0], want_signs=True)
+    out = gemm_nt(h, f.w2, P[P_C2], res2d=r1_2, drop_p=drop_p, seed=seeds[1])
+    saved = LayerSaved(z, kv_len, P[P_G1], P[P_G2], f.wqkvt, f.w1t, f.w2t, xn1, st1, qkv, o, lse, r1, xn2, st2, h, drop_p, seeds, hsign, pack)
     return (out.view(B, N, D) if pack is None else _packed_full(out, B, N)), saved
 
 
@@ -1460,57 +1473,88 @@ class GradSink:
         return self.ok and self.flat.claim(self.idx)
 
 
+# ---- the pieces shared by the three layer backwards
+# Where a layer backward's five gradient launches write: slices of the flat gradient -- (dW, db) for gemm_tn, (dgamma | dbeta) for
+# gemm_lnbwd -- or None = a fresh tensor each.
+_GradDst = namedtuple("_GradDst", "w2 w1 gb2 wqkv gb1")
+_NO_DST = _GradDst(None, None, None, None, None)
+
+
+def _grad_dst(sink):
+    """-> (sink if this backward writes through it else None, its _GradDst)"""
+    if sink is None or not sink.usable():
+        return None, _NO_DST
+    return sink, _GradDst((sink.w2, sink.c2), (sink.w1, sink.c1), sink.gb2, (sink.wqkv, sink.bqkv), sink.gb1)
+
+
+def _ffn_bwd_head(sv, d_out):
+    """(dH, dY2) of out = drop2(h w2^T + c2) + r1 for d_out [rows,256], the rows the FFN ran on.
+    dH = dY2 W2, gated by h > 0 (which encodes ReLU and drop1's mask) in the GEMM epilogue: from the forward's sign bits
+    (bf16: M N / 8 bytes of gate instead of re-reading h) or, in the fp32 build, from h itself.  With the sign-bit kernel the
+    backward of drop2 (dY2 = dropout_bwd(d_out)) rides on its operand load: one launch and one read of d_out less."""
+    p, seeds, hsign = sv.drop_p, sv.seeds, sv.hsign
+    if hsign is not None and p > 0 and tuning.FOLD_DROPOUT_BWD:
+        return gemm_nt_signs(d_out, sv.w2t, hsign, 1.0 / (1.0 - p), drop_p=p, seed=seeds[1])
+    dy2 = dropout_bwd(d_out, seeds[1], p) if p > 0 else d_out
+    if hsign is not None:
+        return gemm_nt_signs(dy2, sv.w2t, hsign, 1.0 / (1.0 - p)), dy2
+    return gemm_nt(dy2, sv.w2t, gate=sv.h, gate_scale=1.0 / (1.0 - p)), dy2
+
+
+def _param_grads(dg1, db1, dwqkv, dbqkv, dg2, db2, dw1, dc1, dw2, dc2):
+    """the 14 gradients in PARAMS order (fp32; weights as 2-D [out,in])"""
+    D = D_MODEL
+    return (dg1, db1, dwqkv[:D], dbqkv[:D], dwqkv[D:2 * D], dbqkv[D:2 * D], dwqkv[2 * D:], dbqkv[2 * D:], dg2, db2, dw1, dc1, dw2, dc2)
+
+
+def _finish_reductions(red, sinks, late):
+    """The end of a layer backward: `red`, its deferred reductions (None or empty: there are none), and `sinks`, those it wrote
+    through.  late: a list -- the caller issues the reduction launch (and marks the gradients ready) later on this stream, behind
+    the next bottleneck exchange, which needs dz but none of the parameter gradients (FusionStackFn.backward, _flush_late)."""
+    if late is not None and red:
+        late.append((red, sinks))
+        return
+    if red:
+        reduce_batch(red)
+    for sk in sinks:
+        sk.flat.mark_ready(sk.idx)
+
+
+def _flush_late(late):
+    for red, sinks in late:
+        reduce_batch(red)
+        for sk in sinks:
+            sk.flat.mark_ready(sk.idx)
+    del late[:]
+
+
 def layer_backward(saved, d_out, sink=None, late=None):
-    """late: a list -- the layer's reduction launch is not issued here but handed back through it (see the end of this function).
-    d_out [B,N,256] contiguous, compute dtype.  Returns (dz [B,N,256], 14 parameter gradients (fp32,
-    in PARAMS order; weights as 2-D [out,in])) -- or (dz, None) when the gradients went straight into
-    the flat gradient buffer through `sink`."""
-    z, kv_len, g1, g2, wqkvt, w1t, w2t, xn1, st1, qkv, o, lse, r1, xn2, st2, h, p, seeds, hsign = saved[:19]
-    pack = saved[19] if len(saved) > 19 else None           # (layer_forward's packed single-stream form: rows counted on the host)
-    B, N, D = z.shape
+    """d_out [B,N,256] contiguous, compute dtype.  Returns (dz [B,N,256], 14 parameter gradients (_param_grads)) -- or (dz, None)
+    when the gradients went straight into the flat gradient buffer through `sink`.  late: see _finish_reductions."""
+    sv = saved
+    B, N, D = sv.z.shape
     M = B * N
+    pack = sv.pack                                       # (layer_forward's packed single-stream form: rows counted on the host)
     live = M if pack is None else int(pack[B])
     d_out = d_out.view(M, D)[:live]
-    # ---- FFN: out = drop2(h w2^T + c2) + r1,  h = drop1(relu(LN2(r1) w1^T + c1))
-    direct = sink is not None and sink.usable()
+    sink, dst = _grad_dst(sink)
     red = [] if tuning.DEFER_REDUCTIONS else None        # this layer's seven gradient reductions, issued as ONE launch at the end
-    # dH = dY2 W2, gated by h > 0 (which encodes ReLU and drop1's mask) in the GEMM epilogue: from the forward's sign bits
-    # (bf16: M N / 8 bytes of gate instead of re-reading h) or, in the fp32 build, from h itself.  With the sign-bit kernel the
-    # backward of drop2 (dY2 = dropout_bwd(d_out)) rides on its operand load: one launch and one read of d_out less.
-    if hsign is not None and p > 0 and tuning.FOLD_DROPOUT_BWD:
-        dh, dy2 = gemm_nt_signs(d_out, w2t, hsign, 1.0 / (1.0 - p), drop_p=p, seed=seeds[1])
-    else:
-        dy2 = dropout_bwd(d_out, seeds[1], p) if p > 0 else d_out
-        if hsign is not None:
-            dh = gemm_nt_signs(dy2, w2t, hsign, 1.0 / (1.0 - p))
-        else:
-            dh = gemm_nt(dy2, w2t, gate=h, gate_scale=1.0 / (1.0 - p))
-    dw2, dc2 = gemm_tn(dy2, h, out=(sink.w2, sink.c2) if direct else None, defer=red)       # [256,1024], [256]
-    dw1, dc1 = gemm_tn(dh, xn2, out=(sink.w1, sink.c1) if direct else None, defer=red)      # [1024,256], [1024]
+    # ---- FFN: out = drop2(h w2^T + c2) + r1,  h = drop1(relu(LN2(r1) w1^T + c1))
+    dh, dy2 = _ffn_bwd_head(sv, d_out)
+    dw2, dc2 = gemm_tn(dy2, sv.h, out=dst.w2, defer=red)       # [256,1024], [256]
+    dw1, dc1 = gemm_tn(dh, sv.xn2, out=dst.w1, defer=red)      # [1024,256], [1024]
     # dXn2 = dH W1 and the backward of LN2 (+ the residual gradient) in one launch; the M x 256 product stays in LDS
-    dr1, dg2, db2 = gemm_lnbwd(dh, w1t, r1.view(M, D)[:live], st2, g2, d_res2d=d_out, gb_out=sink.gb2 if direct else None, defer=red)
+    dr1, dg2, db2 = gemm_lnbwd(dh, sv.w1t, sv.r1.view(M, D)[:live], sv.st2, sv.g2, d_res2d=d_out, gb_out=dst.gb2, defer=red)
     # ---- attention: r1 = z + o  ->  d_o = dr1
     if pack is None:
-        dqkv = attn_bwd(qkv, o, dr1.view(B, N, D), lse, kv_len).view(M, 3 * D)
+        dqkv = attn_bwd(sv.qkv, sv.o, dr1.view(B, N, D), sv.lse, sv.kv_len).view(M, 3 * D)
     else:
-        dqkv = attn_bwd_grouped([qkv], [o], [_packed_full(dr1, B, N)], [lse], [kv_len], [pack])[0].view(M, 3 * D)[:live]
-    dwqkv, dbqkv = gemm_tn(dqkv, xn1, out=(sink.wqkv, sink.bqkv) if direct else None, defer=red)   # [768,256], [768]
-    dz, dg1, db1 = gemm_lnbwd(dqkv, wqkvt, z.view(M, D)[:live], st1, g1, d_res2d=dr1, gb_out=sink.gb1 if direct else None, defer=red)
-    if late is not None and red:
-        # the caller issues this layer's reduction (and marks the gradients ready) later on this stream -- behind the next
-        # bottleneck exchange, which needs dz but none of the parameter gradients (FusionStackFn.backward)
-        late.append((red, sink if direct else None))
-    else:
-        if red:
-            reduce_batch(red)
-        if direct:
-            sink.flat.mark_ready(sink.idx)
+        dqkv = attn_bwd_grouped([sv.qkv], [sv.o], [_packed_full(dr1, B, N)], [sv.lse], [sv.kv_len], [pack])[0].view(M, 3 * D)[:live]
+    dwqkv, dbqkv = gemm_tn(dqkv, sv.xn1, out=dst.wqkv, defer=red)   # [768,256], [768]
+    dz, dg1, db1 = gemm_lnbwd(dqkv, sv.wqkvt, sv.z.view(M, D)[:live], sv.st1, sv.g1, d_res2d=dr1, gb_out=dst.gb1, defer=red)
+    _finish_reductions(red, [] if sink is None else [sink], late)
     dz = dz.view(B, N, D) if pack is None else _packed_full(dz, B, N)
-    if direct:
-        return dz, None
-    grads = (dg1, db1, dwqkv[:D], dbqkv[:D], dwqkv[D:2 * D], dbqkv[D:2 * D], dwqkv[2 * D:], dbqkv[2 * D:],
-             dg2, db2, dw1, dc1, dw2, dc2)
-    return dz, grads
+    return dz, None if sink is not None else _param_grads(dg1, db1, dwqkv, dbqkv, dg2, db2, dw1, dc1, dw2, dc2)
 
 
 # ----------------------------------------------------------------------------- the last layer of a CLS-only reader
@@ -1557,65 +1601,52 @@ def _cls_rows(B, N, cls_tok, dev):
 
 
 def cls_layer_forward(z, kv_len, P, fused, drop_p, seeds, pack, cls_tok):
-    """The last layer for a reader of the CLS row only: z [B,N,256] (padded, or packed with `pack`) -> (out_cls [B,256], saved)."""
+    """The last layer for a reader of the CLS row only: z [B,N,256] (padded, or packed with `pack`) -> (out_cls [B,256], LayerSaved)."""
     B, N, D = z.shape
-    g1, b1, g2, b2, c1, c2 = P[0], P[1], P[8], P[9], P[11], P[13]
-    wqkv, bqkv, w1c, w2c, w2t, wqkvt, w1t = fused
+    f = FusedWeights._make(fused)
     z2 = z.view(B * N, D)
     if pack is not None:                               # (bf16: the grouped form knows the live row count)
-        qkv, xn1, st1 = (t[0] for t in ln_gemm_qkv_grouped([z2], [g1], [b1], [wqkv], [bqkv], [pack])[:3])
+        qkv, xn1, st1 = (t[0] for t in ln_gemm_qkv_grouped([z2], [P[P_G1]], [P[P_B1]], [f.wqkv], [f.bqkv], [pack])[:3])
     else:
-        qkv, xn1, st1 = ln_gemm(z2, g1, b1, wqkv, bqkv, 3 * D)
+        qkv, xn1, st1 = ln_gemm(z2, P[P_G1], P[P_B1], f.wqkv, f.bqkv, 3 * D)
     qkv = qkv.view(B, N, 3 * D)
     o_cls, r1, lse = attn_cls_fwd(qkv, z, kv_len, pack, cls_tok)
-    h, xn2, st2, hsign = ln_gemm(r1, g2, b2, w1c, c1, 4 * D, relu=True, drop_p=drop_p, seed=seeds[0], want_signs=True)
-    out = gemm_nt(h, w2c, c2, res2d=r1, drop_p=drop_p, seed=seeds[1])
+    h, xn2, st2, hsign = ln_gemm(r1, P[P_G2], P[P_B2], f.w1, P[P_C1], 4 * D, relu=True, drop_p=drop_p, seed=seeds[0], want_signs=True)
+    out = gemm_nt(h, f.w2, P[P_C2], res2d=r1, drop_p=drop_p, seed=seeds[1])
     # the CLS rows of the stream buffer, for the backward's residual add: a packed stream's row starts AS THEY ARE (int32; the
     # backward adds into the view that begins at row cls_tok -- `pack[:B].long() + cls_tok` was two launches in front of the head)
     rows = pack[:B] if pack is not None else _cls_rows(B, N, cls_tok, z.device)
-    return out, (z, kv_len, g1, g2, wqkvt, w1t, w2t, xn1, st1, qkv, o_cls, lse, r1, xn2, st2, h, drop_p, seeds, hsign, pack, rows, cls_tok)
+    return out, LayerSaved(z, kv_len, P[P_G1], P[P_G2], f.wqkvt, f.w1t, f.w2t, xn1, st1, qkv, o_cls, lse, r1, xn2, st2, h, drop_p, seeds,
+                           hsign, pack, cls_rows=rows, cls_tok=cls_tok)
 
 
 def cls_layer_backward(saved, d_cls, sink=None, late=None):
     """d_cls [B,256] (gradient of cls_layer_forward's output) -> (dz [B,N,256], 14 parameter gradients | None), as layer_backward."""
-    z, kv_len, g1, g2, wqkvt, w1t, w2t, xn1, st1, qkv, o_cls, lse, r1, xn2, st2, h, p, seeds, hsign, pack, rows, cls_tok = saved
-    B, N, D = z.shape
+    sv = saved
+    B, N, D = sv.z.shape
     M = B * N
-    d_out = _c(d_cls).to(z.dtype)
-    direct = sink is not None and sink.usable()
+    pack, cls_tok = sv.pack, sv.cls_tok
+    d_out = _c(d_cls).to(sv.z.dtype)
+    sink, dst = _grad_dst(sink)
     red = [] if tuning.DEFER_REDUCTIONS else None
     # ---- FFN of the B CLS rows
-    if hsign is not None and p > 0 and tuning.FOLD_DROPOUT_BWD:
-        dh, dy2 = gemm_nt_signs(d_out, w2t, hsign, 1.0 / (1.0 - p), drop_p=p, seed=seeds[1])
-    else:
-        dy2 = dropout_bwd(d_out, seeds[1], p) if p > 0 else d_out
-        dh = gemm_nt_signs(dy2, w2t, hsign, 1.0 / (1.0 - p)) if hsign is not None else gemm_nt(dy2, w2t, gate=h, gate_scale=1.0 / (1.0 - p))
-    dw2, dc2 = gemm_tn(dy2, h, out=(sink.w2, sink.c2) if direct else None, defer=red)
-    dw1, dc1 = gemm_tn(dh, xn2, out=(sink.w1, sink.c1) if direct else None, defer=red)
-    dr1, dg2, db2 = gemm_lnbwd(dh, w1t, r1, st2, g2, d_res2d=d_out, gb_out=sink.gb2 if direct else None, defer=red)
+    dh, dy2 = _ffn_bwd_head(sv, d_out)
+    dw2, dc2 = gemm_tn(dy2, sv.h, out=dst.w2, defer=red)
+    dw1, dc1 = gemm_tn(dh, sv.xn2, out=dst.w1, defer=red)
+    dr1, dg2, db2 = gemm_lnbwd(dh, sv.w1t, sv.r1, sv.st2, sv.g2, d_res2d=d_out, gb_out=dst.gb2, defer=red)
     # ---- attention of the CLS query: dense dK / dV (and a dQ that is zero outside the CLS rows), then the projection's backward
-    dqkv = attn_cls_bwd(qkv, o_cls, dr1, lse, kv_len, pack, cls_tok).view(M, 3 * D)
-    z2 = z.view(M, D)
+    dqkv = attn_cls_bwd(sv.qkv, sv.o, dr1, sv.lse, sv.kv_len, pack, cls_tok).view(M, 3 * D)
+    z2 = sv.z.view(M, D)
     if pack is not None:
-        dwqkv, dbqkv = gemm_tn_grouped([dqkv], [xn1], [(sink.wqkv, sink.bqkv) if direct else None], [red], [pack])[0]
-        dz, dg1, db1 = gemm_lnbwd_grouped([dqkv], [wqkvt], [z2], [st1], [g1], [None], [sink.gb1 if direct else None], [red], [pack])[0]
+        dwqkv, dbqkv = gemm_tn_grouped([dqkv], [sv.xn1], [dst.wqkv], [red], [pack])[0]
+        dz, dg1, db1 = gemm_lnbwd_grouped([dqkv], [sv.wqkvt], [z2], [sv.st1], [sv.g1], [None], [dst.gb1], [red], [pack])[0]
     else:
-        dwqkv, dbqkv = gemm_tn(dqkv, xn1, out=(sink.wqkv, sink.bqkv) if direct else None, defer=red)
-        dz, dg1, db1 = gemm_lnbwd(dqkv, wqkvt, z2, st1, g1, d_res2d=None, gb_out=sink.gb1 if direct else None, defer=red)
-    # r1 = z + o: the CLS rows' residual gradient (packed: `rows` are the samples' first rows, the CLS row lies cls_tok behind)
-    (dz[cls_tok:] if pack is not None else dz).index_add_(0, rows, dr1)
-    if late is not None and red:
-        late.append((red, sink if direct else None))
-    else:
-        if red:
-            reduce_batch(red)
-        if direct:
-            sink.flat.mark_ready(sink.idx)
-    if direct:
-        return dz.view(B, N, D), None
-    grads = (dg1, db1, dwqkv[:D], dbqkv[:D], dwqkv[D:2 * D], dbqkv[D:2 * D], dwqkv[2 * D:], dbqkv[2 * D:],
-             dg2, db2, dw1, dc1, dw2, dc2)
-    return dz.view(B, N, D), grads
+        dwqkv, dbqkv = gemm_tn(dqkv, sv.xn1, out=dst.wqkv, defer=red)
+        dz, dg1, db1 = gemm_lnbwd(dqkv, sv.wqkvt, z2, sv.st1, sv.g1, d_res2d=None, gb_out=dst.gb1, defer=red)
+    # r1 = z + o: the CLS rows' residual gradient (packed: `cls_rows` are the samples' first rows, the CLS row lies cls_tok behind)
+    (dz[cls_tok:] if pack is not None else dz).index_add_(0, sv.cls_rows, dr1)
+    _finish_reductions(red, [] if sink is None else [sink], late)
+    return dz.view(B, N, D), None if sink is not None else _param_grads(dg1, db1, dwqkv, dbqkv, dg2, db2, dw1, dc1, dw2, dc2)
 
 
 # One launch per layer step over the active streams (bf16): csrc/common.hip.h, Grouped.  The three streams of a fusion layer are
@@ -1639,9 +1670,10 @@ def layer_forward_grouped(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ff
     B, D = zs[0].shape[0], D_MODEL
     Ns = [z.shape[1] for z in zs]
     packs = [None] * n if packs is None else list(packs)
+    par = lambda k: [P[k] for P in Ps]
+    f = FusedWeights._make(zip(*fuseds))               # every field: the list over the streams
     z2 = [z.view(B * N, D) for z, N in zip(zs, Ns)]
-    qkv, xn1, st1, knorm = ln_gemm_qkv_grouped(z2, [P[0] for P in Ps], [P[1] for P in Ps], [f[0] for f in fuseds], [f[1] for f in fuseds],
-                                               packs)
+    qkv, xn1, st1, knorm = ln_gemm_qkv_grouped(z2, par(P_G1), par(P_B1), f.wqkv, f.bqkv, packs)
     qkv = [q.view(B, N, 3 * D) for q, N in zip(qkv, Ns)]
     o, r1, lse = attn_fwd_grouped(qkv, kv_lens, list(zs), knorm, packs)
     R = ffn_rows
@@ -1651,9 +1683,8 @@ def layer_forward_grouped(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ff
         r1_2 = [r[:, :R].reshape(B * R, D) for r in r1]            # the rows somebody reads, gathered (B * R x 256 each)
     else:
         r1_2 = [r.view(B * N, D) for r, N in zip(r1, Ns)]
-    h, xn2, st2, hsign = ln_gemm_signs_grouped(r1_2, [P[8] for P in Ps], [P[9] for P in Ps], [f[2] for f in fuseds],
-                                               [P[11] for P in Ps], 4 * D, drop_p, [sd[0] for sd in seeds], packs)
-    out = gemm_nt_grouped(h, [f[3] for f in fuseds], [P[13] for P in Ps], r1_2, drop_p, [sd[1] for sd in seeds], packs)
+    h, xn2, st2, hsign = ln_gemm_signs_grouped(r1_2, par(P_G2), par(P_B2), f.w1, par(P_C1), 4 * D, drop_p, [sd[0] for sd in seeds], packs)
+    out = gemm_nt_grouped(h, f.w2, par(P_C2), r1_2, drop_p, [sd[1] for sd in seeds], packs)
     if R is not None:
         # zeros, not empty: when this layer closes a graph segment these buffers become segment boundaries / outputs of the autograd
         # node; nobody reads the other rows today, and a later reader (a dump, a NaN check) must not meet recycled memory
@@ -1661,64 +1692,42 @@ def layer_forward_grouped(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ff
         for f_, o_ in zip(full, out):
             f_[:, :R] = o_.view(B, R, D)
         out = full
-    saved = [(zs[i], kv_lens[i], Ps[i][0], Ps[i][8], fuseds[i][5], fuseds[i][6], fuseds[i][4], xn1[i], st1[i], qkv[i], o[i], lse[i],
-              r1_2[i] if R is not None else r1[i], xn2[i], st2[i], h[i], drop_p, seeds[i], hsign[i], packs[i], R) for i in range(n)]
+    saved = [LayerSaved(zs[i], kv_lens[i], Ps[i][P_G1], Ps[i][P_G2], f.wqkvt[i], f.w1t[i], f.w2t[i], xn1[i], st1[i], qkv[i], o[i], lse[i],
+                        r1_2[i] if R is not None else r1[i], xn2[i], st2[i], h[i], drop_p, seeds[i], hsign[i], packs[i], R) for i in range(n)]
     return [out[i].view(B, Ns[i], D) for i in range(n)], saved
 
 
 def layer_backward_grouped(saveds, d_outs, sinks, late):
     """layer_backward for the active streams of one fusion layer, one launch per step.  Returns (list of dz, list of
     per-stream gradient tuples | None) like layer_backward; the reductions of ALL streams go into `late` as one entry."""
-    n = len(saveds)
-    B, D = saveds[0][0].shape[0], D_MODEL
-    Ns = [sv[0].shape[1] for sv in saveds]
+    n = len(d_outs)
+    sv = LayerSaved._make(zip(*saveds))                # every field: the tuple over the streams
+    B, D = sv.z[0].shape[0], D_MODEL
+    Ns = [z.shape[1] for z in sv.z]
     Ms = [B * N for N in Ns]
-    p = saveds[0][16]
+    p, R, packs = sv.drop_p[0], sv.ffn_rows[0], list(sv.pack)
     d_out = [d.view(M, D) for d, M in zip(d_outs, Ms)]
-    direct = [sk is not None and sk.usable() for sk in sinks]
+    sinks, dst = zip(*[_grad_dst(sk) for sk in sinks])
     reds = [[] for _ in range(n)]
-    col = lambda k: [sv[k] for sv in saveds]
-    z, g1, g2, wqkvt, w1t, w2t, xn1, st1, qkv, o, lse, r1, xn2, st2, h, hsign = (col(0), col(2), col(3), col(4), col(5), col(6), col(7),
-                                                                              col(8), col(9), col(10), col(11), col(12), col(13),
-                                                                              col(14), col(15), col(18))
-    kv = col(1)
-    seeds = col(17)
-    packs = [sv[19] if len(sv) > 19 else None for sv in saveds]
-    R = saveds[0][20] if len(saveds[0]) > 20 else None
     if R is not None:                     # the FFN half ran on rows 0..R-1 of every sample: so does its backward
         d_out = [d.view(B, N, D)[:, :R].reshape(B * R, D) for d, N in zip(d_out, Ns)]
-    dh, dy2 = gemm_nt_signs_drop_grouped(d_out, w2t, hsign, 1.0 / (1.0 - p), p, [sd[1] for sd in seeds], packs)
-    gw2 = gemm_tn_grouped(dy2, h, [(sinks[i].w2, sinks[i].c2) if direct[i] else None for i in range(n)], reds, packs)
-    gw1 = gemm_tn_grouped(dh, xn2, [(sinks[i].w1, sinks[i].c1) if direct[i] else None for i in range(n)], reds, packs)
-    r1_2 = [r.view(-1, D) for r in r1]
-    l2 = gemm_lnbwd_grouped(dh, w1t, r1_2, st2, g2, d_out, [sinks[i].gb2 if direct[i] else None for i in range(n)], reds, packs)
+    dh, dy2 = gemm_nt_signs_drop_grouped(d_out, sv.w2t, sv.hsign, 1.0 / (1.0 - p), p, [sd[1] for sd in sv.seeds], packs)
+    gw2 = gemm_tn_grouped(dy2, sv.h, [d.w2 for d in dst], reds, packs)
+    gw1 = gemm_tn_grouped(dh, sv.xn2, [d.w1 for d in dst], reds, packs)
+    r1_2 = [r.view(-1, D) for r in sv.r1]
+    l2 = gemm_lnbwd_grouped(dh, sv.w1t, r1_2, sv.st2, sv.g2, d_out, [d.gb2 for d in dst], reds, packs)
     dr1 = [t[0] for t in l2]
     if R is not None:                     # r1's gradient is zero outside those rows (nothing read the other output rows)
         dense = [torch.zeros(B, N, D, dtype=d.dtype, device=d.device) for d, N in zip(dr1, Ns)]
         for f_, d in zip(dense, dr1):
             f_[:, :R] = d.view(B, R, D)
         dr1 = [f_.view(-1, D) for f_ in dense]
-    dqkv = attn_bwd_grouped(qkv, o, [d.view(B, N, D) for d, N in zip(dr1, Ns)], lse, kv, packs)
+    dqkv = attn_bwd_grouped(sv.qkv, sv.o, [d.view(B, N, D) for d, N in zip(dr1, Ns)], sv.lse, sv.kv_len, packs)
     dqkv = [d.view(M, 3 * D) for d, M in zip(dqkv, Ms)]
-    gwq = gemm_tn_grouped(dqkv, xn1, [(sinks[i].wqkv, sinks[i].bqkv) if direct[i] else None for i in range(n)], reds, packs)
-    l1 = gemm_lnbwd_grouped(dqkv, wqkvt, [t.view(M, D) for t, M in zip(z, Ms)], st1, g1, dr1,
-                            [sinks[i].gb1 if direct[i] else None for i in range(n)], reds, packs)
-    allred = [e for r_ in reds for e in r_]
-    marks = [sinks[i] for i in range(n) if direct[i]]
-    if late is not None:
-        late.append((allred, marks))
-    else:
-        reduce_batch(allred)
-        for sk in marks:
-            sk.flat.mark_ready(sk.idx)
-    grads = []
-    for i in range(n):
-        if direct[i]:
-            grads.append(None)
-            continue
-        dwqkv, dbqkv = gwq[i]
-        grads.append((l1[i][1], l1[i][2], dwqkv[:D], dbqkv[:D], dwqkv[D:2 * D], dbqkv[D:2 * D], dwqkv[2 * D:], dbqkv[2 * D:],
-                      l2[i][1], l2[i][2], gw1[i][0], gw1[i][1], gw2[i][0], gw2[i][1]))
+    gwq = gemm_tn_grouped(dqkv, sv.xn1, [d.wqkv for d in dst], reds, packs)
+    l1 = gemm_lnbwd_grouped(dqkv, sv.wqkvt, [t.view(M, D) for t, M in zip(sv.z, Ms)], sv.st1, sv.g1, dr1, [d.gb1 for d in dst], reds, packs)
+    _finish_reductions([e for r_ in reds for e in r_], [sk for sk in sinks if sk is not None], late)
+    grads = [None if sinks[i] is not None else _param_grads(*l1[i][1:], *gwq[i], *l2[i][1:], *gw1[i], *gw2[i]) for i in range(n)]
     return [l1[i][0].view(B, Ns[i], D) for i in range(n)], grads
 
 
@@ -1731,18 +1740,18 @@ class EncoderLayerFn(torch.autograd.Function):
         P, (fused, drop_p, seeds) = rest[:PARAMS_PER_LAYER], rest[PARAMS_PER_LAYER:]
         out, saved = layer_forward(_c(z), kv_len, P, fused, drop_p, seeds)
         ctx.saved = saved
-        ctx.wshapes = (P[10].shape, P[12].shape)
+        ctx.wshapes = (P[P_W1].shape, P[P_W2].shape)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        z = ctx.saved[0]
+        z = ctx.saved.z
         d_out = _c(d_out)
         if d_out.dtype != z.dtype:
             d_out = d_out.to(z.dtype)
         dz, g = layer_backward(ctx.saved, d_out)
         g = list(g)
-        g[10], g[12] = g[10].view(ctx.wshapes[0]), g[12].view(ctx.wshapes[1])
+        g[P_W1], g[P_W2] = g[P_W1].view(ctx.wshapes[0]), g[P_W2].view(ctx.wshapes[1])
         return (dz, None, *g, None, None, None)
 
 
@@ -1787,6 +1796,50 @@ def stream_of_group(m, streams, z):
     if mode == "all":
         return None
     return streams[0] if mode == "small" else streams[(m - 1) % len(streams)]
+
+
+def _each_group(groups, cur):
+    """Yields the stream indices of each of launch_groups()'s groups with that group's HIP stream current.  Several groups: the
+    side streams start behind what `cur` holds now (one event), and `cur` waits for all of them after the last group."""
+    if len(groups) > 1:
+        ev = torch.cuda.Event()
+        ev.record(cur)
+    for gms, gs in groups:
+        if gs is not None:
+            gs.wait_event(ev)
+        with (torch.cuda.stream(gs) if gs is not None else contextlib.nullcontext()):
+            yield gms
+    if len(groups) > 1:
+        for _, gs in groups:
+            if gs is not None:
+                cur.wait_stream(gs)
+
+
+def _stack_params(params, cfg, li, m):
+    """the 14 parameters of layer li, stream m, out of FusionStackFn's flat argument list"""
+    k = (li * cfg.get("n_streams", 3) + m) * PARAMS_PER_LAYER
+    return params[k:k + PARAMS_PER_LAYER]
+
+
+def _stack_sink(cfg, li, m):
+    return cfg["sinks"][li][m] if cfg.get("sinks") else None
+
+
+def _group_forward(z, params, cfg, li, gms, pack_v, ffn_rows):
+    """one launch group of layer li: grouped launches (bf16) or the single-stream form per stream -> (outs, saved records)"""
+    Ps = [_stack_params(params, cfg, li, m) for m in gms]
+    if grouped_ok(z[0]):
+        return layer_forward_grouped([z[m] for m in gms], [cfg["kv"][m] for m in gms], Ps, [cfg["fused"][li][m] for m in gms],
+                                     cfg["drop_p"], [cfg["seeds"][li][m] for m in gms], [pack_v if m == 0 else None for m in gms],
+                                     ffn_rows=ffn_rows)
+    return zip(*[layer_forward(z[m], cfg["kv"][m], P, cfg["fused"][li][m], cfg["drop_p"], cfg["seeds"][li][m]) for m, P in zip(gms, Ps)])
+
+
+def _group_backward(saveds, dzs, sinks, late):
+    """its backward -> (dz per stream, gradient tuple | None per stream)"""
+    if grouped_ok(saveds[0].z):
+        return layer_backward_grouped(saveds, dzs, sinks, late)
+    return zip(*[layer_backward(sv, d, sk, late=late) for sv, d, sk in zip(saveds, dzs, sinks)])
 
 
 class FusionStackFn(torch.autograd.Function):
@@ -1855,49 +1908,27 @@ class FusionStackFn(torch.autograd.Function):
             ms = [0] if last else list(range(n_s))
             outs = [None, None, None]
             row = [None, None, None]
-            # launch groups of this layer: (streams, HIP stream).  Layer 0 keeps one group per stream while the image / text
-            # inputs are still being made on the side streams (the vital-sign stream's first layer runs beside the image encoder)
             # the layer in front of a last layer that runs stream 0 alone, read by a CLS-only reader (the encoder names it, by its
             # index in this segment): the image / text outputs of THIS layer feed the bottleneck exchange (rows 0..3) and nothing else
             exchange_only = li == cfg.get("exchange_only_layer", -1) and tuning.FFN_ROWS_BEFORE_LAST
             if last and cfg.get("cls_only"):       # the reader takes the CLS row only: ops.cls_layer_forward
-                P = params[(li * n_s) * PARAMS_PER_LAYER:(li * n_s + 1) * PARAMS_PER_LAYER]
                 mark(f"f{li}.g0.s")
-                cls_out, row[0] = cls_layer_forward(z[0], cfg["kv"][0], P, cfg["fused"][li][0], cfg["drop_p"], cfg["seeds"][li][0],
-                                                    pack_v, NB)
+                cls_out, row[0] = cls_layer_forward(z[0], cfg["kv"][0], _stack_params(params, cfg, li, 0), cfg["fused"][li][0],
+                                                    cfg["drop_p"], cfg["seeds"][li][0], pack_v, NB)
                 mark(f"f{li}.g0.e")
                 saved.append(row)
                 active.append(ms)
                 z = [None, None, None]
                 break
+            # launch groups of this layer: (streams, HIP stream).  Layer 0 keeps one group per stream while the image / text
+            # inputs are still being made on the side streams (the vital-sign stream's first layer runs beside the image encoder)
             groups = launch_groups(ms, streams, z[0], solo=(li == 0 and bool(cfg.get("inputs_on_side"))))
-            if len(groups) > 1:
-                ev = torch.cuda.Event()
-                ev.record(cur)
-            for gms, gs in groups:
-                if gs is not None:
-                    gs.wait_event(ev)
-                with (torch.cuda.stream(gs) if gs is not None else contextlib.nullcontext()):
-                    mark(f"f{li}.g{gms[0]}.s")
-                    if grouped_ok(z[0]):
-                        go, gsaved = layer_forward_grouped(
-                            [z[m] for m in gms], [cfg["kv"][m] for m in gms],
-                            [params[(li * n_s + m) * PARAMS_PER_LAYER:(li * n_s + m + 1) * PARAMS_PER_LAYER] for m in gms],
-                            [cfg["fused"][li][m] for m in gms], cfg["drop_p"], [cfg["seeds"][li][m] for m in gms],
-                            [pack_v if m == 0 else None for m in gms],
-                            ffn_rows=NB if (exchange_only and 0 not in gms) else None)
-                        for i, m in enumerate(gms):
-                            outs[m], row[m] = go[i], gsaved[i]
-                    else:
-                        for m in gms:
-                            P = params[(li * n_s + m) * PARAMS_PER_LAYER:(li * n_s + m + 1) * PARAMS_PER_LAYER]
-                            outs[m], row[m] = layer_forward(z[m], cfg["kv"][m], P, cfg["fused"][li][m], cfg["drop_p"],
-                                                            cfg["seeds"][li][m])
-                    mark(f"f{li}.g{gms[0]}.e")
-            if len(groups) > 1:
-                for _, gs in groups:
-                    if gs is not None:
-                        cur.wait_stream(gs)
+            for gms in _each_group(groups, cur):
+                mark(f"f{li}.g{gms[0]}.s")
+                go, gsaved = _group_forward(z, params, cfg, li, gms, pack_v, NB if (exchange_only and 0 not in gms) else None)
+                for i, m in enumerate(gms):
+                    outs[m], row[m] = go[i], gsaved[i]
+                mark(f"f{li}.g{gms[0]}.e")
             saved.append(row)
             active.append(ms)
             if last:
@@ -1937,7 +1968,7 @@ class FusionStackFn(torch.autograd.Function):
         dev = wsel.device
         streams = cfg.get("side_streams")
         cur = torch.cuda.current_stream()
-        n_run = len(saved)
+        n_run = len(active)             # layers that ran
         n_s = cfg.get("n_streams", 3)
         final = cfg.get("final", True)
         # vsltonly == 0: the last layer ran all three streams, but when nothing downstream read the image / text outputs
@@ -1968,13 +1999,13 @@ class FusionStackFn(torch.autograd.Function):
         # text streams' last launches that the vital-sign stream waits for there.
         late = [[], [], []]          # keyed by the first stream of the launch group that produced them
 
-        def flush_late(m):
-            for red, sks in late[m]:
-                reduce_batch(red)
-                for sk in (sks if isinstance(sks, (list, tuple)) else [sks]):
-                    if sk is not None:
-                        sk.flat.mark_ready(sk.idx)
-            del late[m][:]
+        def keep_grads(li, m, g):
+            """a layer's returned gradients (None: they went through its sink) into their places of this node's result"""
+            if g is not None:
+                base = (li * n_s + m) * PARAMS_PER_LAYER
+                for k in range(PARAMS_PER_LAYER):
+                    pgrads[base + k] = g[k].view(pshapes[base + k])
+
         def zero_other_streams(nxt):
             """zero gradient buffers of the streams a vslt-only layer skipped: ONE fill for both (views of one allocation)"""
             buf = torch.zeros(B * sum(Ns[m] for m in range(1, n_s)), D_MODEL, dtype=dt, device=dev)
@@ -1996,49 +2027,19 @@ class FusionStackFn(torch.autograd.Function):
             if ctx.cls_only and li == n_run - 1:
                 mark(f"b{li}.g0.s")
                 d1 = d_cls if d_cls is not None else torch.zeros(B, D_MODEL, dtype=dt, device=dev)
-                nxt[0], gg0 = cls_layer_backward(saved[li][0], d1, cfg["sinks"][li][0] if cfg.get("sinks") else None,
-                                                 late=late[0] if tuning.LATE_REDUCTIONS else None)
-                if gg0 is not None:
-                    base = (li * n_s) * PARAMS_PER_LAYER
-                    for k in range(PARAMS_PER_LAYER):
-                        pgrads[base + k] = gg0[k].view(pshapes[base + k])
+                nxt[0], gg0 = cls_layer_backward(saved[li][0], d1, _stack_sink(cfg, li, 0), late=late[0] if tuning.LATE_REDUCTIONS else None)
+                keep_grads(li, 0, gg0)
                 mark(f"b{li}.g0.e")
-                saved[li] = None
-                if li > 0:
-                    zero_other_streams(nxt)
-                dz = nxt
-                continue
-            groups = launch_groups(ms, streams, saved[li][ms[0]][0])
-            if len(groups) > 1:
-                ev = torch.cuda.Event()
-                ev.record(cur)
-            for gi, (gms, gs) in enumerate(groups):
-                if gs is not None:
-                    gs.wait_event(ev)
-                with (torch.cuda.stream(gs) if gs is not None else contextlib.nullcontext()):
+            else:
+                for gms in _each_group(launch_groups(ms, streams, saved[li][ms[0]].z), cur):
                     mark(f"b{li}.g{gms[0]}.s")
-                    flush_late(gms[0])                  # the layer above's reductions of this group: behind this layer's exchange
-                    lt = late[gms[0]] if tuning.LATE_REDUCTIONS else None
-                    if grouped_ok(saved[li][ms[0]][0]):
-                        gdz, gg = layer_backward_grouped([saved[li][m] for m in gms], [dz[m] for m in gms],
-                                                         [cfg["sinks"][li][m] if cfg.get("sinks") else None for m in gms], lt)
-                    else:
-                        gdz, gg = [], []
-                        for m in gms:
-                            d1, g1_ = layer_backward(saved[li][m], dz[m], cfg["sinks"][li][m] if cfg.get("sinks") else None, late=lt)
-                            gdz.append(d1)
-                            gg.append(g1_)
+                    _flush_late(late[gms[0]])           # the layer above's reductions of this group: behind this layer's exchange
+                    gdz, gg = _group_backward([saved[li][m] for m in gms], [dz[m] for m in gms], [_stack_sink(cfg, li, m) for m in gms],
+                                              late[gms[0]] if tuning.LATE_REDUCTIONS else None)
                     for i, m in enumerate(gms):
                         nxt[m] = gdz[i]
-                        if gg[i] is not None:
-                            base = (li * n_s + m) * PARAMS_PER_LAYER
-                            for k in range(PARAMS_PER_LAYER):
-                                pgrads[base + k] = gg[i][k].view(pshapes[base + k])
+                        keep_grads(li, m, gg[i])
                     mark(f"b{li}.g{gms[0]}.e")
-            if len(groups) > 1:
-                for _, gs in groups:
-                    if gs is not None:
-                        cur.wait_stream(gs)
             saved[li] = None
             # streams skipped by the vslt-only last layer re-enter here with zero gradient
             if len(ms) == 1 and li > 0:
@@ -2047,12 +2048,10 @@ class FusionStackFn(torch.autograd.Function):
         for m in range(3):                  # the first layer's reductions, on the stream their group ran on
             if late[m]:
                 gs = stream_of_group(m, streams, next(t for t in dz if t is not None))
+                with (torch.cuda.stream(gs) if gs is not None else contextlib.nullcontext()):
+                    _flush_late(late[m])
                 if gs is not None:
-                    with torch.cuda.stream(gs):
-                        flush_late(m)
                     cur.wait_stream(gs)
-                else:
-                    flush_late(m)
         if cfg.get("prebuilt"):            # the bottleneck rows' gradient flows on through the stream-input nodes
             d_bott = None if d_prev_bott is None else d_prev_bott.sum(0, keepdim=True)
             return (dz[0], dz[1], dz[2], d_bott, *pgrads, None)

@@ -1,11 +1,12 @@
 """Scheduling choices of the hot path, in ONE place (the A/B booleans were scattered over ops.py and trainer.py).
 
-None of these changes a result beyond the order in which independent launches are issued or which of two equivalent launch
-sequences runs (every combination is covered by the parity tests: they are bit-identical or within the documented tolerances);
-each default is the faster setting as measured on MI355X -- the measurement is named beside it and lives in DESIGN.md section 9
-("Built, measured, not kept").  They are module attributes so that ``tools/dbg/ab_patch.py`` can flip one inside a single gpurun
-call (boxes differ by up to 5 %: an A/B across two calls says nothing); product code reads them at call time, nothing else
-writes them.
+Each switch chooses the order in which independent launches are issued, or which of two launch sequences meant to be equivalent
+runs.  The defaults below are what the tests and bench.py run, and the only settings they run: no test reads or sets one of these
+attributes.  The other settings are exercised only through ``tools/dbg/ab_patch.py`` (and the tools/dbg probes that flip one), so
+treat a non-default setting as unverified until such a run has compared it.  Each default is the faster setting as measured on
+MI355X -- the measurement is named beside it and lives in DESIGN.md section 9 ("Built, measured, not kept").  They are module
+attributes so that ab_patch.py can flip one and measure both settings on one machine in one session (machines differ by up to
+5 %: an A/B across two sessions says nothing); product code reads them at call time, nothing else writes them.
 """
 
 # ops.layer_backward: drop2's backward rides on the operand load of the dH launch (one launch and one read of d_out less).
