@@ -562,6 +562,39 @@ int mtmp_cxr_resize(const uint8_t* pixels, const int32_t* desc, const int32_t* t
 int mtmp_cxr_affine_crop(const uint8_t* scratch, const int32_t* desc, const int32_t* slot_map, float* out, int n_slots, int S,
                          void* stream);
 
+/* ---- The random chains of the chest X-ray input (additive; ABI stays 6): --image-train-type random = RandomResizedCrop(S, scale
+ * (0.8, 1.1), ratio (3/4, 4/3)), randaug = RandAugment() in front of it (builder/data/dataset_new.py:60-89), behind the loader's
+ * equalisation.  Per image: equalise, two ops, crop box (i, j, ch, cw), PIL's resize of the box to S x S, / 255 -- bit for bit what
+ * PIL computes (csrc/image_aug.hip states each rule).  pixels / tables / slot_map as above; the histograms of the source pixels come
+ * from mtmp_cxr_hist with a desc row per image that holds words 0..2.
+ *   aug:     int32 [max(n, 1)][64] device, one row per image: 0 source byte offset, 1 h, 2 w, 3 output slot, 4 byte offset of the
+ *            image's map inside each scratch half (a multiple of 16), 5..8 crop box i, j, ch, cw, 9 / 10 / 11 word offset of the
+ *            horizontal bounds table, of the weights, taps per weight row of the (cw -> S) resize, 12 / 13 / 14 the same for
+ *            (ch -> S); 16 + 8 k (k = 0, 1): stage k, the RandAugment op k + 1 when it writes a map: kind (0 none, 1 affine, 2
+ *            Sharpness), then the 16.16 words a0..a5 or the float32 bits of the blend factor; 32 + 8 r (r = 0, 1: stage r, r = 2: the
+ *            resize): what reader r reads: base (0 source pixels, 1 + k map of stage k), number of pending table ops (0..3), their
+ *            three codes (1 Equalize, 2 Brightness, 3 Contrast, 4 Posterize, 5 Solarize, 6 AutoContrast), their three parameters
+ *            (float32 bits of the blend factor; Posterize's mask; Solarize's threshold rounded up); every other word zero.
+ *   hist:    uint32 [3][n][256] device: [0] the source pixels' histograms (mtmp_cxr_hist), [1 + k] those of the maps of stage k,
+ *            added by mtmp_cxr_aug_stage (the caller ZEROES all three; integer atomics, order-independent).
+ *   scratch: uint8 [2][half_bytes] device, 16-byte aligned, half_bytes a multiple of 16: map of stage k of image m at
+ *            k half_bytes + aug[m][4], h w bytes.
+ * mtmp_cxr_aug_stage: runs stage `stage` (0, then 1) of every image that has one: reads its base map through the composed pending
+ *   table, writes its map (0 outside the source for the affine kind) and that map's histogram.  max_pixels = the largest h w.  A
+ *   batch in which no image has stage k needs no launch for k.  The affine words must keep |a2| + |a0| w + |a1| h and the same for
+ *   a3..a5 below 2^31 (the host checks).
+ * mtmp_cxr_crop_resize: out float [n_slots][S][S] <- for every slot with an image (slot_map >= 0) the crop box of its last map through
+ *   the pending table, resized in two passes (horizontal pass rounded to uint8), float / 255 with IEEE division; zeros for the
+ *   other slots.  n may be 0 (no image: all zeros; hist and scratch are then not read but must be non-null).  lds_rows: the most
+ *   box rows any tile of 32 output rows reads (<= 960), the maximum over images and tiles [r0, r1) of vbounds[r1-1].first +
+ *   vbounds[r1-1].taps - vbounds[r0].first; with a smaller value than that the tile's rows past lds_rows are left out (wrong
+ *   pixels, no access outside the LDS rows).  builder/data/cxr_transform.py computes it with the tables. */
+int mtmp_cxr_aug_stage(const uint8_t* pixels, const int32_t* aug, uint32_t* hist, uint8_t* scratch, int n, int max_pixels,
+                       long long half_bytes, int stage, void* stream);
+int mtmp_cxr_crop_resize(const uint8_t* pixels, const uint8_t* scratch, const int32_t* aug, const int32_t* tables,
+                         const uint32_t* hist, const int32_t* slot_map, float* out, int n, int n_slots, int S, long long half_bytes,
+                         int lds_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -448,7 +448,10 @@ def cxr_hist(pixels, desc, max_pixels: int):
 def cxr_prepare(raw):
     """RawCxrBatch (device) -> float32 [B, 1, S, S] or [B, K, 1, S, S]: the reference loader's equalize + transform chain for
     every present image, zeros for the slots without one (builder/data/cxr_transform.py holds the plan).  Three launches behind
-    the zero-fill of the histogram table: mtmp_cxr_hist, mtmp_cxr_resize, mtmp_cxr_affine_crop."""
+    the zero-fill of the histogram table: mtmp_cxr_hist, mtmp_cxr_resize, mtmp_cxr_affine_crop.  A batch of the random chains
+    (``raw.aug``) goes through _cxr_prepare_random."""
+    if raw.aug is not None:
+        return _cxr_prepare_random(raw)
     _gpu(raw.pixels, raw.desc, raw.tables, raw.slot_map)
     dev, S = raw.pixels.device, raw.image_size
     out = torch.empty(raw.out_shape, dtype=torch.float32, device=dev)
@@ -458,6 +461,26 @@ def cxr_prepare(raw):
         call("mtmp_cxr_resize", _p(raw.pixels), _p(raw.desc), _p(raw.tables), _p(hist), _p(scratch), raw.n, raw.max_rh,
              raw.max_rw, raw.lds_rows, _stream())
     call("mtmp_cxr_affine_crop", _p(scratch), _p(raw.desc), _p(raw.slot_map), _p(out), raw.slot_map.numel(), S, _stream())
+    return out
+
+
+def _cxr_prepare_random(raw):
+    """The chains ``random`` and ``randaug`` (csrc/image_aug.hip): mtmp_cxr_hist, one mtmp_cxr_aug_stage launch per RandAugment
+    position at which some image of the batch writes a map (none for ``random``), mtmp_cxr_crop_resize -- two to four launches
+    behind the zero-fill of the histogram tables, whatever the number of images."""
+    _gpu(raw.pixels, raw.desc, raw.aug, raw.tables, raw.slot_map)
+    dev, S, n = raw.pixels.device, raw.image_size, raw.n
+    out = torch.empty(raw.out_shape, dtype=torch.float32, device=dev)
+    half = raw.scratch_bytes if raw.stages else 0
+    scratch = torch.empty(max(2 * half, 16), dtype=torch.uint8, device=dev)
+    hist = torch.zeros(3 if raw.stages else 1, max(n, 1), 256, dtype=torch.int32, device=dev)
+    if n > 0:
+        call("mtmp_cxr_hist", _p(raw.pixels), _p(raw.desc), _p(hist), n, raw.max_pixels, _stream())
+        for k in (0, 1):
+            if raw.stages >> k & 1:
+                call("mtmp_cxr_aug_stage", _p(raw.pixels), _p(raw.aug), _p(hist), _p(scratch), n, raw.max_pixels, half, k, _stream())
+    call("mtmp_cxr_crop_resize", _p(raw.pixels), _p(scratch), _p(raw.aug), _p(raw.tables), _p(hist), _p(raw.slot_map), _p(out), n,
+         raw.slot_map.numel(), S, half, max(raw.lds_rows, 1), _stream())
     return out
 
 

@@ -10,7 +10,8 @@ build-only flags wired in:
     --fused-adamw 1   optim.FusedAdamW over the flat buffers (0: torch.optim.AdamW(model.parameters()) as in the reference)
     --hip-graph 1     hipGraph replay of zero_grad + forward + backward (needs --fused-adamw 1)
     --raw-images 1    the synthetic batches carry uint8 images of varying size (synthetic.make_raw_cxr) as a RawCxrBatch; the
-                      trainer runs the reference loader's equalize / resize / affine / crop chain on the GPU (ops.cxr_prepare)
+                      trainer runs the reference loader's equalize / resize / affine / crop chain on the GPU (ops.cxr_prepare);
+                      every --image-train-type but resize_larger, RandomResizedCrop (random) and RandAugment (randaug) included
 
     python -m medical_tri_modal_pilot_amd.train --input-types vslt_img_txt --model tri_mbt_vsltcls \\
         --modality-inclusion train-missing_test-missing --lr-init 1e-5 --batch-size 64 --epochs 1 \\
@@ -54,10 +55,10 @@ def synthetic_loader(args, n_iters: int, rank: int, epoch: int):
                         img_size=int(args.image_size), n_images=int(getattr(args, "n_images", 3)))
         static = torch.stack([bt["gen"], bt["age"]], 1)
         if int(getattr(args, "raw_images", 0)) == 1:
-            from .builder.data.cxr_transform import CxrTransform, collate_raw_cxr
+            from .builder.data.cxr_transform import collate_raw_cxr, transform_from_args
             from .synthetic import make_raw_cxr
             g = torch.Generator().manual_seed(4241 + 7919 * rank + 104729 * epoch + it)
-            raw = collate_raw_cxr(make_raw_cxr(g.initial_seed(), bt["img_time"]), CxrTransform.from_args(args, train=True),
+            raw = collate_raw_cxr(make_raw_cxr(g.initial_seed(), bt["img_time"]), transform_from_args(args, train=True),
                                   int(getattr(args, "n_images", 3)) if multi else 0, generator=g)
             bt["img"], bt["img_time"] = raw, raw.img_time.half().float()
         yield (bt["x"], static, bt["y"], bt["input_lengths"], bt["img"], bt["img_time"], bt["txt"], bt["txt_lengths"],

@@ -280,6 +280,43 @@ def main():
                              f"  ({n / tot * 1e3:10.0f} images/s; ops.cxr_prepare with its allocations and zero-fill {t_all * 1e3:8.1f} us); CPU chain: {cpu_s}")
         cxr_table = ("# chest X-ray input chain, resize_affine_crop, uint8 sources already on the device, one process, warm, median over %d rounds of 5 calls\n"
                      % a.rounds + "\n".join(lines) + "\n")
+        # the random chains (csrc/image_aug.hip): launches and us per batch of 64 images of 256 x 311 -> 224, ops and boxes drawn
+        from medical_tri_modal_pilot_amd.builder.data.cxr_transform import CxrRandomTransform, draw_randaug, draw_resized_crop
+
+        def pil_random_ms(src, S, randaug):
+            """RandAugment (when asked for) + RandomResizedCrop by the PIL calls they are on an L image, one core, drawn per repetition"""
+            try:
+                from PIL import Image, ImageOps
+            except ImportError:
+                return None
+            spec = importlib.util.spec_from_file_location("make_golden_cxr_aug", os.path.join(ROOT, "tests", "golden", "gen", "make_golden_cxr_aug.py"))
+            gen = importlib.util.module_from_spec(spec)
+            spec.loader.exec_module(gen)
+            im, g, reps = Image.fromarray(src), torch.Generator().manual_seed(2), 40
+            plans = [(draw_randaug(*src.shape, g) if randaug else [], draw_resized_crop(*src.shape, g)) for _ in range(reps)]
+            t0 = time.perf_counter()
+            for ops_, (bi, bj, bh, bw) in plans:
+                r = ImageOps.equalize(im)
+                for op, m in ops_:
+                    r = gen.apply_op(r, op, m)
+                np.asarray(r.crop((bj, bi, bj + bw, bi + bh)).resize((S, S), Image.BILINEAR), dtype=np.float32) / 255
+            return (time.perf_counter() - t0) / reps * 1e3
+
+        import importlib.util
+        lines, (h, w), S, n = [], (256, 311), 224, 64
+        srcs = [source(h, w) for _ in range(8)]
+        for kind in ("random", "randaug"):
+            raw = collate_raw_cxr([([srcs[i % 8]], [-1.0]) for i in range(n)], CxrRandomTransform(S, kind), 0,
+                                  generator=torch.Generator().manual_seed(1)).to(DEV)
+            launches = 2 + bin(raw.stages).count("1")
+            t_all = timeit(lambda: ops.cxr_prepare(raw), a.rounds)
+            rec(f"cxr.prepare.{kind}[{n}x{h}x{w}->{S}]", t_all)
+            cpu = pil_random_ms(srcs[0], S, kind == "randaug")
+            cpu_s = "PIL not installed" if cpu is None else f"{cpu:7.3f} ms/image/core (PIL {__import__('PIL').__version__}, this box's CPU)"
+            lines.append(f"{kind:8s} {n:4d} x {h} x {w} -> {S}: {launches} launches, ops.cxr_prepare with its allocations and zero-fill "
+                         f"{t_all * 1e3:8.1f} us  ({n / t_all * 1e3:10.0f} images/s); CPU chain: {cpu_s}")
+        cxr_table += ("# random chains (RandomResizedCrop; RandAugment in front of it), ops and boxes drawn with seed 1, same conditions\n"
+                      + "\n".join(lines) + "\n")
         print(cxr_table, end="", flush=True)
     # ---- attention
     if want("attn"):
