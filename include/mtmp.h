@@ -595,6 +595,41 @@ int mtmp_cxr_crop_resize(const uint8_t* pixels, const uint8_t* scratch, const in
                          const uint32_t* hist, const int32_t* slot_map, float* out, int n, int n_slots, int S, long long half_bytes,
                          int lds_rows, void* stream);
 
+/* ---- Baseline greyscale JPEG decoding (additive; ABI stays 6): the reference's loader opens every image with PIL's Image.open
+ * (builder/data/dataset_new.py:2094); the files are what PIL wrote (1_mimic_cxr_preprocess.py:81-82): 8-bit, one component,
+ * baseline sequential (SOF0), Huffman coded.  The host (builder/data/jpeg.py) parses the markers and REMOVES the stuffed FF 00
+ * zero bytes and the RSTn markers from the entropy-coded data; the device does the rest -- Huffman decoding, integer
+ * dequantisation, libjpeg's jpeg_idct_islow, the range limit -- and equals PIL bit for bit.  The coefficient buffer is int16
+ * (DC absolute, natural order) and holds the UNdequantised values: the quantiser product is part of mtmp_jpeg_idct.
+ *   streams: uint8 device buffer, every segment's de-stuffed bytes (segments of an image back to back, images back to back).
+ *   desc:    int32 [n][16] device, one row per image: 0 byte offset of its first segment in `streams`, 1 its first row in `segs`,
+ *            2 its number of segments, 3 h, 4 w, 5 blocks per row = ceil(w / 8), 6 blocks = ceil(h / 8) ceil(w / 8), 7 byte offset
+ *            of its first pixel in `pixels` (row stride w, any alignment), 8 word offset of its quantisation table in `tables`
+ *            (64 words, natural order), 9 / 10 word offset of its DC / AC decode table, 11 its first block in `coef`, 12 restart
+ *            interval in blocks (0: none), 13..15 zero.
+ *   segs:    int32 [n_seg][4] device, one row per restart segment: 0 byte offset in `streams`, 1 bytes (<= 2^22), 2 image, 3 its
+ *            first block within the image.  A segment holds min(restart interval, blocks - first block) blocks (all of them
+ *            without an interval); every segment starts with a zero DC predictor.
+ *   tables:  int32 device.  A decode table is 1316 words: look[1024], indexed by the next 10 bits of the stream: (code length << 8)
+ *            | symbol, 0 where the code is longer or there is none; maxcode[18], indexed by the code length: the largest code of
+ *            that length, -1 for none, [17] = 0x7fffffff; valoff[18]: index of that length's first symbol minus its first code;
+ *            huffval[256]: the symbols in code order.  Tables are shared between images that carry the same payload.
+ *   status:  int32 [n] device, ZEROED by the caller: bit 0 a segment did not yield its block count (truncated or corrupt data),
+ *            bit 1 a segment has more subsequences than the launch has lanes, bit 2 the image's segments do not cover its blocks.
+ * mtmp_jpeg_entropy: coef int16 [blocks of the batch][64], ZEROED by the caller, <- the coefficients.  One workgroup per segment,
+ *   one lane per subsequence of subseq_bits bits (0: one lane decodes the whole segment); max_seg_bytes = the largest segment
+ *   (at most 1024 subsequences; the entry refuses more); stage_bytes (0..32768): dynamic LDS of a workgroup, a segment of at
+ *   most that many bytes is copied into it and decoded from there, a larger one is read from global memory.  The lanes find their entry states by decoding in rounds inside the
+ *   workgroup (csrc/jpeg.hip); rounds: int32 [n_seg] or NULL, receives the number of rounds that moved an exit state.  Every loop
+ *   is bounded by the segment's bits and the lane count: a truncated or corrupt stream ends and sets its image's status.  Nothing
+ *   outside the image's blocks of coef is written.
+ * mtmp_jpeg_idct: pixels <- the decoded images (only bytes of rows < h, columns < w at the image's offset are written); an image
+ *   whose status word is set is written as zeros.  max_blocks = the largest block count of an image. */
+int mtmp_jpeg_entropy(const uint8_t* streams, const int32_t* desc, const int32_t* segs, const int32_t* tables, int16_t* coef,
+                      int32_t* status, int32_t* rounds, int n_seg, int max_seg_bytes, int subseq_bits, int stage_bytes, void* stream);
+int mtmp_jpeg_idct(const int16_t* coef, const int32_t* desc, const int32_t* tables, const int32_t* status, uint8_t* pixels, int n,
+                   int max_blocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,9 @@ Reference behaviour restated here (file:line in the reference's builder/data/dat
   * :60-89                  the train chains ``random`` (RandomResizedCrop(S, scale (0.8, 1.1), ratio (3/4, 4/3))) and ``randaug``
                             (RandAugment() in front of that crop): ``CxrRandomTransform``, see "The random chains" below.
 What is NOT restated: ``resize_larger`` (the reference names a function for it that it never defines) raises
-NotImplementedError; JPEG decoding stays with the loader.  ``transform_from_args`` picks the class for a set of flags.
+NotImplementedError.  ``transform_from_args`` picks the class for a set of flags.  An image may be handed over as the bytes
+of its JPEG file instead of the decoded array: builder/data/jpeg.py plans its decoding (csrc/jpeg.hip), which then runs in front
+of the chain on the device.
 
 All of the chain is integer arithmetic in PIL (ImageOps.equalize, the 22-bit fixed-point antialiased bilinear resize with a
 uint8 rounding between its two passes, the 16.16 fixed-point nearest-neighbour affine map), so the kernels reproduce it bit
@@ -55,6 +57,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from .jpeg import is_jpeg_source, parse_jpeg, plan_jpegs
 
 PRECISION_BITS = 22                 # PIL's 8-bit resampling: 32 - 8 - 2
 TILE_ROWS, TILE_COLS = 32, 64       # output tile of one workgroup of mtmp_cxr_resize (csrc/image_prep.hip)
@@ -381,11 +385,14 @@ class RawCxrBatch:
     aug       int32 [max(n, 1), AUG_WORDS]   their plan; ``desc`` then holds source offset, h, w and the slot only
     stages    bit k set: some image's RandAugment op k writes a map, so stage k is launched; ``scratch_bytes`` is one of the
               two maps' buffers, ``lds_rows`` belongs to the tables of the crop boxes
+    Images handed over as JPEG file bytes add
+    jpeg      builder/data/jpeg.JpegPlan | None   their streams, descriptor rows, segment rows and decode tables; their regions
+              of ``pixels`` are left for ``ops.jpeg_decode`` to fill (``ops.cxr_prepare`` calls it)
     """
 
     def __init__(self, pixels, desc, tables, slot_map, img_time, image_size, batch, n_images, scratch_bytes, max_pixels,
-                 max_rh, max_rw, lds_rows, params, aug=None, stages=0):
-        self.aug, self.stages = aug, int(stages)
+                 max_rh, max_rw, lds_rows, params, aug=None, stages=0, jpeg=None):
+        self.aug, self.stages, self.jpeg = aug, int(stages), jpeg
         self.pixels, self.desc, self.tables, self.slot_map, self.img_time = pixels, desc, tables, slot_map, img_time
         self.image_size, self.batch, self.n_images = int(image_size), int(batch), int(n_images)
         self.scratch_bytes, self.max_pixels, self.max_rh, self.max_rw = int(scratch_bytes), int(max_pixels), int(max_rh), int(max_rw)
@@ -407,7 +414,8 @@ class RawCxrBatch:
         mv = lambda t: t.to(device, non_blocking=non_blocking)
         return RawCxrBatch(mv(self.pixels), mv(self.desc), mv(self.tables), mv(self.slot_map), self.img_time, self.image_size,
                            self.batch, self.n_images, self.scratch_bytes, self.max_pixels, self.max_rh, self.max_rw,
-                           self.lds_rows, self.params, None if self.aug is None else mv(self.aug), self.stages)
+                           self.lds_rows, self.params, None if self.aug is None else mv(self.aug), self.stages,
+                           None if self.jpeg is None else self.jpeg.to(device, non_blocking=non_blocking))
 
 
 def _tile_rows_needed(vb: np.ndarray) -> int:
@@ -447,6 +455,10 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
     """samples: one ``(images, times)`` pair per sample.  n_images = K > 0: the multi-image layout [B, K, 1, S, S] (absent
     slots zero, their time 10); n_images = 0: one image per sample, [B, 1, S, S] (absent: zeros, time -1).
     affine_params: per image ``(angle, tx, ty, scale)`` in batch order instead of drawing them (tests).
+    An image is a ``uint8 [h, w]`` array or the ``bytes`` / ``bytearray`` / ``memoryview`` of a baseline greyscale JPEG file
+    (builder/data/jpeg.parse_jpeg says what is accepted; anything else raises -- the loader then decodes that file itself and
+    passes the array).  The file's header gives h and w, so everything below is planned as for an array; the file's region of
+    ``pixels`` is left zero and ``RawCxrBatch.jpeg`` holds what the device needs to fill it.
     A ``CxrRandomTransform`` draws per image, in the reference's order, the RandAugment ops (``randaug``) and then the crop
     box; aug_params: per image two ``(op, magnitude)`` pairs, crop_params: per image ``(i, j, ch, cw)``, instead (tests)."""
     rnd = isinstance(transform, CxrRandomTransform)
@@ -460,6 +472,7 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
     slot_map = np.full(B * per, -1, np.int32)
     img_time = np.full((B, per), 10.0 if K else -1.0, np.float32)
     src_off = scratch_off = max_pixels = max_rh = max_rw = lds_rows = 0
+    jpg_infos, jpg_dst, jpg_rows, jpg_bytes = [], [], [], 0
 
     def table(in_size, out_size):
         nonlocal tab_words
@@ -475,10 +488,22 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
         if len(images) > per or len(images) != len(times):
             raise ValueError(f"sample {b}: {len(images)} images, {len(times)} times, {per} slots")
         for j, (im, t) in enumerate(zip(images, times)):
-            im = np.ascontiguousarray(im)
-            if im.dtype != np.uint8 or im.ndim != 2 or im.size == 0:
-                raise ValueError(f"sample {b} image {j}: a non-empty uint8 [h, w] array is required")
-            h, w = im.shape
+            if is_jpeg_source(im):
+                try:
+                    info = parse_jpeg(im)
+                except (ValueError, NotImplementedError) as e:
+                    raise type(e)(f"sample {b} image {j}: {e}") from None
+                jpg_infos.append(info)
+                jpg_dst.append(src_off)
+                jpg_rows.append(len(rows))
+                jpg_bytes += memoryview(im).nbytes
+                h, w = info.h, info.w
+                im = np.zeros(h * w, np.uint8)                     # ops.jpeg_decode writes these bytes on the device
+            else:
+                im = np.ascontiguousarray(im)
+                if im.dtype != np.uint8 or im.ndim != 2 or im.size == 0:
+                    raise ValueError(f"sample {b} image {j}: a non-empty uint8 [h, w] array or the bytes of a JPEG file is required")
+                h, w = im.shape
             if rnd:
                 if transform.randaug:
                     ops = [(str(o), float(m)) for o, m in aug_params[len(rows)]] if aug_params is not None \
@@ -555,4 +580,5 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
     t_img = torch.from_numpy(img_time if K else img_time[:, 0].copy())
     return RawCxrBatch(pixels, host(desc.astype(np.int32), torch.int32), tables, host(slot_map, torch.int32), t_img, S, B, K,
                        scratch_off, max_pixels, max_rh, max_rw, lds_rows, params,
-                       None if aug is None else host(aug.astype(np.int32), torch.int32), stage_mask)
+                       None if aug is None else host(aug.astype(np.int32), torch.int32), stage_mask,
+                       plan_jpegs(jpg_infos, jpg_dst, jpg_rows, jpg_bytes, pin) if jpg_infos else None)

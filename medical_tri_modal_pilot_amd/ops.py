@@ -445,11 +445,68 @@ def cxr_hist(pixels, desc, max_pixels: int):
     return hist
 
 
-def cxr_prepare(raw):
+# ---- baseline greyscale JPEG decoding (csrc/jpeg.hip): the loader hands over file bytes ------------------------------------
+def _jpeg_decode_plan(plan, pixels, subseq_bits=None, rounds=None, stage_bytes=None):
+    """Decode the images of a builder/data/jpeg.JpegPlan (device) into ``pixels``: the zero-fill of the coefficient buffer and of
+    the status words, mtmp_jpeg_entropy, mtmp_jpeg_idct.  Returns the status words int32 [n]."""
+    _gpu(plan.streams, plan.desc, plan.segs, plan.tables, pixels)
+    dev = pixels.device
+    coef = torch.zeros(max(plan.total_blocks, 1) * 64, dtype=torch.int16, device=dev)
+    status = torch.zeros(plan.n, dtype=torch.int32, device=dev)
+    call("mtmp_jpeg_entropy", _p(plan.streams), _p(plan.desc), _p(plan.segs), _p(plan.tables), _p(coef), _p(status), _p(rounds),
+         plan.segs.shape[0], plan.max_seg_bytes, plan.subseq_bits(subseq_bits), plan.stage_bytes(stage_bytes), _stream())
+    call("mtmp_jpeg_idct", _p(coef), _p(plan.desc), _p(plan.tables), _p(status), _p(pixels), plan.n, plan.max_blocks, _stream())
+    return status
+
+
+def jpeg_decode(raw, subseq_bits=None):
+    """Fill the regions of ``raw.pixels`` (RawCxrBatch on the device) that belong to images handed over as JPEG file bytes;
+    returns their status words, int32 [raw.jpeg.n] on the device (0: decoded; include/mtmp.h names the bits).  An image whose
+    status is set is written as zeros.  subseq_bits: bits of the stream one lane decodes (None: the host's choice, 0: one lane
+    per restart segment)."""
+    if raw.jpeg is None:
+        raise ValueError("jpeg_decode: the batch holds no JPEG image")
+    return _jpeg_decode_plan(raw.jpeg, raw.pixels, subseq_bits)
+
+
+def jpeg_status_check(raw, status):
+    """Raise for the images of the batch whose JPEG stream did not decode (one small device-to-host copy)."""
+    st = status.cpu()
+    bad = torch.nonzero(st).flatten().tolist()
+    if bad:
+        raise ValueError("jpeg_decode: the JPEG stream of image(s) " + ", ".join(str(raw.jpeg.images[i]) for i in bad) +
+                         " of the batch is truncated or corrupt (status " + ", ".join(str(int(st[i])) for i in bad) + ")")
+
+
+def jpeg_decode_images(files, device, subseq_bits=None, stage_bytes=None):
+    """The decoder on its own: the bytes of baseline greyscale JPEG files -> a list of uint8 [h, w] tensors on ``device`` (views
+    of one buffer).  Raises ValueError for a file whose stream is truncated or corrupt; what builder/data/jpeg.parse_jpeg does
+    not accept raises there.  stage_bytes: JpegPlan.stage_bytes (tests)."""
+    from .builder.data.jpeg import plan_files
+    plan, sizes = plan_files(list(files))
+    pixels = torch.empty(sum(h * w for h, w in sizes), dtype=torch.uint8, device=device)
+    status = _jpeg_decode_plan(plan.to(device), pixels, subseq_bits, stage_bytes=stage_bytes).cpu()
+    bad = torch.nonzero(status).flatten().tolist()
+    if bad:
+        raise ValueError(f"jpeg_decode_images: the stream of file(s) {bad} is truncated or corrupt")
+    out, o = [], 0
+    for h, w in sizes:
+        out.append(pixels[o:o + h * w].view(h, w))
+        o += h * w
+    return out
+
+
+def cxr_prepare(raw, check: bool = True, subseq_bits=None):
     """RawCxrBatch (device) -> float32 [B, 1, S, S] or [B, K, 1, S, S]: the reference loader's equalize + transform chain for
     every present image, zeros for the slots without one (builder/data/cxr_transform.py holds the plan).  Three launches behind
     the zero-fill of the histogram table: mtmp_cxr_hist, mtmp_cxr_resize, mtmp_cxr_affine_crop.  A batch of the random chains
-    (``raw.aug``) goes through _cxr_prepare_random."""
+    (``raw.aug``) goes through _cxr_prepare_random.  Images handed over as JPEG file bytes (``raw.jpeg``) are decoded first
+    (jpeg_decode); a stream that did not decode raises ValueError naming the image -- check=False skips that test, and the
+    device-to-host copy it costs, for callers that must not synchronise (the image is then a zero image)."""
+    if raw.jpeg is not None:
+        status = jpeg_decode(raw, subseq_bits)
+        if check:
+            jpeg_status_check(raw, status)
     if raw.aug is not None:
         return _cxr_prepare_random(raw)
     _gpu(raw.pixels, raw.desc, raw.tables, raw.slot_map)

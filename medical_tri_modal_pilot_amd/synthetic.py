@@ -135,3 +135,20 @@ def make_raw_cxr(seed: int, img_time: torch.Tensor, sizes=RAW_CXR_SIZES):
             times.append(float(t[b, j]))
         samples.append((images, times))
     return samples
+
+
+def jpeg_encode(image, quality: int = 75) -> bytes:
+    """The uint8 [h, w] image as the bytes of the file ``Image.fromarray(image).save(path, 'JPEG')`` writes: 8-bit greyscale,
+    baseline, PIL's defaults (what the reference's preprocessing stores, 1_mimic_cxr_preprocess.py:81-82).  PIL is needed for
+    this stand-in only -- the decoder (builder/data/jpeg.py, csrc/jpeg.hip) does not use it.  ``image`` None: only the check."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise SystemExit("--raw-images 2 writes its synthetic JPEG files with PIL (Pillow), which is not installed; "
+                         "--raw-images 1 feeds the same images decoded") from e
+    if image is None:
+        return b""
+    import io
+    buf = io.BytesIO()
+    Image.fromarray(image).save(buf, "JPEG", quality=quality)
+    return buf.getvalue()

@@ -12,6 +12,8 @@ build-only flags wired in:
     --raw-images 1    the synthetic batches carry uint8 images of varying size (synthetic.make_raw_cxr) as a RawCxrBatch; the
                       trainer runs the reference loader's equalize / resize / affine / crop chain on the GPU (ops.cxr_prepare);
                       every --image-train-type but resize_larger, RandomResizedCrop (random) and RandAugment (randaug) included
+    --raw-images 2    the same images JPEG-encoded (PIL writes them, as the reference's preprocessing does): the batches carry
+                      file bytes, and the decoder runs on the GPU in front of that chain (ops.jpeg_decode, csrc/jpeg.hip)
 
     python -m medical_tri_modal_pilot_amd.train --input-types vslt_img_txt --model tri_mbt_vsltcls \\
         --modality-inclusion train-missing_test-missing --lr-init 1e-5 --batch-size 64 --epochs 1 \\
@@ -54,11 +56,14 @@ def synthetic_loader(args, n_iters: int, rank: int, epoch: int):
                         missing_mode="mixed" if "missing" in args.modality_inclusion else "none", multiimages=multi,
                         img_size=int(args.image_size), n_images=int(getattr(args, "n_images", 3)))
         static = torch.stack([bt["gen"], bt["age"]], 1)
-        if int(getattr(args, "raw_images", 0)) == 1:
+        if int(getattr(args, "raw_images", 0)) in (1, 2):
             from .builder.data.cxr_transform import collate_raw_cxr, transform_from_args
-            from .synthetic import make_raw_cxr
+            from .synthetic import jpeg_encode, make_raw_cxr
             g = torch.Generator().manual_seed(4241 + 7919 * rank + 104729 * epoch + it)
-            raw = collate_raw_cxr(make_raw_cxr(g.initial_seed(), bt["img_time"]), transform_from_args(args, train=True),
+            samples = make_raw_cxr(g.initial_seed(), bt["img_time"])
+            if int(args.raw_images) == 2:
+                samples = [([jpeg_encode(im) for im in ims], times) for ims, times in samples]
+            raw = collate_raw_cxr(samples, transform_from_args(args, train=True),
                                   int(getattr(args, "n_images", 3)) if multi else 0, generator=g)
             bt["img"], bt["img_time"] = raw, raw.img_time.half().float()
         yield (bt["x"], static, bt["y"], bt["input_lengths"], bt["img"], bt["img_time"], bt["txt"], bt["txt_lengths"],
@@ -94,8 +99,9 @@ def main(argv=None):
     from .builder.utils.cosine_annealing_with_warmup_v2 import CosineAnnealingWarmupRestarts
     parser = build_parser()
     parser.add_argument("--iters-per-epoch", type=int, default=100, help="len(train_loader) for synthetic data")
-    parser.add_argument("--raw-images", type=int, default=0, choices=[0, 1],
-                        help="1: synthetic batches carry uint8 images; the transform chain runs on the GPU (ops.cxr_prepare)")
+    parser.add_argument("--raw-images", type=int, default=0, choices=[0, 1, 2],
+                        help="1: synthetic batches carry uint8 images; the transform chain runs on the GPU (ops.cxr_prepare); "
+                             "2: they carry JPEG file bytes, decoded on the GPU in front of it (needs PIL to write the files)")
     args = parser.parse_args(argv)
     args.dir_root = os.getcwd()
     if int(args.synthetic) != 1:
@@ -105,6 +111,9 @@ def main(argv=None):
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("LOCAL_RANK", "0"), ("WORLD_SIZE", "1")))
     if not torch.cuda.is_available():
         raise SystemExit("training runs on an MI355X only (no CPU fallback)")
+    if int(args.raw_images) == 2:
+        from .synthetic import jpeg_encode
+        jpeg_encode(None)                              # fails here, by name, where PIL is not installed
     torch.cuda.set_device(local)
     device = torch.device("cuda", local)
     if ddp:
