@@ -630,6 +630,33 @@ int mtmp_jpeg_entropy(const uint8_t* streams, const int32_t* desc, const int32_t
 int mtmp_jpeg_idct(const int16_t* coef, const int32_t* desc, const int32_t* tables, const int32_t* status, uint8_t* pixels, int n,
                    int max_blocks, void* stream);
 
+/* ---- TIE event windows from a device-resident event store (additive; ABI stays 6): the reference builds every window on the
+ * host (builder/data/dataset_new.py:1969-2030, restated by builder/data/tie_dataset.py tie_window).  Here the data set is stored
+ * once (builder/data/tie_store.py: CSR over patients -> hours -> events) and a window is a row of `desc`; ONE launch writes the
+ * batch in the layout mtmp_tie_embed_packed_fwd reads, bit-identical to tie_window (+ the trainer's fp16 rounding).
+ *   ev_time / ev_val / ev_feat: float64 / float32 / uint8 [n_events], the events of all hours back to back (time, normalised
+ *            value, feature index); may be NULL when n_events is 0.
+ *   norm:    float32 [n_hours][18], the normalised carry-forward table; delta: float64 [n_hours][18], hours since measurement;
+ *   hour_min: float64 [n_hours], the earliest event time of the hour (+inf without one).
+ *   desc:    int64 [B][8] device, one row per window: 0 its first event, 1 its number of events (before the TIE-len cut), 2 the
+ *            hour whose norm / delta rows make the initial rows, 3 its first hour and 4 its number of hours after the trimming,
+ *            5 the mask of the features that come as initial rows (bit f = feature f), 6 t0, the first hour of the trimmed
+ *            window relative to the admission, 7 the (moved) prediction hour.
+ *   cu_seqlens: int32 [B + 1] device, prefix sums of the lengths AFTER the cut (row b of the batch has cu[b+1] - cu[b] rows:
+ *            its initial rows in feature order, then its events).  max_len / total_rows: the host's copy of the largest length
+ *            and of cu[B] (they size the launch; no device value is waited for).
+ *   Row r < popcount(mask): time = (-delta[f] + (t0 + 1)) - shift, value = norm[f], index = f for the r-th set bit f; row r beyond:
+ *   event first + r - popcount(mask), time - shift.  shift = desc[7] for realtime == 1, otherwise the minimum time over all rows
+ *   of the uncut window (recomputed per workgroup from the initial rows and hour_min).  float64 arithmetic, then float32, then
+ *   with round_fp16 float32 -> fp16 -> float32.
+ *   padded == 0: out float32 [out_rows][3], rows cu[B] .. out_rows - 1 are written as zeros (out_rows >= total_rows);
+ *   padded == 1: out float32 [B][t_pad][3], rows behind a sample's length are written as zeros (t_pad >= max_len).
+ *   A descriptor row that points outside the store's arrays has its rows written as zeros (both forms), not read out of bounds. */
+int mtmp_tie_window_gather(const double* ev_time, const float* ev_val, const uint8_t* ev_feat, const float* norm,
+                           const double* delta, const double* hour_min, long long n_events, long long n_hours,
+                           const long long* desc, const int32_t* cu_seqlens, float* out, int B, int max_len, int t_pad,
+                           long long total_rows, long long out_rows, int padded, int realtime, int round_fp16, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -120,6 +120,10 @@ class TRI_MBT_VSLTCLS(nn.Module):
         self.n_images = int(getattr(args, "n_images", 3)) if self.args.multiimages == 1 else 1
 
     head_fusable = True        # ie_demo = Linear -> LayerNorm -> ReLU: what ops.HeadFn fuses (a sibling may differ)
+    # forward accepts a PackedTie in place of the padded x.  The trainer asks before it hands windows of the event store over
+    # (trainer.py); a sibling that reads the padded tensor sets False, and a model class that does not define the flag at all is
+    # given the padded form too.
+    takes_packed_tie = True
     TRAINS_ENCODER_IN_REFERENCE = False      # this model and most siblings run the image encoder under no_grad (:205-209)
 
     def _make_embeddings(self, args) -> bool:

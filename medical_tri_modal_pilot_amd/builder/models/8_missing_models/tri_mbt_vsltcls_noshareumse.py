@@ -26,6 +26,7 @@ from .tri_mbt_vsltcls import TRI_MBT_VSLTCLS
 
 class TRI_MBT_VSLTCLS_NOSHAREUMSE(TRI_MBT_VSLTCLS):
     head_fusable = False          # ie_demo has no LayerNorm: the head's torch form (parent forward) runs
+    takes_packed_tie = False      # _vslt_embedding below reads the padded [B, T, 3] tensor
 
     def _make_embeddings(self, args) -> bool:
         def chain(n_in):

@@ -18,6 +18,7 @@ import torch
 from medical_tri_modal_pilot_amd import ops, tuning
 from medical_tri_modal_pilot_amd.builder.data.cxr_transform import RawCxrBatch
 from medical_tri_modal_pilot_amd.builder.data.tie_dataset import PackedTie, PackedTieBatch
+from medical_tri_modal_pilot_amd.builder.data.tie_store import TieWindowBatch
 
 GRAPH_LEN_BUCKET = 128
 GRAPH_EVENT_BUCKET = 4096       # packed batches: the event count is rounded up to this for hipGraph replays
@@ -226,6 +227,22 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
             max_len = graph_len_bucket(max_len, int(args.TIE_len))
         pk = train_x.on_device(device, max_len, GRAPH_EVENT_BUCKET if graphed else 0)   # fp16 rounding inside
         data, cu_seqlens, t_pad = pk.events, pk.cu_seqlens, pk.t_pad
+    elif isinstance(train_x, TieWindowBatch):
+        # Windows of the device-resident event store (builder/data/tie_store.py): the batch is its host plan, the events are
+        # gathered here, eagerly in front of the step like ops.cxr_prepare's images -- one launch that writes what on_device
+        # above hands over (fp16 rounding, event bucket and zero tail included) and fills the captured graph's static input.
+        # The lengths are the plan's: nothing waits for the device.  A model class says with ``takes_packed_tie = True`` that its
+        # forward accepts a PackedTie (TRI_MBT_VSLTCLS and the siblings derived from it, unless they override it); a class
+        # WITHOUT the attribute gets the padded tensor of the trim below -- always correct, at the price of the pad rows.
+        graphed = _use_graph(args, flow_type, device, optimizer, scaler)
+        max_len = max(1, train_x.max_len)
+        if graphed:
+            max_len = graph_len_bucket(max_len, int(args.TIE_len))
+        if getattr(model, "takes_packed_tie", False):
+            pk = ops.tie_windows(train_x, device, max_len, GRAPH_EVENT_BUCKET if graphed else 0)
+            data, cu_seqlens, t_pad = pk.events, pk.cu_seqlens, pk.t_pad
+        else:
+            data = ops.tie_windows(train_x, device, max_len, padded=True)
     elif args.vslt_type == "carryforward":
         train_x = train_x.permute(1, 0, 2, 3)
         data = train_x[0].half().float().to(device, non_blocking=True)

@@ -111,6 +111,44 @@ def make_batch(seed: int, B: int, T: int, *, ragged: bool = True, missing_mode: 
                 img_time=img_time, txt_time=txt_time, y=y, missing=missing, missing_num=mnum)
 
 
+def make_tie_patients(seed: int, n_patients: int = 32, events_per_hour: int = 50):
+    """Seeded stand-ins for the reference's per-admission pickles (keys ``data``, ``delta``, ``data_in_time``, ``age``,
+    ``gender``) and their feature range: 30 to 72 hours each, hours without a measurement (``None``) at both ends and inside,
+    present hours without an event, and -- every fourth patient -- ``events_per_hour`` events in every hour, so that a
+    24-hour window holds more than 1000 of them.  Returns ``(patients, feature_mins, feature_maxs)``."""
+    rng = np.random.default_rng(seed)
+    fmin = np.linspace(-1.0, 2.0, 18)
+    fmax = fmin + np.linspace(3.0, 40.0, 18)
+    patients = []
+    for i in range(n_patients):
+        H = int(rng.integers(30, 73))
+        dense = i % 4 == 0
+        present = np.ones(H, bool) if dense else rng.random(H) > 0.25
+        if not dense:
+            present[:int(rng.integers(0, 3))] = False
+            present[H - int(rng.integers(0, 3)):] = False
+            present[H // 2] = True
+        dit = []
+        for h in range(H):
+            if not present[h]:
+                dit.append(None)
+                continue
+            n = events_per_hour if dense else int(rng.integers(0, 12))          # 0: a present hour without an event
+            t = np.sort(np.round(h + rng.random(n), 4))
+            dit.append(np.stack([t, rng.random(n), rng.integers(0, 18, n).astype(np.float64)], axis=1).reshape(n, 3))
+        data = fmin + (fmax - fmin) * rng.random((H, 18))
+        delta = rng.integers(0, 6, (H, 18)).astype(np.float64)
+        patients.append(dict(data=data, delta=delta, data_in_time=dit, age=float(rng.random()), gender="M" if rng.integers(2) else "F"))
+    return patients, fmin, fmax
+
+
+def make_tie_store(seed: int, n_patients: int = 32, events_per_hour: int = 50):
+    """builder/data/tie_store.TieEventStore of ``make_tie_patients`` (on the host; ``.to(device)`` uploads it)."""
+    from .builder.data.tie_store import TieEventStore
+    patients, fmin, fmax = make_tie_patients(seed, n_patients, events_per_hour)
+    return TieEventStore.from_patients(patients, fmin, fmax)
+
+
 RAW_CXR_SIZES = ((256, 311), (311, 256), (256, 256), (300, 256))     # h x w of the stand-ins (MIMIC-CXR-JPG resized to ~256)
 
 

@@ -14,6 +14,9 @@ build-only flags wired in:
                       every --image-train-type but resize_larger, RandomResizedCrop (random) and RandAugment (randaug) included
     --raw-images 2    the same images JPEG-encoded (PIL writes them, as the reference's preprocessing does): the batches carry
                       file bytes, and the decoder runs on the GPU in front of that chain (ops.jpeg_decode, csrc/jpeg.hip)
+    --tie-store 1     the vital-sign windows come from a synthetic device-resident event store (synthetic.make_tie_store: None
+                      hours at both ends, empty present hours, windows over 1000 events): the loader hands over (patient, hour,
+                      length) triples, builder/data/tie_store.py plans them, ops.tie_windows gathers in front of the step
 
     python -m medical_tri_modal_pilot_amd.train --input-types vslt_img_txt --model tri_mbt_vsltcls \\
         --modality-inclusion train-missing_test-missing --lr-init 1e-5 --batch-size 64 --epochs 1 \\
@@ -47,7 +50,7 @@ class _Logger:
         self.lr = lr
 
 
-def synthetic_loader(args, n_iters: int, rank: int, epoch: int):
+def synthetic_loader(args, n_iters: int, rank: int, epoch: int, tie_store=None):
     """n_iters batches of the 12-tuple of 2_train.py:143 (CPU tensors, like the reference's loader output)."""
     from .synthetic import make_batch
     multi = int(args.multiimages)
@@ -66,6 +69,18 @@ def synthetic_loader(args, n_iters: int, rank: int, epoch: int):
             raw = collate_raw_cxr(samples, transform_from_args(args, train=True),
                                   int(getattr(args, "n_images", 3)) if multi else 0, generator=g)
             bt["img"], bt["img_time"] = raw, raw.img_time.half().float()
+        if tie_store is not None:
+            # the vital-sign stream as windows of the device-resident event store: the loader hands over B triples, the plan
+            # is host work on the hour-level arrays, the events are gathered in front of the step (ops.tie_windows)
+            import random
+            from .builder.data.tie_store import StoreWindowDataset
+            random.seed(977 + 7919 * rank + 104729 * epoch + it)
+            ds = StoreWindowDataset(tie_store)
+            wb = tie_store.plan([ds[random.randrange(len(ds))] for _ in range(args.batch_size)], int(args.TIE_len),
+                                int(args.realtime), "train-missing" in args.modality_inclusion)
+            bt["x"], static, bt["input_lengths"] = wb, wb.static, wb.input_lengths
+            if int(args.realtime) == 1:
+                bt["txt_time"] = wb.txt_time
         yield (bt["x"], static, bt["y"], bt["input_lengths"], bt["img"], bt["img_time"], bt["txt"], bt["txt_lengths"],
                bt["txt_time"], bt["missing"], None, None)
 
@@ -102,6 +117,9 @@ def main(argv=None):
     parser.add_argument("--raw-images", type=int, default=0, choices=[0, 1, 2],
                         help="1: synthetic batches carry uint8 images; the transform chain runs on the GPU (ops.cxr_prepare); "
                              "2: they carry JPEG file bytes, decoded on the GPU in front of it (needs PIL to write the files)")
+    parser.add_argument("--tie-store", type=int, default=0, choices=[0, 1],
+                        help="1: the vital-sign windows come from a synthetic device-resident event store "
+                             "(builder/data/tie_store.py); the loader hands over (patient, hour, length) triples")
     args = parser.parse_args(argv)
     args.dir_root = os.getcwd()
     if int(args.synthetic) != 1:
@@ -126,12 +144,19 @@ def main(argv=None):
     scheduler = CosineAnnealingWarmupRestarts(optimizer, first_cycle_steps=args.t_0 * n_it, cycle_mult=args.t_mult,
                                               max_lr=args.lr_init * math.sqrt(args.batch_size), min_lr=1e-6,
                                               warmup_steps=args.t_up * n_it, gamma=args.gamma)      # 2_train.py:118-124
+    tie_store = None
+    if int(args.tie_store) == 1:
+        from .synthetic import make_tie_store
+        tie_store = make_tie_store(4099).to(device)
+        if rank == 0:
+            print(f"event store: {tie_store.n_patients} patients, {tie_store.n_hours} hours, {tie_store.n_events} events, "
+                  f"{tie_store.nbytes} bytes on {device}", flush=True)
     logger = _Logger()
     model.train()                                                                                    # 2_train.py:128
     iteration = 0
     for epoch in range(1, int(args.epochs) + 1):
         logger.loss, t0 = 0.0, time.perf_counter()
-        for it, batch in enumerate(synthetic_loader(args, n_it, rank, epoch), 1):
+        for it, batch in enumerate(synthetic_loader(args, n_it, rank, epoch, tie_store), 1):
             x, static, y, in_len, img, img_time, txt, txt_len, txt_time, missing, _f, _y2 = batch
             iteration += 1
             model, iter_loss = get_trainer(args=args, iteration=iteration, x=x, static=static, input_lengths=in_len, y=y,
