@@ -657,6 +657,22 @@ int mtmp_tie_window_gather(const double* ev_time, const float* ev_val, const uin
                            const long long* desc, const int32_t* cu_seqlens, float* out, int B, int max_len, int t_pad,
                            long long total_rows, long long out_rows, int padded, int realtime, int round_fp16, void* stream);
 
+/* ---- report token embeddings from a device-resident embedding store (additive; ABI stays 6): the reference reads a report's
+ * [len][768] BioBERT embeddings from an h5 file per sample, appends zeros up to [128][768] and stacks the batch on the host
+ * (builder/data/dataset_new.py:2135-2155).  Here every report is stored once (builder/data/report_store.py: CSR over reports ->
+ * token rows) and a sample is a row of `desc`; ONE launch writes the batch the text projection reads.
+ *   emb:   [total_tokens][W] in emb_dtype (MTMP_F32 | MTMP_BF16), the reports' token rows back to back; may be NULL when
+ *          total_tokens is 0.
+ *   desc:  int64 [B][2] device, one row per sample: 0 its first token row in emb, 1 its number of tokens n (0: a missing report).
+ *   out:   [B][L][W] in out_dtype.  Row t < n of sample b is row desc[b][0] + t of emb; every other row is written as zeros (no
+ *          memset is needed in front) and reads nothing from emb.  MTMP_F32 -> MTMP_BF16 rounds to nearest even with the bits of
+ *          torch's .to(torch.bfloat16) (a NaN stays a NaN); MTMP_BF16 -> MTMP_F32 is exact; equal types copy.
+ *   W % 8 == 0 (a row is a whole number of 16-byte pieces in either type: every global access is 16 bytes per lane); emb and out
+ *   16-byte aligned.  A descriptor row with first < 0, n < 0, n > L or first + n > total_tokens has its sample written as zeros,
+ *   not read out of bounds. */
+int mtmp_report_gather(const void* emb, int emb_dtype, long long total_tokens, const long long* desc, void* out, int out_dtype,
+                       int B, int L, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

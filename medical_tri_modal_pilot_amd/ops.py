@@ -578,6 +578,34 @@ def tie_windows(batch, device, t_pad: int, bucket: int = 0, padded: bool = False
     return out if padded else PackedTie(out, cu, int(t_pad))
 
 
+# ---- report token embeddings from the device-resident embedding store (csrc/report_store.hip) ----------------------------
+def report_tokens(batch, device, dtype, out=None, tables=None):
+    """ReportBatch (builder/data/report_store.py: the host plan of a batch of report indices) -> the ``[B, max_tokens, width]``
+    tensor of ``dtype`` (float32 | bfloat16) the reference's loader and collate build on the host and the trainer uploads: row
+    ``t < txt_lengths[b]`` of sample b is token t of its report, every other row zeros, in ONE launch that writes all of it (no
+    memset).  From a float32 store to bfloat16 the values are rounded as ``.to(torch.bfloat16)`` rounds them.  The store must be on
+    ``device`` (``store.to(device, dtype)``, once).  One small host-to-device copy (the descriptor), no device value is waited
+    for.  out: a buffer to write into; tables: the descriptor already on the device (tools/bench_report_store.py times the
+    launch alone, the tests hand over descriptors the plan would never make)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"medical_tri_modal_pilot_amd ops run on an MI355X only (report_tokens on {device}); there is no CPU fallback")
+    store = batch.store
+    B, L, W = batch.batch_size, batch.max_tokens, batch.width
+    desc = batch.descriptor().to(device, non_blocking=True) if tables is None else tables
+    if store.device != desc.device:
+        raise RuntimeError(f"report_tokens: the report store is on {store.device}, not on {desc.device}: call store.to(device) once")
+    if tuple(desc.shape) != (B, 2) or desc.dtype != torch.int64 or not desc.is_contiguous():
+        raise ValueError(f"report_tokens: the descriptor must be a contiguous int64 tensor {(B, 2)}")
+    if out is None:
+        out = torch.empty((B, L, W), dtype=dtype, device=device)
+    elif tuple(out.shape) != (B, L, W) or out.dtype != dtype or not out.is_contiguous() or out.device != desc.device:
+        raise ValueError(f"report_tokens: out must be a contiguous {dtype} tensor {(B, L, W)} on {device}")
+    with torch.cuda.device(device), kernel_marks("report_gather", B):
+        call("mtmp_report_gather", _p(store.emb), _dt(store.emb), store.n_tokens, _p(desc), _p(out), _dt(out), B, L, W, _stream())
+    return out
+
+
 # ---- packed token streams (the ragged vital-sign stream without its pad rows) ------------------------------------------
 # A stream is PACKED when its samples' valid rows (bottleneck prefix + CLS + events = kv_len[b]) sit back to back in the
 # [B * N_max, 256] buffers instead of N_max rows apart: `pack` = row_starts(kv_len, N_max), int32[2 B + 1] on the device --

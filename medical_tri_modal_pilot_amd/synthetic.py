@@ -149,6 +149,18 @@ def make_tie_store(seed: int, n_patients: int = 32, events_per_hour: int = 50):
     return TieEventStore.from_patients(patients, fmin, fmax)
 
 
+def make_report_store(seed: int, n_reports: int = 256, width: int = 768, max_tokens: int = 128):
+    """builder/data/report_store.ReportStore of seeded stand-ins for the BioBERT report embeddings (on the host; ``.to(device,
+    dtype)`` uploads it): report ``i`` is keyed ``"report i"``, lengths drawn like ``make_batch`` draws its ``txt_lengths``
+    (uniform on 1 .. max_tokens - 2), except report 0 with ONE token and report 1 with ``max_tokens``; standard normal values."""
+    from .builder.data.report_store import ReportStore
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.randint(1, max_tokens - 1, (n_reports,), generator=g)
+    lens[:2] = torch.tensor([1, max_tokens])[:n_reports]
+    return ReportStore.from_mapping({f"report {i}": {"embedding": torch.randn(int(n), width, generator=g).numpy()}
+                                     for i, n in enumerate(lens.tolist())}, width, max_tokens)
+
+
 RAW_CXR_SIZES = ((256, 311), (311, 256), (256, 256), (300, 256))     # h x w of the stand-ins (MIMIC-CXR-JPG resized to ~256)
 
 

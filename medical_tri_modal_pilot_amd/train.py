@@ -17,6 +17,9 @@ build-only flags wired in:
     --tie-store 1     the vital-sign windows come from a synthetic device-resident event store (synthetic.make_tie_store: None
                       hours at both ends, empty present hours, windows over 1000 events): the loader hands over (patient, hour,
                       length) triples, builder/data/tie_store.py plans them, ops.tie_windows gathers in front of the step
+    --report-store 1  the report embeddings come from a synthetic device-resident embedding store (synthetic.make_report_store):
+                      the loader hands over one report index per sample, builder/data/report_store.py plans them,
+                      ops.report_tokens gathers in front of the step, in the model's compute type
 
     python -m medical_tri_modal_pilot_amd.train --input-types vslt_img_txt --model tri_mbt_vsltcls \\
         --modality-inclusion train-missing_test-missing --lr-init 1e-5 --batch-size 64 --epochs 1 \\
@@ -50,7 +53,7 @@ class _Logger:
         self.lr = lr
 
 
-def synthetic_loader(args, n_iters: int, rank: int, epoch: int, tie_store=None):
+def synthetic_loader(args, n_iters: int, rank: int, epoch: int, tie_store=None, report_store=None):
     """n_iters batches of the 12-tuple of 2_train.py:143 (CPU tensors, like the reference's loader output)."""
     from .synthetic import make_batch
     multi = int(args.multiimages)
@@ -81,6 +84,14 @@ def synthetic_loader(args, n_iters: int, rank: int, epoch: int, tie_store=None):
             bt["x"], static, bt["input_lengths"] = wb, wb.static, wb.input_lengths
             if int(args.realtime) == 1:
                 bt["txt_time"] = wb.txt_time
+        if report_store is not None:
+            # the reports as indices into the device-resident embedding store: the loader hands over B integers, the plan
+            # applies the batch's modality combinations (1 and 3 drop the report), the rows are gathered in front of the step
+            g = torch.Generator().manual_seed(3373 + 7919 * rank + 104729 * epoch + it)
+            rb = report_store.plan(torch.randint(0, report_store.n_reports, (args.batch_size,), generator=g).numpy(),
+                                   bt["missing_num"].numpy())
+            bt["txt"], bt["txt_lengths"] = rb, rb.txt_lengths
+            bt["missing"] = torch.stack([bt["missing"][:, 0], bt["missing"][:, 1], rb.missing], 1)
         yield (bt["x"], static, bt["y"], bt["input_lengths"], bt["img"], bt["img_time"], bt["txt"], bt["txt_lengths"],
                bt["txt_time"], bt["missing"], None, None)
 
@@ -120,6 +131,9 @@ def main(argv=None):
     parser.add_argument("--tie-store", type=int, default=0, choices=[0, 1],
                         help="1: the vital-sign windows come from a synthetic device-resident event store "
                              "(builder/data/tie_store.py); the loader hands over (patient, hour, length) triples")
+    parser.add_argument("--report-store", type=int, default=0, choices=[0, 1],
+                        help="1: the report embeddings come from a synthetic device-resident embedding store "
+                             "(builder/data/report_store.py); the loader hands over one report index per sample")
     args = parser.parse_args(argv)
     args.dir_root = os.getcwd()
     if int(args.synthetic) != 1:
@@ -151,12 +165,19 @@ def main(argv=None):
         if rank == 0:
             print(f"event store: {tie_store.n_patients} patients, {tie_store.n_hours} hours, {tie_store.n_events} events, "
                   f"{tie_store.nbytes} bytes on {device}", flush=True)
+    report_store = None
+    if int(args.report_store) == 1:
+        from .synthetic import make_report_store
+        report_store = make_report_store(5003).to(device, getattr(model, "compute_dtype", torch.float32))
+        if rank == 0:
+            print(f"report store: {report_store.n_reports} reports, {report_store.n_tokens} tokens, {report_store.nbytes} bytes "
+                  f"({report_store.dtype}) on {device}", flush=True)
     logger = _Logger()
     model.train()                                                                                    # 2_train.py:128
     iteration = 0
     for epoch in range(1, int(args.epochs) + 1):
         logger.loss, t0 = 0.0, time.perf_counter()
-        for it, batch in enumerate(synthetic_loader(args, n_it, rank, epoch, tie_store), 1):
+        for it, batch in enumerate(synthetic_loader(args, n_it, rank, epoch, tie_store, report_store), 1):
             x, static, y, in_len, img, img_time, txt, txt_len, txt_time, missing, _f, _y2 = batch
             iteration += 1
             model, iter_loss = get_trainer(args=args, iteration=iteration, x=x, static=static, input_lengths=in_len, y=y,
@@ -174,6 +195,11 @@ def main(argv=None):
             dt = time.perf_counter() - t0
             print(f"epoch {epoch}: mean loss {logger.loss / n_it:.5f}, {world * args.batch_size * n_it / dt:.1f} samples/s "
                   f"(host-resident synthetic batches, H2D inside the step)", flush=True)
+    gs = getattr(model, "_mtmp_graph_step", None)
+    if rank == 0 and gs is not None:
+        st = gs.stats()
+        print(f"hipGraph: {st['captures']} captures, {st['replays']} replays, {st['eager_over_budget']} eager steps past the "
+              f"capture budget", flush=True)
     if ddp:
         dist.destroy_process_group()
     return logger.loss / max(1, n_it)
