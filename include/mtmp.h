@@ -673,6 +673,36 @@ int mtmp_tie_window_gather(const double* ev_time, const float* ev_val, const uin
 int mtmp_report_gather(const void* emb, int emb_dtype, long long total_tokens, const long long* desc, void* out, int out_dtype,
                        int B, int L, int W, void* stream);
 
+/* ---- token-id reports (--berttype bert) from a device-resident store, the embedding lookup and its gradient (additive; ABI
+ * stays 6).  The reference's loader puts a BOS (2) in front of a report's ids, trims, appends an EOS (3), pads and replaces every
+ * 1 by 0 (builder/data/dataset_new.py:2157-2175, clinical_note_transform :186-192); its model looks the ids up in a trained
+ * nn.Embedding(30000, 256).  builder/data/report_store.py (TokenReportStore) keeps every report's ids once, CSR.
+ *
+ * mtmp_report_ids_gather: ONE launch writes out int32 [B][L], every element (no memset in front).
+ *   ids:   int32 [total], the reports' ids back to back; may be NULL when total is 0.
+ *   desc:  int64 [B][2] device, one row per sample: 0 its first id in `ids`, 1 its number of ids n, UNTRIMMED (0: missing).
+ *   out:   with k = min(n, L - 2): [2, t_0 .. t_{k-1}, 3, 0 .. 0], every t_i == 1 written as 0; all zeros when n == 0.
+ *   L >= 3; out 16-byte aligned.  A row with first < 0, n < 0 or first + n > total has its sample written as zeros.
+ *
+ * mtmp_token_embed_fwd: out[t] = table[ids[t]], t < T; table [V][D] and out [T][D] in MTMP_F32 | MTMP_BF16 each.  MTMP_F32 ->
+ *   MTMP_BF16 rounds to nearest even with the bits of torch's .to(torch.bfloat16); MTMP_BF16 -> MTMP_F32 is exact; equal types
+ *   copy.  Every lane moves 16-byte pieces.  An id outside [0, V) gives a zero row and reads nothing.  D == 256 only.
+ *
+ * mtmp_token_embed_bwd: dw[v] = sum over {t : ids[t] == v} of dy[t] in float32; dy [T][D] in dy_dtype, dw float32 [V][D].
+ *   Only the rows v that have a token are WRITTEN (overwritten, not accumulated into); the caller hands over a zeroed dw if it
+ *   wants zeros elsewhere.  No float atomics: the order of every sum depends on the positions t alone -- rows in ascending t
+ *   inside chunks of mtmp_token_embed_bwd_chunk() rows of an id's position list, then the chunks' partial sums in chunk order --
+ *   so equal inputs give equal bits.  Ids outside [0, V) contribute nothing.  Two launches.  workspace: device memory of
+ *   mtmp_token_embed_bwd_workspace(T, V) bytes, 16-byte aligned, contents irrelevant before and after.  D == 256 only;
+ *   T <= 2^24. */
+int mtmp_report_ids_gather(const int32_t* ids, long long total, const long long* desc, int32_t* out, int B, int L, void* stream);
+int mtmp_token_embed_fwd(const int32_t* ids, long long T, const void* table, int table_dtype, void* out, int out_dtype, int V,
+                         int D, void* stream);
+long long mtmp_token_embed_bwd_workspace(long long T, int V);
+int mtmp_token_embed_bwd_chunk(void);
+int mtmp_token_embed_bwd(const int32_t* ids, long long T, const void* dy, int dy_dtype, float* dw, void* workspace, int V, int D,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

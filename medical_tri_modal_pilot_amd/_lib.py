@@ -121,6 +121,11 @@ SIGNATURES = {
     "mtmp_tie_window_gather": (c_int, [c_void_p] * 6 + [c_longlong, c_longlong] + [c_void_p] * 3 + [c_int] * 3 +
                                [c_longlong, c_longlong] + [c_int] * 3 + [c_void_p]),
     "mtmp_report_gather": (c_int, [c_void_p, c_int, c_longlong, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "mtmp_report_ids_gather": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "mtmp_token_embed_fwd": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "mtmp_token_embed_bwd_workspace": (c_longlong, [c_longlong, c_int]),
+    "mtmp_token_embed_bwd_chunk": (c_int, []),
+    "mtmp_token_embed_bwd": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "mtmp_dropout_bwd": (c_int, [c_int, c_void_p, c_void_p, c_longlong, c_uint, c_void_p, c_float, c_void_p]),
 }
 

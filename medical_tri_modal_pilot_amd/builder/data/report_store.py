@@ -154,3 +154,128 @@ class ReportStore:
         first = np.where(miss, 0, first).astype(np.int64)
         return ReportBatch(self, idx, first, n, torch.from_numpy(n.copy()), torch.from_numpy(miss.astype(np.float32)))
 
+
+# ------------------------------------------------------------------------------------------------- token-id reports (--berttype bert)
+# The reference's second text branch (dataset_new.py:2157-2175): a report is a list of token ids, ``txtDict[(pat_id, chid)]``, and the
+# model looks them up in a TRAINED ``nn.Embedding(30000, 256)``.  Per sample the loader puts a BOS (2) in front, lets
+# ``clinical_note_transform`` (:186-192) trim to ``L - 1`` values, append an EOS (3) and pad with 1 up to ``L =
+# --bert-token-max-length``, and replaces every 1 by 0.  With ``n`` ids and ``k = min(n, L - 2)`` that is
+#     tokens[L] = [2, t_0 .. t_{k-1}, 3, 0 .. 0]  with every 1 written as 0,        textLength = n (NOT trimmed),
+# and zeros with textLength 0 for a missing sample.  The ids are stored once (``TokenReportStore``), a sample is ONE integer, the plan
+# is the control flow on the counts, and ``ops.report_token_ids`` (csrc/token_embed.hip) writes the int32 ``[B, L]`` batch.
+#
+# Two things the reference does that the store does NOT reproduce: (1) ``tokens.insert(0, 2)`` and the short branch's
+# ``tokens.append(3)`` change the list INSIDE ``txtDict``, so the same report grows by a BOS and an EOS on every read -- the store
+# reproduces a FIRST read, of a copy it made; (2) a key that ``txtDict`` lacks raises ``KeyError`` in ``__getitem__`` (the data set's
+# ``__init__`` drops such files beforehand, :300-308) -- here ``index_of`` gives -1 and the plan treats the sample as missing.
+class TokenReportBatch:
+    """The host plan of a batch of token-id reports: everything but the ids.  ``ops.report_token_ids`` turns it into the int32
+    ``[B, max_length]`` tensor on the device; the lengths and the missing flags are here without a device sync."""
+
+    def __init__(self, store, report_idx, first_token, n_tokens, txt_lengths, key_lengths, missing):
+        self.store, self.report_idx = store, report_idx
+        self.first_token, self.n_tokens = first_token, n_tokens          # int64 [B] each; 0 ids when missing
+        self.txt_lengths = txt_lengths                                   # int64 [B]: the reference's textLength, UNTRIMMED
+        self.key_lengths = key_lengths                                   # int64 [B]: min(textLength, L - 2), what the model's mask reads
+        self.missing = missing                                           # float32 [B], column 2 of the loader's `missing`
+        self.max_length = store.max_length
+
+    @property
+    def batch_size(self) -> int:
+        return int(self.txt_lengths.numel())
+
+    def descriptor(self) -> torch.Tensor:
+        """int64 [B, DESC_WORDS]: the per-sample words of mtmp_report_ids_gather."""
+        return torch.from_numpy(np.ascontiguousarray(np.stack([self.first_token, self.n_tokens], axis=1).astype(np.int64)))
+
+
+class TokenReportStore:
+    """CSR form of all reports' token ids: ``tok_ptr`` int64 [R + 1] (host, numpy) and ``ids`` int32 [total] (a torch tensor: on
+    the host after building, on the device after ``to``)."""
+
+    def __init__(self, tok_ptr, ids, index, vocab: int = 30000, max_length: int = 128):
+        self.tok_ptr, self.ids, self._index = tok_ptr, ids, index
+        self.vocab, self.max_length = int(vocab), int(max_length)
+        self.device = torch.device("cpu")
+
+    @classmethod
+    def from_mapping(cls, mapping, vocab: int = 30000, max_length: int = 128):
+        """``mapping[(pat_id, chid)]`` -> sequence of ints, the shape of the reference's ``txtDictLoad`` result, in the mapping's
+        own order.  The ids are COPIED: the caller's lists are neither kept nor changed."""
+        if max_length < 3:
+            raise ValueError(f"TokenReportStore: max_length {max_length} < 3 leaves no room for BOS, one id and EOS")
+        if vocab < 4:
+            raise ValueError(f"TokenReportStore: vocab {vocab} < 4 does not hold UNK, PAD, BOS and EOS")
+        index, counts, rows = {}, [], []
+        for key in mapping:
+            k = (int(key[0]), int(key[1]))
+            if k in index:
+                raise ValueError(f"TokenReportStore: two reports share the key {k}")
+            a = np.array(mapping[key], copy=True)
+            if a.size == 0:
+                a = np.zeros(0, np.int64)
+            if a.ndim != 1:
+                raise ValueError(f"TokenReportStore: report {k} has shape {tuple(a.shape)}, want a flat sequence of ids")
+            if a.dtype.kind not in "iu":
+                raise ValueError(f"TokenReportStore: report {k} holds a non-integer value ({a.dtype})")
+            if ((a < 0) | (a >= vocab)).any():
+                bad = a[(a < 0) | (a >= vocab)][0]
+                raise ValueError(f"TokenReportStore: report {k} holds the id {int(bad)}, outside [0, {vocab})")
+            index[k] = len(counts)
+            counts.append(a.shape[0])
+            rows.append(a.astype(np.int32))
+        tok_ptr = np.zeros(len(counts) + 1, np.int64)
+        np.cumsum(np.asarray(counts, np.int64), out=tok_ptr[1:])
+        ids = np.concatenate(rows) if rows else np.zeros(0, np.int32)
+        return cls(tok_ptr, torch.from_numpy(np.ascontiguousarray(ids, np.int32)), index, vocab, max_length)
+
+    def index_of(self, pat_id, chid) -> int:
+        """index of the report ``txtDict[(int(pat_id), int(chid))]``; -1 for a key the store does not hold"""
+        return self._index.get((int(pat_id), int(chid)), -1)
+
+    @property
+    def n_reports(self) -> int:
+        return int(self.tok_ptr.shape[0] - 1)
+
+    @property
+    def n_tokens(self) -> int:
+        return int(self.tok_ptr[-1])
+
+    @property
+    def nbytes(self) -> int:
+        """size of the ids as they are held: 4 bytes per token"""
+        return int(self.ids.numel() * 4)
+
+    def to(self, device):
+        """Upload the ids once (no host copy is kept); ``tok_ptr`` stays on the host for ``plan``."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device != self.device:
+            self.ids = self.ids.to(device)
+            self.device = self.ids.device
+        return self
+
+    def plan(self, report_idx, missing_comb=None) -> TokenReportBatch:
+        """``report_idx`` int [B]: the report of every sample, -1 where ``report_wanted`` is false or ``index_of`` gave -1;
+        ``missing_comb``: the loader's per-sample (or one for all) modality combination, 1 and 3 drop the report (:2159).
+        The same control flow as ``ReportStore.plan``, on the id counts alone: no id is touched."""
+        idx = np.asarray(report_idx)
+        if idx.ndim != 1 or idx.shape[0] < 1 or idx.dtype.kind not in "iu":
+            raise ValueError(f"plan: report_idx must be an integer array [B >= 1], got {idx.dtype} {idx.shape}")
+        idx = idx.astype(np.int64)
+        if (idx >= self.n_reports).any():
+            b = int(np.flatnonzero(idx >= self.n_reports)[0])
+            raise ValueError(f"plan: sample {b} names report {int(idx[b])}, the store holds 0..{self.n_reports - 1}")
+        have = idx >= 0
+        at = np.where(have, idx, 0)
+        first = self.tok_ptr[at] if self.n_reports else np.zeros_like(at)
+        n = (self.tok_ptr[at + 1] - first) if self.n_reports else np.zeros_like(at)
+        miss = ~have | (n == 0)
+        if missing_comb is not None:
+            mc = np.broadcast_to(np.asarray(missing_comb), idx.shape)
+            miss = miss | (mc == 1) | (mc == 3)
+        n = np.where(miss, 0, n).astype(np.int64)
+        first = np.where(miss, 0, first).astype(np.int64)
+        return TokenReportBatch(self, idx, first, n, torch.from_numpy(n.copy()),
+                                torch.from_numpy(np.minimum(n, self.max_length - 2)), torch.from_numpy(miss.astype(np.float32)))

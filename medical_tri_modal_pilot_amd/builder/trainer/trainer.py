@@ -18,7 +18,7 @@ import torch
 from medical_tri_modal_pilot_amd import ops, tuning
 from medical_tri_modal_pilot_amd.builder.data.cxr_transform import RawCxrBatch
 from medical_tri_modal_pilot_amd.builder.data.tie_dataset import PackedTie, PackedTieBatch
-from medical_tri_modal_pilot_amd.builder.data.report_store import ReportBatch
+from medical_tri_modal_pilot_amd.builder.data.report_store import ReportBatch, TokenReportBatch
 from medical_tri_modal_pilot_amd.builder.data.tie_store import TieWindowBatch
 
 GRAPH_LEN_BUCKET = 128
@@ -278,6 +278,21 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
                 raise ValueError("txt_lengths differs from the lengths of the ReportBatch's plan (pass None, or the plan's own)")
         txt_lengths = x_txt.txt_lengths
         x_txt = ops.report_tokens(x_txt, device, getattr(model, "compute_dtype", torch.float32))
+    elif isinstance(x_txt, TokenReportBatch):
+        # Token-id reports of the device-resident store (--berttype bert): the same hand-over, the int32 [B, L] ids -- BOS, the
+        # report trimmed to L - 2 ids, EOS, zeros -- written by one launch in front of the step.  The caller's lengths are the
+        # reference's UNTRIMMED textLength and are checked against the plan's; the model gets key_lengths = min(textLength, L - 2),
+        # so that its key count textLength + 2 never names more rows than the stream has (the mask is the same: all L rows).
+        if getattr(args, "berttype", "biobert") != "bert":
+            raise ValueError("a TokenReportBatch holds token ids; a model built with --berttype "
+                             f"{getattr(args, 'berttype', 'biobert')} reads BioBERT token embeddings")
+        if txt_lengths is not None:
+            if torch.is_tensor(txt_lengths) and txt_lengths.is_cuda:          # comparing it would make the host wait for the device
+                raise ValueError("with a TokenReportBatch, txt_lengths is None or a host tensor (the plan's own lengths are on the host)")
+            if not torch.equal(torch.as_tensor(txt_lengths).long(), x_txt.txt_lengths):
+                raise ValueError("txt_lengths differs from the lengths of the TokenReportBatch's plan (pass None, or the plan's own)")
+        txt_lengths = x_txt.key_lengths
+        x_txt = ops.report_token_ids(x_txt, device)
     else:
         x_txt = x_txt.to(device, non_blocking=True)
     if isinstance(x_img, RawCxrBatch):

@@ -606,6 +606,104 @@ def report_tokens(batch, device, dtype, out=None, tables=None):
     return out
 
 
+# ---- token-id reports (--berttype bert): ids from the device-resident store, the lookup and its gradient (csrc/token_embed.hip) ----
+def report_token_ids(batch, device, out=None, tables=None):
+    """TokenReportBatch (builder/data/report_store.py: the host plan of a batch of report indices) -> the int32 ``[B, max_length]``
+    tensor of token ids the reference's loader builds as float32 on the host (BOS, the report's ids trimmed to ``max_length - 2``,
+    EOS, zeros; every 1 written as 0), in ONE launch that writes all of it (no memset).  The same contract as ``report_tokens``:
+    the store must be on ``device`` (``store.to(device)``, once), one small host-to-device copy (the descriptor), no device value
+    is waited for.  out: a buffer to write into; tables: the descriptor already on the device."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"medical_tri_modal_pilot_amd ops run on an MI355X only (report_token_ids on {device}); there is no CPU fallback")
+    store = batch.store
+    B, L = batch.batch_size, batch.max_length
+    desc = batch.descriptor().to(device, non_blocking=True) if tables is None else tables
+    if store.device != desc.device:
+        raise RuntimeError(f"report_token_ids: the token store is on {store.device}, not on {desc.device}: call store.to(device) once")
+    if tuple(desc.shape) != (B, 2) or desc.dtype != torch.int64 or not desc.is_contiguous():
+        raise ValueError(f"report_token_ids: the descriptor must be a contiguous int64 tensor {(B, 2)}")
+    if out is None:
+        out = torch.empty((B, L), dtype=torch.int32, device=device)
+    elif tuple(out.shape) != (B, L) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != desc.device:
+        raise ValueError(f"report_token_ids: out must be a contiguous int32 tensor {(B, L)} on {device}")
+    with torch.cuda.device(device), kernel_marks("report_ids_gather", B):
+        call("mtmp_report_ids_gather", _p(store.ids), store.n_tokens, _p(desc), _p(out), B, L, _stream())
+    return out
+
+
+_token_embed_chunk = None
+
+
+def token_embed_chunk() -> int:
+    """rows of one partial sum of mtmp_token_embed_bwd: an id's position list longer than this is summed in chunks of it"""
+    global _token_embed_chunk
+    if _token_embed_chunk is None:
+        _token_embed_chunk = int(_lib.lib().mtmp_token_embed_bwd_chunk())
+    return _token_embed_chunk
+
+
+def token_embed_fwd(ids, table, dtype):
+    """``table[ids]`` in ``dtype``: ids int32 contiguous (any shape), table ``[V, 256]`` float32 | bfloat16 -> ``ids.shape + (256,)``.
+    float32 -> bfloat16 rounds as ``.to(torch.bfloat16)``; an id outside ``[0, V)`` gives a zero row."""
+    _gpu(ids, table)
+    V, D = table.shape
+    out = torch.empty(tuple(ids.shape) + (D,), dtype=dtype, device=ids.device)
+    with kernel_marks("token_embed_fwd", ids.numel()):
+        call("mtmp_token_embed_fwd", _p(ids), ids.numel(), _p(table), _dt(table), _p(out), _dt(out), V, D, _stream())
+    return out
+
+
+def token_embed_bwd(ids, dy, dw):
+    """``dw[v] = sum of dy[t] over ids[t] == v`` for the rows v that have a token, OVERWRITTEN in float32 ``dw [V, 256]`` (a
+    contiguous tensor or view); no other row of dw is touched.  No float atomics: equal inputs give equal bits."""
+    _gpu(ids, dy, dw)
+    V, D = dw.shape
+    T = ids.numel()
+    ws = torch.empty(_lib.lib().mtmp_token_embed_bwd_workspace(T, V), dtype=torch.uint8, device=ids.device)
+    with kernel_marks("token_embed_bwd", T):
+        call("mtmp_token_embed_bwd", _p(ids), T, _p(dy), _dt(dy), _p(dw), _p(ws), V, D, _stream())
+    return dw
+
+
+class TokenEmbedFn(torch.autograd.Function):
+    """``nn.Embedding(30000, 256)`` on the token ids of ``--berttype bert`` (tri_mbt_vsltcls.py:202, tri_mbt_v2.py:205):
+    ``apply(ids, weight, dtype)`` = ``F.embedding(ids, weight).to(dtype)``, bit for bit.  ids: any integer type or the loader's
+    float32 (anything but contiguous int32 is converted with one torch op).  Forward mtmp_token_embed_fwd on the optimizer's bf16
+    shadow of the table when there is a current one, else on the float32 table itself (the kernel rounds the rows it reads: no
+    cast of 30000 rows).  Backward mtmp_token_embed_bwd: the rows that have a token are written into the table's slice of the
+    flat gradient buffer (zeroed by FlatParams.zero_grad) -- torch's embedding_dense_backward builds a dense [30000, 256]
+    gradient from zero and AccumulateGrad adds it, ~90 MB of traffic for at most B * L touched rows."""
+
+    @staticmethod
+    def forward(ctx, ids, weight, dtype):
+        _gpu(ids, weight)
+        if ids.dtype != torch.int32 or not ids.is_contiguous():
+            ids = torch.empty(ids.shape, dtype=torch.int32, device=ids.device).copy_(ids)      # type and layout in one launch
+        from .optim import compute_view             # optim.compute_weight's view; without one, the float32 table (no cast launch)
+        table = compute_view(weight, dtype)
+        if table is None:
+            table = weight.detach()
+        ctx.save_for_backward(ids)
+        ctx.wshape, ctx.prm = weight.shape, [weight]
+        return token_embed_fwd(ids, _c(table), dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.needs_input_grad[1]:                # a frozen table: nothing is claimed, nothing is written
+            return None, None, None
+        (ids,) = ctx.saved_tensors
+        dy2 = _c(dy.reshape(-1, dy.shape[-1]))
+        if dy2.dtype not in (torch.float32, torch.bfloat16):
+            dy2 = dy2.float()
+        sk = _sink_dsts(ctx.prm) if tuning.FUSED_INPUT_TAIL else None
+        if sk is not None:            # touched rows only, into the zeroed slice of the flat gradient
+            token_embed_bwd(ids, dy2, sk[2][0].view(ctx.wshape))
+            sk[0].mark_ready(sk[1])
+            return None, None, None
+        return None, token_embed_bwd(ids, dy2, torch.zeros(ctx.wshape, dtype=torch.float32, device=dy.device)), None
+
+
 # ---- packed token streams (the ragged vital-sign stream without its pad rows) ------------------------------------------
 # A stream is PACKED when its samples' valid rows (bottleneck prefix + CLS + events = kv_len[b]) sit back to back in the
 # [B * N_max, 256] buffers instead of N_max rows apart: `pack` = row_starts(kv_len, N_max), int32[2 B + 1] on the device --

@@ -137,15 +137,22 @@ class FlatParams:
         return shadow[lo:end]
 
 
-def compute_weight(p: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """``p`` in the compute dtype: a view of the flat master / shadow buffer when there is a current one,
-    otherwise a cast."""
+def compute_view(p: torch.Tensor, dtype: torch.dtype):
+    """``p`` in the compute dtype WITHOUT a launch: a view of the flat master / shadow buffer when there is a current one,
+    else None (``compute_weight`` then casts; ops.TokenEmbedFn reads the float32 table itself instead of casting 30000 rows)."""
     flat = getattr(p, "_mtmp_flat", None)
-    if flat is not None:
+    if flat is not None and id(p) in flat.index_of:
         v = flat.span([flat.index_of[id(p)]], dtype)
         if v is not None:
             return v.view(p.shape)
-    return p.detach().to(dtype)
+    return None
+
+
+def compute_weight(p: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """``p`` in the compute dtype: a view of the flat master / shadow buffer when there is a current one,
+    otherwise a cast."""
+    v = compute_view(p, dtype)
+    return v if v is not None else p.detach().to(dtype)
 
 
 class FusedAdamW(torch.optim.Optimizer):

@@ -161,6 +161,17 @@ def make_report_store(seed: int, n_reports: int = 256, width: int = 768, max_tok
                                      for i, n in enumerate(lens.tolist())}, width, max_tokens)
 
 
+def make_token_report_store(seed: int, n_reports: int = 256, vocab: int = 30000, max_length: int = 128):
+    """builder/data/report_store.TokenReportStore of seeded stand-ins for the reference's ``txtDict`` (on the host; ``.to(device)``
+    uploads it): report ``i`` is keyed ``(i, 0)``, lengths uniform on 0 .. 160 -- an empty report, the short branch of
+    ``clinical_note_transform`` and the trimmed one (more than ``max_length - 3`` ids) all occur --, ids uniform on ``[0, vocab)``."""
+    from .builder.data.report_store import TokenReportStore
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.randint(0, 161, (n_reports,), generator=g)
+    return TokenReportStore.from_mapping({(i, 0): torch.randint(0, vocab, (int(n),), generator=g).tolist()
+                                          for i, n in enumerate(lens.tolist())}, vocab, max_length)
+
+
 RAW_CXR_SIZES = ((256, 311), (311, 256), (256, 256), (300, 256))     # h x w of the stand-ins (MIMIC-CXR-JPG resized to ~256)
 
 

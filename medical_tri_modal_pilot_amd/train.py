@@ -20,6 +20,9 @@ build-only flags wired in:
     --report-store 1  the report embeddings come from a synthetic device-resident embedding store (synthetic.make_report_store):
                       the loader hands over one report index per sample, builder/data/report_store.py plans them,
                       ops.report_tokens gathers in front of the step, in the model's compute type
+    --report-store 2  with --berttype bert: the reports are token ids from a synthetic device-resident id store
+                      (synthetic.make_token_report_store: 0 to 160 ids a report, so both trim branches occur);
+                      ops.report_token_ids writes the int32 [B, 128] batch, ops.TokenEmbedFn looks the ids up
 
     python -m medical_tri_modal_pilot_amd.train --input-types vslt_img_txt --model tri_mbt_vsltcls \\
         --modality-inclusion train-missing_test-missing --lr-init 1e-5 --batch-size 64 --epochs 1 \\
@@ -131,9 +134,10 @@ def main(argv=None):
     parser.add_argument("--tie-store", type=int, default=0, choices=[0, 1],
                         help="1: the vital-sign windows come from a synthetic device-resident event store "
                              "(builder/data/tie_store.py); the loader hands over (patient, hour, length) triples")
-    parser.add_argument("--report-store", type=int, default=0, choices=[0, 1],
+    parser.add_argument("--report-store", type=int, default=0, choices=[0, 1, 2],
                         help="1: the report embeddings come from a synthetic device-resident embedding store "
-                             "(builder/data/report_store.py); the loader hands over one report index per sample")
+                             "(builder/data/report_store.py); the loader hands over one report index per sample; "
+                             "2: the same for the token ids of --berttype bert (TokenReportStore)")
     args = parser.parse_args(argv)
     args.dir_root = os.getcwd()
     if int(args.synthetic) != 1:
@@ -143,6 +147,8 @@ def main(argv=None):
     rank, local, world = (int(os.environ.get(k, d)) for k, d in (("RANK", "0"), ("LOCAL_RANK", "0"), ("WORLD_SIZE", "1")))
     if not torch.cuda.is_available():
         raise SystemExit("training runs on an MI355X only (no CPU fallback)")
+    if int(args.report_store) == 2 and args.berttype != "bert":
+        raise SystemExit("--report-store 2 is the token-id store: it needs --berttype bert (--report-store 1 holds BioBERT embeddings)")
     if int(args.raw_images) == 2:
         from .synthetic import jpeg_encode
         jpeg_encode(None)                              # fails here, by name, where PIL is not installed
@@ -172,6 +178,12 @@ def main(argv=None):
         if rank == 0:
             print(f"report store: {report_store.n_reports} reports, {report_store.n_tokens} tokens, {report_store.nbytes} bytes "
                   f"({report_store.dtype}) on {device}", flush=True)
+    if int(args.report_store) == 2:
+        from .synthetic import make_token_report_store
+        report_store = make_token_report_store(5011, max_length=int(args.bert_token_max_length)).to(device)
+        if rank == 0:
+            print(f"token store: {report_store.n_reports} reports, {report_store.n_tokens} ids, {report_store.nbytes} bytes "
+                  f"on {device}", flush=True)
     logger = _Logger()
     model.train()                                                                                    # 2_train.py:128
     iteration = 0

@@ -38,3 +38,7 @@ INPUT_NODE_ORDER = "long_last"
 # the flat gradient (the event and time embeddings' backward as one launch, the bottleneck tokens' gradient through ops.BottSink)
 # instead of two reduction levels, a multi-tensor copy and the accumulation launches of the shared parameters per node.
 FUSED_INPUT_TAIL = True
+# tri_mbt_vsltcls (--berttype bert): the nn.Embedding(30000, 256) lookup and its gradient as ops.TokenEmbedFn (csrc/token_embed.hip:
+# touched rows written into the flat gradient) instead of F.embedding + cast and embedding_dense_backward + AccumulateGrad (a dense
+# [30000, 256] gradient built from zero and added: ~90 MB of traffic).  Forward bits are equal; profiles/token_embed.txt.
+HIP_TOKEN_EMBED = True
