@@ -630,6 +630,49 @@ int mtmp_jpeg_entropy(const uint8_t* streams, const int32_t* desc, const int32_t
 int mtmp_jpeg_idct(const int16_t* coef, const int32_t* desc, const int32_t* tables, const int32_t* status, uint8_t* pixels, int n,
                    int max_blocks, void* stream);
 
+/* ---- Chest X-rays from a device-resident JPEG store (additive; ABI stays 6): builder/data/cxr_store.py parses every file once
+ * and keeps its de-stuffed bytes on the device; the entry state of every subsequence of every restart segment -- which
+ * mtmp_jpeg_entropy finds again for every batch, in rounds -- is a property of the file and is found once, into the SYNC TABLE.
+ * A batch is then decoded by one pass over a flat grid of subsequences.
+ *   streams: uint8 device buffer, the de-stuffed segments of ALL images back to back (may exceed 2^31 bytes).
+ *   An image row is a `desc` row of mtmp_jpeg_entropy (int32 [16]) with two more words: 13 the image's OWN subsequence length in
+ *            bits (a multiple of 32 with at most 1024 subsequences in its largest segment), 14 its number of sync rows (the sum
+ *            over its segments of max(ceil(8 bytes / word 13), 1)).  Word 1 is its first row in the store's `segs`.  Its two
+ *            64-bit offsets live beside it in
+ *   wide:    int64 [n][2]: 0 the byte offset of the image's first segment in `streams` (word 0 of the row is then unused),
+ *            1 its first row in `sync`.  Everything inside one image is 32-bit.
+ *   segs:    (store form) int32 [n_segs][4] device, one row per restart segment, all relative to its image: 0 byte offset behind
+ *            the image's first byte, 1 bytes (<= 2^22), 2 its first block within the image, 3 its first sync row behind the
+ *            image's first.
+ *   sync:    int32 [n_sync][4] device, 16-byte aligned, one row per subsequence, segments and images in order: 0 the entry state
+ *            (bit position within the segment << 6) | coefficient index (0: a DC code is next) of the first symbol that starts
+ *            at or behind the subsequence's nominal start (0 for the first subsequence of a segment), 1 the block that symbol
+ *            belongs to, relative to the segment's first block, 2 the DC predictor at that point, 3 the segment, relative to the
+ *            image's first -- a decoder lane finds its segment row through it without a search.
+ * mtmp_jpeg_sync_points: the build pass over one CHUNK of images (the store is built chunk by chunk so that every offset of a
+ *   launch is 32-bit): the launch shape and the rounds of mtmp_jpeg_entropy (the same kernel body), each lane writing its sync row
+ *   in place of coefficients.  streams / sync / status point at the chunk's first byte / sync row / image; desc: int32 [images of
+ *   the chunk][16] with word 0 the image's byte offset and word 1 its first segment row WITHIN THE CHUNK; segs: int32
+ *   [n_seg][4] in the form of mtmp_jpeg_entropy (offset within the chunk, bytes, image within the chunk, first block); sync0:
+ *   int32 [n_seg], every segment's first sync row within the chunk; max_lanes: the most subsequences of a segment (<= 1024);
+ *   n_sync: sync rows of the chunk (a row at or behind it is not written); status as for mtmp_jpeg_entropy, ZEROED by the caller.
+ * mtmp_jpeg_store_entropy: the per-batch decoder.  desc: int32 [n][16], the store's rows of the batch's images with word 7
+ *   (pixel offset) and word 11 (first block in `coef`) filled in -- also what mtmp_jpeg_idct reads next; wide: int64 [n][2],
+ *   8-byte aligned, their rows of the store's `wide`; prefix: int32 [n + 1], exclusive prefix sum of word 14 over the batch;
+ *   total_lanes = prefix[n] (the host's copy).  256 lanes per workgroup, lane g decodes subsequence g - prefix[b] of batch image
+ *   b (found by bisection of `prefix`): ONE pass from its sync row's entry state up to the first symbol at or behind its
+ *   subsequence's end, into coef (ZEROED by the caller) at the image's blocks.  No rounds, no scan, no status: the build refused
+ *   every image that does not decode.  stream_bytes / n_segs / n_sync / table_words: the sizes of streams / segs / sync /
+ *   tables; a lane whose rows point outside any of them writes nothing, and nothing outside the image's blocks of coef is
+ *   written. */
+int mtmp_jpeg_sync_points(const uint8_t* streams, const int32_t* desc, const int32_t* segs, const int32_t* tables,
+                          const int32_t* sync0, int32_t* sync, int32_t* status, int n_seg, int max_lanes, long long n_sync,
+                          int stage_bytes, void* stream);
+int mtmp_jpeg_store_entropy(const uint8_t* streams, const int32_t* segs, const int32_t* sync, const int32_t* tables,
+                            const int32_t* desc, const long long* wide, const int32_t* prefix, int16_t* coef, int n,
+                            int total_lanes, long long stream_bytes, long long n_segs, long long n_sync, long long table_words,
+                            void* stream);
+
 /* ---- TIE event windows from a device-resident event store (additive; ABI stays 6): the reference builds every window on the
  * host (builder/data/dataset_new.py:1969-2030, restated by builder/data/tie_dataset.py tie_window).  Here the data set is stored
  * once (builder/data/tie_store.py: CSR over patients -> hours -> events) and a window is a row of `desc`; ONE launch writes the

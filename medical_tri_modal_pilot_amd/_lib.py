@@ -118,6 +118,8 @@ SIGNATURES = {
     "mtmp_cxr_crop_resize": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_longlong, c_int, c_void_p]),
     "mtmp_jpeg_entropy": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_void_p]),
     "mtmp_jpeg_idct": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
+    "mtmp_jpeg_sync_points": (c_int, [c_void_p] * 7 + [c_int, c_int, c_longlong, c_int, c_void_p]),
+    "mtmp_jpeg_store_entropy": (c_int, [c_void_p] * 8 + [c_int, c_int] + [c_longlong] * 4 + [c_void_p]),
     "mtmp_tie_window_gather": (c_int, [c_void_p] * 6 + [c_longlong, c_longlong] + [c_void_p] * 3 + [c_int] * 3 +
                                [c_longlong, c_longlong] + [c_int] * 3 + [c_void_p]),
     "mtmp_report_gather": (c_int, [c_void_p, c_int, c_longlong, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),

@@ -6,6 +6,7 @@
 from .tie_dataset import (PackedTie, PackedTieBatch, SampleTieDataset, collate_packed, tie_window)  # noqa: F401
 from .tie_store import StoreWindowDataset, TieEventStore, TieWindowBatch, collate_windows  # noqa: F401
 from .report_store import ReportBatch, ReportStore, TokenReportBatch, TokenReportStore, report_wanted  # noqa: F401
+from .cxr_store import CxrImage, CxrStore, CxrStoreBatch, image_wanted  # noqa: F401
 from .jpeg import JpegInfo, JpegPlan, parse_jpeg  # noqa: F401
 from .cxr_transform import (CxrRandomTransform, CxrTransform, RawCxrBatch, collate_raw_cxr, draw_affine, draw_randaug,  # noqa: F401
                             draw_resized_crop, transform_from_args)

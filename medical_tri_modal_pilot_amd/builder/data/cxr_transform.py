@@ -13,7 +13,8 @@ Reference behaviour restated here (file:line in the reference's builder/data/dat
 What is NOT restated: ``resize_larger`` (the reference names a function for it that it never defines) raises
 NotImplementedError.  ``transform_from_args`` picks the class for a set of flags.  An image may be handed over as the bytes
 of its JPEG file instead of the decoded array: builder/data/jpeg.py plans its decoding (csrc/jpeg.hip), which then runs in front
-of the chain on the device.
+of the chain on the device.  Or as ``store.image(i)``, a handle into a device-resident store of such files
+(builder/data/cxr_store.py): nothing is parsed and no byte of it crosses the link.
 
 All of the chain is integer arithmetic in PIL (ImageOps.equalize, the 22-bit fixed-point antialiased bilinear resize with a
 uint8 rounding between its two passes, the 16.16 fixed-point nearest-neighbour affine map), so the kernels reproduce it bit
@@ -58,6 +59,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .cxr_store import CxrImage
 from .jpeg import is_jpeg_source, parse_jpeg, plan_jpegs
 
 PRECISION_BITS = 22                 # PIL's 8-bit resampling: 32 - 8 - 2
@@ -388,11 +390,16 @@ class RawCxrBatch:
     Images handed over as JPEG file bytes add
     jpeg      builder/data/jpeg.JpegPlan | None   their streams, descriptor rows, segment rows and decode tables; their regions
               of ``pixels`` are left for ``ops.jpeg_decode`` to fill (``ops.cxr_prepare`` calls it)
+    Images handed over as handles of a ``CxrStore`` add
+    stored    builder/data/cxr_store.CxrStoreBatch | None   their store, indices, descriptor rows and lane prefix; filled by
+              ``ops.jpeg_decode`` as well.  When EVERY present image is stored, ``pixels`` is None on the host and ``to(device)``
+              allocates its ``pixel_bytes`` bytes there: no pixel byte crosses the link.
     """
 
     def __init__(self, pixels, desc, tables, slot_map, img_time, image_size, batch, n_images, scratch_bytes, max_pixels,
-                 max_rh, max_rw, lds_rows, params, aug=None, stages=0, jpeg=None):
-        self.aug, self.stages, self.jpeg = aug, int(stages), jpeg
+                 max_rh, max_rw, lds_rows, params, aug=None, stages=0, jpeg=None, stored=None, pixel_bytes=None):
+        self.aug, self.stages, self.jpeg, self.stored = aug, int(stages), jpeg, stored
+        self.pixel_bytes = int(pixels.numel() if pixel_bytes is None else pixel_bytes)
         self.pixels, self.desc, self.tables, self.slot_map, self.img_time = pixels, desc, tables, slot_map, img_time
         self.image_size, self.batch, self.n_images = int(image_size), int(batch), int(n_images)
         self.scratch_bytes, self.max_pixels, self.max_rh, self.max_rw = int(scratch_bytes), int(max_pixels), int(max_rh), int(max_rw)
@@ -412,10 +419,12 @@ class RawCxrBatch:
 
     def to(self, device, non_blocking: bool = False) -> "RawCxrBatch":
         mv = lambda t: t.to(device, non_blocking=non_blocking)
-        return RawCxrBatch(mv(self.pixels), mv(self.desc), mv(self.tables), mv(self.slot_map), self.img_time, self.image_size,
+        pixels = mv(self.pixels) if self.pixels is not None else torch.empty(self.pixel_bytes, dtype=torch.uint8, device=device)
+        return RawCxrBatch(pixels, mv(self.desc), mv(self.tables), mv(self.slot_map), self.img_time, self.image_size,
                            self.batch, self.n_images, self.scratch_bytes, self.max_pixels, self.max_rh, self.max_rw,
                            self.lds_rows, self.params, None if self.aug is None else mv(self.aug), self.stages,
-                           None if self.jpeg is None else self.jpeg.to(device, non_blocking=non_blocking))
+                           None if self.jpeg is None else self.jpeg.to(device, non_blocking=non_blocking),
+                           None if self.stored is None else self.stored.to(device, non_blocking=non_blocking), self.pixel_bytes)
 
 
 def _tile_rows_needed(vb: np.ndarray) -> int:
@@ -459,6 +468,8 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
     (builder/data/jpeg.parse_jpeg says what is accepted; anything else raises -- the loader then decodes that file itself and
     passes the array).  The file's header gives h and w, so everything below is planned as for an array; the file's region of
     ``pixels`` is left zero and ``RawCxrBatch.jpeg`` holds what the device needs to fill it.
+    Or it is ``store.image(i)`` of a ``CxrStore``: h and w come from the handle, nothing is parsed, ``RawCxrBatch.stored`` holds
+    the plan; all handles of a batch must come from one store.  The three kinds may mix in one batch.
     A ``CxrRandomTransform`` draws per image, in the reference's order, the RandAugment ops (``randaug``) and then the crop
     box; aug_params: per image two ``(op, magnitude)`` pairs, crop_params: per image ``(i, j, ch, cw)``, instead (tests)."""
     rnd = isinstance(transform, CxrRandomTransform)
@@ -473,6 +484,7 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
     img_time = np.full((B, per), 10.0 if K else -1.0, np.float32)
     src_off = scratch_off = max_pixels = max_rh = max_rw = lds_rows = 0
     jpg_infos, jpg_dst, jpg_rows, jpg_bytes = [], [], [], 0
+    store, st_idx, st_dst, st_rows = None, [], [], []
 
     def table(in_size, out_size):
         nonlocal tab_words
@@ -488,7 +500,16 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
         if len(images) > per or len(images) != len(times):
             raise ValueError(f"sample {b}: {len(images)} images, {len(times)} times, {per} slots")
         for j, (im, t) in enumerate(zip(images, times)):
-            if is_jpeg_source(im):
+            if isinstance(im, CxrImage):
+                if store is not None and im.store is not store:
+                    raise ValueError(f"sample {b} image {j}: the stored images of a batch must come from one CxrStore")
+                store = im.store
+                st_idx.append(im.index)
+                st_dst.append(src_off)
+                st_rows.append(len(rows))
+                h, w = im.h, im.w
+                im = None                                          # ops.jpeg_decode writes these bytes on the device
+            elif is_jpeg_source(im):
                 try:
                     info = parse_jpeg(im)
                 except (ValueError, NotImplementedError) as e:
@@ -527,7 +548,7 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
                 img_time[b, j] = t
                 rows.append(d)
                 aug_rows.append(a)
-                chunks.append(im.ravel())
+                chunks.append((h * w) if im is None else im.ravel())
                 src_off += h * w
                 scratch_off += (h * w + 15) // 16 * 16          # the stages store four pixels at a time
                 max_pixels, max_rh, max_rw = max(max_pixels, h * w), S, S
@@ -555,7 +576,7 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
             slot_map[b * per + j] = len(rows)
             img_time[b, j] = t
             rows.append(d)
-            chunks.append(im.ravel())
+            chunks.append((h * w) if im is None else im.ravel())
             src_off += h * w
             scratch_off += rh * rw
             max_pixels, max_rh, max_rw = max(max_pixels, h * w), max(max_rh, rh), max(max_rw, rw)
@@ -575,10 +596,15 @@ def collate_raw_cxr(samples, transform, n_images: int, generator: Optional[torch
         t = torch.empty(a.shape, dtype=dtype, pin_memory=pin)
         t.copy_(torch.from_numpy(a))
         return t
-    pixels = host(np.concatenate(chunks) if chunks else np.zeros(1, np.uint8), torch.uint8)
+    if st_rows and len(st_rows) == len(rows):             # every present image is stored: the pixel buffer exists on the device only
+        pixels = None
+    else:
+        chunks = [np.zeros(c, np.uint8) if isinstance(c, int) else c for c in chunks]
+        pixels = host(np.concatenate(chunks) if chunks else np.zeros(1, np.uint8), torch.uint8)
     tables = host(np.concatenate(tab_parts).astype(np.int32) if tab_parts else np.zeros(1, np.int32), torch.int32)
     t_img = torch.from_numpy(img_time if K else img_time[:, 0].copy())
     return RawCxrBatch(pixels, host(desc.astype(np.int32), torch.int32), tables, host(slot_map, torch.int32), t_img, S, B, K,
                        scratch_off, max_pixels, max_rh, max_rw, lds_rows, params,
                        None if aug is None else host(aug.astype(np.int32), torch.int32), stage_mask,
-                       plan_jpegs(jpg_infos, jpg_dst, jpg_rows, jpg_bytes, pin) if jpg_infos else None)
+                       plan_jpegs(jpg_infos, jpg_dst, jpg_rows, jpg_bytes, pin) if jpg_infos else None,
+                       store.batch(st_idx, st_dst, st_rows, pin) if st_rows else None, max(src_off, 1))

@@ -16,6 +16,11 @@
 //   that is not in the table, or a symbol that would end behind the segment, costs one bit), the slow path of the code lookup
 //   walks lengths 11..16, the rounds stop at the lane count.  Nothing waits for another workgroup.  Bits behind the segment's end
 //   read as ones: no code is all ones, so the fill bits and the end of a truncated stream are not symbols.
+// mtmp_jpeg_sync_points    the same kernel under a template flag, once per file when an image store is built
+//   (builder/data/cxr_store.py): what the rounds and the scan find -- every lane's entry state, first block and DC predictor --
+//   is a property of the file, so it is written to a sync table in place of the write pass.
+// mtmp_jpeg_store_entropy  the per-batch decoder of such a store: a flat grid over the batch's subsequences, each lane ONE span()
+//   call from its sync row.  No rounds, no scan, no per-segment workgroup.
 // mtmp_jpeg_idct      eight lanes per block: a column per lane, the transpose through LDS, a row per lane.  Dequantisation and
 //   both passes of libjpeg's jpeg_idct_islow (jidctint.c: CONST_BITS 13, PASS1_BITS 2, its twelve FIX constants), which PIL's
 //   libjpeg-turbo computes bit-identically in its SIMD forms; the library's zero-AC shortcuts equal the general path, so there
@@ -25,8 +30,10 @@
 namespace {
 
 constexpr int JPG_WORDS = 16, SEG_WORDS = 4;
-enum { J_STREAM = 0, J_SEG0, J_NSEG, J_H, J_W, J_BPR, J_NBLK, J_DST, J_QT, J_DC, J_AC, J_COEF, J_RI };
+enum { J_STREAM = 0, J_SEG0, J_NSEG, J_H, J_W, J_BPR, J_NBLK, J_DST, J_QT, J_DC, J_AC, J_COEF, J_RI, J_SUBSEQ, J_NSYNC };
 enum { S_OFF = 0, S_BYTES, S_IMG, S_BLOCK0 };
+enum { T_OFF = 0, T_BYTES, T_BLOCK0, T_SYNC0 };    // a segment row of the image store: everything relative to its image
+enum { W_STREAM = 0, W_SYNC0 };                    // the two 64-bit words of a stored image
 constexpr int LOOK_BITS = 10, LOOK = 1 << LOOK_BITS;
 constexpr int HUFF_WORDS = LOOK + 18 + 18 + 256;   // look | maxcode[18] | valoff[18] | huffval[256]  (builder/data/jpeg.py)
 constexpr int MAX_SUBSEQ = 1024;                   // lanes of a workgroup
@@ -52,10 +59,11 @@ MTMP_DEV unsigned window(const uint8_t* seg, int nbytes, int p) {
 }
 
 // From state (p, k) up to the first symbol that starts at or behind `end`.  WRITE: the coefficients of blocks blk.. < nb go to
-// coef (the segment's first block), DC = pred + the running sum of differences.
+// coef (the segment's first block), DC = pred + the running sum of differences.  zz: the ZIGZAG table the write pass reads (the
+// constant itself, or a workgroup's LDS copy of it: the read sits in front of every coefficient's store).
 template <bool WRITE>
 MTMP_DEV SpanOut span(const uint8_t* seg, int nbytes, int nbits, const int* dc, const int* ac, int p, int k, int end,
-                      int16_t* coef, int blk, int pred, int nb) {
+                      int16_t* coef, int blk, int pred, int nb, const uint8_t* zz = ZIGZAG) {
     int nblk = 0, dcs = 0;
     while (p < end) {                              // p grows by at least one per turn
         const unsigned win = window(seg, nbytes, p);
@@ -95,7 +103,7 @@ MTMP_DEV SpanOut span(const uint8_t* seg, int nbytes, int nbits, const int* dc, 
                 k = r == 15 ? k + 16 : 64;         // ZRL | EOB
             } else {
                 k += r;
-                if (WRITE && k < 64 && blk < nb) coef[(long long)blk * 64 + ZIGZAG[k]] = (int16_t)v;
+                if (WRITE && k < 64 && blk < nb) coef[(long long)blk * 64 + zz[k]] = (int16_t)v;
                 k += 1;
             }
         }
@@ -108,11 +116,16 @@ MTMP_DEV SpanOut span(const uint8_t* seg, int nbytes, int nbits, const int* dc, 
     return SpanOut{p, k, nblk, dcs};
 }
 
+// SYNC: the build pass of the image store (mtmp_jpeg_sync_points).  The same rounds and the same scan; what a lane has found --
+// its entry state, its first block, its DC predictor -- goes to its row of the sync table in place of the write pass, and the
+// subsequence length is the image's own (J_SUBSEQ).  sync0[sid]: the segment's first row; rows >= n_sync are not written.
+template <bool SYNC>
 __global__ __launch_bounds__(MAX_SUBSEQ) void jpeg_entropy_kernel(const uint8_t* __restrict__ streams,
                                                                   const int* __restrict__ desc, const int* __restrict__ segs,
                                                                   const int* __restrict__ tables, int16_t* __restrict__ coef,
                                                                   int* __restrict__ status, int* __restrict__ rounds_out,
-                                                                  int subseq_bits, int stage_bytes) {
+                                                                  int subseq_bits, int stage_bytes, const int* __restrict__ sync0,
+                                                                  int4* __restrict__ sync, long long n_sync) {
     __shared__ int tab[2][HUFF_WORDS];             // 10.3 KB
     __shared__ unsigned exit_s[MAX_SUBSEQ];        // 4 KB
     __shared__ int nblk_s[MAX_SUBSEQ], dcs_s[MAX_SUBSEQ];        // 8 KB
@@ -124,7 +137,7 @@ __global__ __launch_bounds__(MAX_SUBSEQ) void jpeg_entropy_kernel(const uint8_t*
     const int nbytes = min(max(sg[S_BYTES], 0), MAX_SEGMENT_BYTES), nbits = nbytes * 8;
     const int ri = d[J_RI], left = d[J_NBLK] - b0;
     const int nb = max(ri > 0 ? min(ri, left) : left, 0);
-    const int S = subseq_bits > 0 ? subseq_bits : max(nbits, 1);
+    const int S = SYNC ? max(d[J_SUBSEQ], 1) : subseq_bits > 0 ? subseq_bits : max(nbits, 1);
     const int nsub = (int)max(((long long)nbits + S - 1) / S, 1ll);
     if (nsub > nthr) {                             // uniform: the host cut the segments for this launch's lane count
         if (tid == 0) atomicOr(&status[img], STATUS_LANES);
@@ -176,8 +189,13 @@ __global__ __launch_bounds__(MAX_SUBSEQ) void jpeg_entropy_kernel(const uint8_t*
     }
     if (active) {
         const int blk0 = tid ? nblk_s[tid - 1] : 0, pred = tid ? dcs_s[tid - 1] : 0;
-        span<true>(seg, nbytes, nbits, tab[0], tab[1], (int)(used >> 6), (int)(used & 63u), end,
-                   coef + ((long long)d[J_COEF] + b0) * 64, blk0, pred, nb);
+        if (SYNC) {
+            const long long row = (long long)sync0[sid] + tid;
+            if (row >= 0 && row < n_sync) sync[row] = int4{(int)used, blk0, pred, sid - d[J_SEG0]};
+        } else {
+            span<true>(seg, nbytes, nbits, tab[0], tab[1], (int)(used >> 6), (int)(used & 63u), end,
+                       coef + ((long long)d[J_COEF] + b0) * 64, blk0, pred, nb);
+        }
     }
     if (tid == 0) {
         int code = nblk_s[nsub - 1] < nb ? STATUS_SHORT : 0;
@@ -185,6 +203,100 @@ __global__ __launch_bounds__(MAX_SUBSEQ) void jpeg_entropy_kernel(const uint8_t*
         if (code) atomicOr(&status[img], code);
         if (rounds_out) rounds_out[sid] = rounds;
     }
+}
+
+constexpr int STORE_LANES = 256;
+constexpr int STORE_STAGE_BITS = 1024;                           // a subsequence of up to this many bits is decoded out of LDS
+constexpr int STORE_STAGE_WORDS = STORE_STAGE_BITS / 32 + 1;     // + 4 bytes: the last symbol's window; 33 words: no bank conflicts
+#ifndef MTMP_JPEG_STORE_TABLES_LDS
+#define MTMP_JPEG_STORE_TABLES_LDS 1                             // 0: every lane reads its tables from global memory (the A/B of
+#endif                                                           // profiles/cxr_store.txt; a diagnostic build only)
+
+// The per-batch decoder of the image store: a flat grid over the subsequences of the batch's images, one lane each, ONE span()
+// call from the stored entry state.  prefix[b] = lanes of the batch's images < b; a lane finds its image by bisection (at most
+// 32 turns), its segment through its sync row.  The decode tables of the workgroup's first image are copied into LDS; a lane
+// whose image names another pair reads its own from global memory (a wave-uniform choice wherever a wave holds one image).
+// The 64 bytes of ZIGZAG are copied with them.  A lane whose subsequence has at most STORE_STAGE_BITS bits (the default length) first copies its bytes -- 33 independent
+// loads -- into LDS words of its own and decodes from there with all positions rebased to its subsequence: span() then waits
+// for LDS, not for global memory, once per symbol.  The words are the lane's alone, so no barrier follows the table load.
+// Every index that comes out of a row is checked against the size of what it indexes before it is used.
+__global__ __launch_bounds__(STORE_LANES) void jpeg_store_entropy_kernel(
+    const uint8_t* __restrict__ streams, const int* __restrict__ segs, const int4* __restrict__ sync,
+    const int* __restrict__ tables, const int* __restrict__ desc, const long long* __restrict__ wide,
+    const int* __restrict__ prefix, int16_t* __restrict__ coef, int n, int total, long long stream_bytes, long long n_segs,
+    long long n_sync, long long table_words) {
+    __shared__ int tab[2][HUFF_WORDS];             // 10.3 KB
+    __shared__ unsigned stage[STORE_LANES * STORE_STAGE_WORDS];  // 33 KB
+    __shared__ uint8_t zz[64];
+    const int tid = threadIdx.x, g = blockIdx.x * STORE_LANES + tid;
+    auto image_of = [&](int lane) {                // the last b with prefix[b] <= lane
+        int lo = 0, hi = n;
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (prefix[mid] <= lane) lo = mid; else hi = mid;
+        }
+        return lo;
+    };
+    const int* d0 = desc + (long long)image_of(min(blockIdx.x * STORE_LANES, total - 1)) * JPG_WORDS;
+    const int dc0 = d0[J_DC], ac0 = d0[J_AC];
+    const bool ok0 = MTMP_JPEG_STORE_TABLES_LDS && dc0 >= 0 && ac0 >= 0 && dc0 + HUFF_WORDS <= table_words &&
+                     ac0 + HUFF_WORDS <= table_words;
+    if (tid < 64) zz[tid] = ZIGZAG[tid];
+    if (ok0)
+        for (int i = tid; i < HUFF_WORDS; i += STORE_LANES) {
+            tab[0][i] = tables[dc0 + i];
+            tab[1][i] = tables[ac0 + i];
+        }
+    __syncthreads();
+    if (g >= total) return;
+    const int b = image_of(g), l = g - prefix[b];
+    const int* d = desc + (long long)b * JPG_WORDS;
+    const long long row = wide[2 * b + W_SYNC0] + l;
+    if (l < 0 || l >= d[J_NSYNC] || row < 0 || row >= n_sync) return;
+    const int4 sy = sync[row];                     // entry state, first block, DC predictor, segment
+    const long long srow = (long long)d[J_SEG0] + sy.w;
+    if (sy.w < 0 || sy.w >= d[J_NSEG] || srow < 0 || srow >= n_segs || sy.y < 0) return;
+    const int* sg = segs + srow * SEG_WORDS;
+    const int nbytes = min(max(sg[T_BYTES], 0), MAX_SEGMENT_BYTES), nbits = nbytes * 8;
+    const long long soff = wide[2 * b + W_STREAM] + sg[T_OFF];
+    const int j = l - sg[T_SYNC0], S = d[J_SUBSEQ], b0 = sg[T_BLOCK0];
+    const int dc = d[J_DC], ac = d[J_AC];
+    if (soff < 0 || soff + nbytes > stream_bytes || j < 0 || S < 1 || b0 < 0 || dc < 0 || ac < 0 ||
+        dc + HUFF_WORDS > table_words || ac + HUFF_WORDS > table_words)
+        return;
+    const int ri = d[J_RI], left = d[J_NBLK] - b0;
+    const int nb = max(ri > 0 ? min(ri, left) : left, 0);
+    int end = (int)min(((long long)j + 1) * S, (long long)nbits);
+    const uint8_t* seg = streams + soff;
+    int16_t* out = coef + ((long long)d[J_COEF] + b0) * 64;
+    int p = (int)((unsigned)sy.x >> 6), nby = nbytes, nbi = nbits;
+    const int k = sy.x & 63;
+    const long long base = (long long)j * (S >> 3);               // the subsequence's first byte within the segment
+    if (S <= STORE_STAGE_BITS && (S & 31) == 0 && base <= nbytes && p >= base * 8) {
+        unsigned* mine = stage + tid * STORE_STAGE_WORDS;
+        const uint8_t* src = seg + base;
+        const int have = min(nbytes - (int)base, STORE_STAGE_WORDS * 4);
+#pragma unroll
+        for (int i = 0; i < STORE_STAGE_WORDS; ++i) {
+            unsigned v = 0;
+            if (4 * i + 4 <= have) {
+                __builtin_memcpy(&v, src + 4 * i, 4);              // the stream's alignment is arbitrary
+            } else {
+                for (int c = 0; c < 4; ++c)
+                    if (4 * i + c < have) v |= (unsigned)src[4 * i + c] << (8 * c);
+            }
+            mine[i] = v;
+        }
+        seg = reinterpret_cast<const uint8_t*>(mine);
+        p -= (int)base * 8;
+        end -= (int)base * 8;
+        nby -= (int)base;
+        nbi -= (int)base * 8;
+    }
+    if (ok0 && dc == dc0 && ac == ac0)
+        span<true>(seg, nby, nbi, tab[0], tab[1], p, k, end, out, sy.y, sy.z, nb, zz);
+    else
+        span<true>(seg, nby, nbi, tables + dc, tables + ac, p, k, end, out, sy.y, sy.z, nb, zz);
 }
 
 constexpr unsigned FIX_0_298631336 = 2446, FIX_0_390180644 = 3196, FIX_0_541196100 = 4433, FIX_0_765366865 = 6270,
@@ -298,9 +410,40 @@ extern "C" int mtmp_jpeg_entropy(const uint8_t* streams, const int32_t* desc, co
     MTMP_CHECK_ARG(lanes <= MAX_SUBSEQ, "mtmp_jpeg_entropy: a segment of %d bytes has %lld subsequences of %d bits (limit %d)",
                    max_seg_bytes, lanes, subseq_bits, MAX_SUBSEQ);
     const int threads = (int)((lanes < 1 ? 1 : lanes) + 63) / 64 * 64;
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(n_seg), dim3(threads), (size_t)stage_bytes, (hipStream_t)stream, streams, desc, segs,
-                       tables, coef, status, rounds, subseq_bits, stage_bytes);
+    hipLaunchKernelGGL(jpeg_entropy_kernel<false>, dim3(n_seg), dim3(threads), (size_t)stage_bytes, (hipStream_t)stream, streams, desc,
+                       segs, tables, coef, status, rounds, subseq_bits, stage_bytes, (const int*)nullptr, (int4*)nullptr, 0ll);
     MTMP_CHECK_LAUNCH("mtmp_jpeg_entropy");
+    return MTMP_OK;
+}
+
+extern "C" int mtmp_jpeg_sync_points(const uint8_t* streams, const int32_t* desc, const int32_t* segs, const int32_t* tables,
+                                     const int32_t* sync0, int32_t* sync, int32_t* status, int n_seg, int max_lanes,
+                                     long long n_sync, int stage_bytes, void* stream) {
+    MTMP_CHECK_ARG(streams && desc && segs && tables && sync0 && sync && status && n_seg > 0 && max_lanes > 0 &&
+                       max_lanes <= MAX_SUBSEQ && n_sync > 0 && stage_bytes >= 0 && stage_bytes <= MAX_STAGE_BYTES &&
+                       ((uintptr_t)sync & 15) == 0,
+                   "mtmp_jpeg_sync_points: bad argument (n_seg=%d max_lanes=%d n_sync=%lld stage_bytes=%d)", n_seg, max_lanes, n_sync,
+                   stage_bytes);
+    hipLaunchKernelGGL(jpeg_entropy_kernel<true>, dim3(n_seg), dim3((max_lanes + 63) / 64 * 64), (size_t)stage_bytes,
+                       (hipStream_t)stream, streams, desc, segs, tables, (int16_t*)nullptr, status, (int*)nullptr, 0, stage_bytes, sync0,
+                       (int4*)sync, n_sync);
+    MTMP_CHECK_LAUNCH("mtmp_jpeg_sync_points");
+    return MTMP_OK;
+}
+
+extern "C" int mtmp_jpeg_store_entropy(const uint8_t* streams, const int32_t* segs, const int32_t* sync, const int32_t* tables,
+                                       const int32_t* desc, const long long* wide, const int32_t* prefix, int16_t* coef, int n,
+                                       int total_lanes, long long stream_bytes, long long n_segs, long long n_sync,
+                                       long long table_words, void* stream) {
+    MTMP_CHECK_ARG(streams && segs && sync && tables && desc && wide && prefix && coef && n > 0 && total_lanes > 0 &&
+                       stream_bytes > 0 && n_segs > 0 && n_sync > 0 && table_words > 0 && ((uintptr_t)sync & 15) == 0 &&
+                       ((uintptr_t)wide & 7) == 0,
+                   "mtmp_jpeg_store_entropy: bad argument (n=%d total_lanes=%d stream_bytes=%lld n_segs=%lld n_sync=%lld)", n,
+                   total_lanes, stream_bytes, n_segs, n_sync);
+    hipLaunchKernelGGL(jpeg_store_entropy_kernel, dim3((total_lanes + STORE_LANES - 1) / STORE_LANES), dim3(STORE_LANES), 0,
+                       (hipStream_t)stream, streams, segs, (const int4*)sync, tables, desc, wide, prefix, coef, n, total_lanes,
+                       stream_bytes, n_segs, n_sync, table_words);
+    MTMP_CHECK_LAUNCH("mtmp_jpeg_store_entropy");
     return MTMP_OK;
 }
 

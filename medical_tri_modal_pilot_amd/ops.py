@@ -459,14 +459,51 @@ def _jpeg_decode_plan(plan, pixels, subseq_bits=None, rounds=None, stage_bytes=N
     return status
 
 
+def _store_decode(sb, pixels):
+    """Decode the images of a builder/data/cxr_store.CxrStoreBatch (device) into ``pixels``: the zero-fill of the coefficient
+    buffer and of the status words mtmp_jpeg_idct reads, mtmp_jpeg_store_entropy (one flat launch over the batch's subsequences,
+    from the store's sync table), mtmp_jpeg_idct.  Nothing is read back: the store's build checked every stream."""
+    store = sb.store
+    _gpu(sb.buf, pixels)
+    dev = pixels.device
+    if store.device != dev:
+        raise RuntimeError(f"cxr store: the image store is on {store.device}, not on {dev}: call store.to(device) once")
+    coef = torch.zeros(max(sb.total_blocks, 1) * 64, dtype=torch.int16, device=dev)
+    status = torch.zeros(sb.n, dtype=torch.int32, device=dev)
+    call("mtmp_jpeg_store_entropy", _p(store.d_streams), _p(store.d_segs), _p(store.d_sync), _p(store.d_tables), _p(sb.desc),
+         _p(sb.wide), _p(sb.prefix), _p(coef), sb.n, sb.lanes, store.d_streams.numel(), store.d_segs.shape[0],
+         store.d_sync.shape[0], store.d_tables.numel(), _stream())
+    call("mtmp_jpeg_idct", _p(coef), _p(sb.desc), _p(store.d_tables), _p(status), _p(pixels), sb.n, sb.max_blocks, _stream())
+
+
 def jpeg_decode(raw, subseq_bits=None):
-    """Fill the regions of ``raw.pixels`` (RawCxrBatch on the device) that belong to images handed over as JPEG file bytes;
-    returns their status words, int32 [raw.jpeg.n] on the device (0: decoded; include/mtmp.h names the bits).  An image whose
-    status is set is written as zeros.  subseq_bits: bits of the stream one lane decodes (None: the host's choice, 0: one lane
-    per restart segment)."""
-    if raw.jpeg is None:
+    """Fill the regions of ``raw.pixels`` (RawCxrBatch on the device) that belong to images handed over as JPEG file bytes
+    (``raw.jpeg``) or as handles of a CxrStore (``raw.stored``); returns the status words of the former, int32 [raw.jpeg.n] on
+    the device (0: decoded; include/mtmp.h names the bits; an empty tensor without ``raw.jpeg``).  An image whose status is set
+    is written as zeros; stored images have no status: the store's build refused what does not decode.  subseq_bits: bits of
+    the stream one lane decodes for ``raw.jpeg`` (None: the host's choice, 0: one lane per restart segment)."""
+    if raw.jpeg is None and raw.stored is None:
         raise ValueError("jpeg_decode: the batch holds no JPEG image")
+    if raw.stored is not None:
+        _store_decode(raw.stored, raw.pixels)
+    if raw.jpeg is None:
+        return torch.zeros(0, dtype=torch.int32, device=raw.pixels.device)
     return _jpeg_decode_plan(raw.jpeg, raw.pixels, subseq_bits)
+
+
+def cxr_store_decode(store, indices):
+    """The store's decoder on its own: images ``indices`` of a CxrStore on the device (any order, repeats allowed) -> (the uint8
+    pixel buffer on the store's device, the images back to back, and their ``(h, w)`` list)."""
+    from .builder.data.jpeg import JPG_H, JPG_W
+    if store.device.type != "cuda":
+        raise RuntimeError(f"medical_tri_modal_pilot_amd ops run on an MI355X only (cxr_store_decode: the store is on {store.device}); "
+                           "there is no CPU fallback")
+    sb = store.batch(indices)
+    sizes = [(int(h), int(w)) for h, w in store.rows[sb.indices][:, [JPG_H, JPG_W]]]
+    pixels = torch.empty(sum(h * w for h, w in sizes), dtype=torch.uint8, device=store.device)
+    with torch.cuda.device(store.device):
+        _store_decode(sb.to(store.device, non_blocking=True), pixels)
+    return pixels, sizes
 
 
 def jpeg_status_check(raw, status):
@@ -502,10 +539,11 @@ def cxr_prepare(raw, check: bool = True, subseq_bits=None):
     the zero-fill of the histogram table: mtmp_cxr_hist, mtmp_cxr_resize, mtmp_cxr_affine_crop.  A batch of the random chains
     (``raw.aug``) goes through _cxr_prepare_random.  Images handed over as JPEG file bytes (``raw.jpeg``) are decoded first
     (jpeg_decode); a stream that did not decode raises ValueError naming the image -- check=False skips that test, and the
-    device-to-host copy it costs, for callers that must not synchronise (the image is then a zero image)."""
-    if raw.jpeg is not None:
+    device-to-host copy it costs, for callers that must not synchronise (the image is then a zero image).  Handles of a CxrStore
+    (``raw.stored``) are decoded from the store; they need no such test and no copy."""
+    if raw.jpeg is not None or raw.stored is not None:
         status = jpeg_decode(raw, subseq_bits)
-        if check:
+        if check and raw.jpeg is not None:
             jpeg_status_check(raw, status)
     if raw.aug is not None:
         return _cxr_prepare_random(raw)

@@ -198,6 +198,27 @@ def make_raw_cxr(seed: int, img_time: torch.Tensor, sizes=RAW_CXR_SIZES):
     return samples
 
 
+def make_cxr_store(seed: int, n_images: int = 256):
+    """A CxrStore (builder/data/cxr_store.py, host half) of ``n_images`` of ``make_raw_cxr``'s images, JPEG-encoded as
+    ``--raw-images 2`` encodes them."""
+    from .builder.data.cxr_store import CxrStore
+    samples = make_raw_cxr(seed, torch.zeros(n_images))
+    return CxrStore.from_files([jpeg_encode(ims[0]) for ims, _ in samples], names=[f"synthetic/{i:05d}.jpg" for i in range(n_images)])
+
+
+def stored_cxr_samples(store, seed: int, img_time: torch.Tensor):
+    """``make_raw_cxr``'s ``(images, times)`` pairs with seeded handles of ``store`` in place of the arrays."""
+    rng = np.random.default_rng(seed)
+    multi = img_time.dim() == 2
+    t = img_time if multi else img_time.view(-1, 1)
+    absent = 10.0 if multi else -1.0
+    samples = []
+    for b in range(t.shape[0]):
+        times = [float(v) for v in t[b] if float(v) != absent]
+        samples.append(([store.image(int(rng.integers(store.n_images))) for _ in times], times))
+    return samples
+
+
 def jpeg_encode(image, quality: int = 75) -> bytes:
     """The uint8 [h, w] image as the bytes of the file ``Image.fromarray(image).save(path, 'JPEG')`` writes: 8-bit greyscale,
     baseline, PIL's defaults (what the reference's preprocessing stores, 1_mimic_cxr_preprocess.py:81-82).  PIL is needed for

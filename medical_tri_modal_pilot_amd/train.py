@@ -14,6 +14,9 @@ build-only flags wired in:
                       every --image-train-type but resize_larger, RandomResizedCrop (random) and RandAugment (randaug) included
     --raw-images 2    the same images JPEG-encoded (PIL writes them, as the reference's preprocessing does): the batches carry
                       file bytes, and the decoder runs on the GPU in front of that chain (ops.jpeg_decode, csrc/jpeg.hip)
+    --raw-images 3    those files in a synthetic device-resident image store (synthetic.make_cxr_store, builder/data/cxr_store.py),
+                      built and uploaded once: the batches carry handles, nothing is parsed and no stream or pixel byte is
+                      uploaded per batch (ops.jpeg_decode decodes them from the store's sync table)
     --tie-store 1     the vital-sign windows come from a synthetic device-resident event store (synthetic.make_tie_store: None
                       hours at both ends, empty present hours, windows over 1000 events): the loader hands over (patient, hour,
                       length) triples, builder/data/tie_store.py plans them, ops.tie_windows gathers in front of the step
@@ -56,7 +59,7 @@ class _Logger:
         self.lr = lr
 
 
-def synthetic_loader(args, n_iters: int, rank: int, epoch: int, tie_store=None, report_store=None):
+def synthetic_loader(args, n_iters: int, rank: int, epoch: int, tie_store=None, report_store=None, cxr_store=None):
     """n_iters batches of the 12-tuple of 2_train.py:143 (CPU tensors, like the reference's loader output)."""
     from .synthetic import make_batch
     multi = int(args.multiimages)
@@ -65,11 +68,14 @@ def synthetic_loader(args, n_iters: int, rank: int, epoch: int, tie_store=None, 
                         missing_mode="mixed" if "missing" in args.modality_inclusion else "none", multiimages=multi,
                         img_size=int(args.image_size), n_images=int(getattr(args, "n_images", 3)))
         static = torch.stack([bt["gen"], bt["age"]], 1)
-        if int(getattr(args, "raw_images", 0)) in (1, 2):
+        if int(getattr(args, "raw_images", 0)) in (1, 2, 3):
             from .builder.data.cxr_transform import collate_raw_cxr, transform_from_args
-            from .synthetic import jpeg_encode, make_raw_cxr
+            from .synthetic import jpeg_encode, make_raw_cxr, stored_cxr_samples
             g = torch.Generator().manual_seed(4241 + 7919 * rank + 104729 * epoch + it)
-            samples = make_raw_cxr(g.initial_seed(), bt["img_time"])
+            if int(args.raw_images) == 3:
+                samples = stored_cxr_samples(cxr_store, g.initial_seed(), bt["img_time"])
+            else:
+                samples = make_raw_cxr(g.initial_seed(), bt["img_time"])
             if int(args.raw_images) == 2:
                 samples = [([jpeg_encode(im) for im in ims], times) for ims, times in samples]
             raw = collate_raw_cxr(samples, transform_from_args(args, train=True),
@@ -128,9 +134,10 @@ def main(argv=None):
     from .builder.utils.cosine_annealing_with_warmup_v2 import CosineAnnealingWarmupRestarts
     parser = build_parser()
     parser.add_argument("--iters-per-epoch", type=int, default=100, help="len(train_loader) for synthetic data")
-    parser.add_argument("--raw-images", type=int, default=0, choices=[0, 1, 2],
+    parser.add_argument("--raw-images", type=int, default=0, choices=[0, 1, 2, 3],
                         help="1: synthetic batches carry uint8 images; the transform chain runs on the GPU (ops.cxr_prepare); "
-                             "2: they carry JPEG file bytes, decoded on the GPU in front of it (needs PIL to write the files)")
+                             "2: they carry JPEG file bytes, decoded on the GPU in front of it (needs PIL to write the files); "
+                             "3: they carry handles of a device-resident store of those files (builder/data/cxr_store.py)")
     parser.add_argument("--tie-store", type=int, default=0, choices=[0, 1],
                         help="1: the vital-sign windows come from a synthetic device-resident event store "
                              "(builder/data/tie_store.py); the loader hands over (patient, hour, length) triples")
@@ -149,7 +156,7 @@ def main(argv=None):
         raise SystemExit("training runs on an MI355X only (no CPU fallback)")
     if int(args.report_store) == 2 and args.berttype != "bert":
         raise SystemExit("--report-store 2 is the token-id store: it needs --berttype bert (--report-store 1 holds BioBERT embeddings)")
-    if int(args.raw_images) == 2:
+    if int(args.raw_images) in (2, 3):
         from .synthetic import jpeg_encode
         jpeg_encode(None)                              # fails here, by name, where PIL is not installed
     torch.cuda.set_device(local)
@@ -184,12 +191,19 @@ def main(argv=None):
         if rank == 0:
             print(f"token store: {report_store.n_reports} reports, {report_store.n_tokens} ids, {report_store.nbytes} bytes "
                   f"on {device}", flush=True)
+    cxr_store = None
+    if int(args.raw_images) == 3:
+        from .synthetic import make_cxr_store
+        cxr_store = make_cxr_store(6007 + rank).to(device)
+        if rank == 0:
+            print(f"image store: {cxr_store.n_images} images, {cxr_store.nbytes_streams} stream bytes, {cxr_store.nbytes_sync} "
+                  f"sync-table bytes, {cxr_store.nbytes} bytes on {device}, built in {cxr_store.build_ms:.1f} ms", flush=True)
     logger = _Logger()
     model.train()                                                                                    # 2_train.py:128
     iteration = 0
     for epoch in range(1, int(args.epochs) + 1):
         logger.loss, t0 = 0.0, time.perf_counter()
-        for it, batch in enumerate(synthetic_loader(args, n_it, rank, epoch, tie_store, report_store), 1):
+        for it, batch in enumerate(synthetic_loader(args, n_it, rank, epoch, tie_store, report_store, cxr_store), 1):
             x, static, y, in_len, img, img_time, txt, txt_len, txt_time, missing, _f, _y2 = batch
             iteration += 1
             model, iter_loss = get_trainer(args=args, iteration=iteration, x=x, static=static, input_lengths=in_len, y=y,
