@@ -746,6 +746,34 @@ int mtmp_token_embed_bwd_chunk(void);
 int mtmp_token_embed_bwd(const int32_t* ids, long long T, const void* dy, int dy_dtype, float* dw, void* workspace, int V, int D,
                          void* stream);
 
+/* ---- the device-side evaluator of a validation pass (additive; ABI stays 6).  builder/utils/device_evaluator.py owns the state:
+ *   pred float32 [capacity], tgt uint8 [capacity], logit float32 [capacity] (optional), ctr int64 [4] = predictions stored,
+ *   batches added, predictions dropped for lack of room, reserved; loss_sum float64 [1].  capacity <= 2^24.
+ *
+ * mtmp_eval_append: ONE launch of one workgroup per validation batch, capturable in a hipGraph: the cursor is ctr[0], read on the
+ *   device.  values / targets: float32 [count].  mode 0: values are logits, the stored prediction is 1 / (1 + exp(-x)) evaluated in
+ *   float64 and rounded once to float32 (and the raw logit goes to `logit` when that is given); mode 1: values are probabilities,
+ *   stored as they are.  Both then: NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX (torch.nan_to_num), -0.0 -> +0.0.  The target is
+ *   stored as t != 0.  Element i goes to slot ctr[0] + i when that is below capacity, otherwise it is dropped and counted in
+ *   ctr[2]; nothing is written out of range.  loss (may be NULL): the batch's float32 mean loss on the device; with it
+ *   loss_sum += (double)*loss and ctr[1] += 1.
+ *
+ * mtmp_eval_metrics: once per pass.  n is the HOST's count of stored predictions (launch geometry: nothing waits for the device).
+ *   out: float64 [8] device = auroc, ap, f1 at 0.01, best f1 over 0.01 .. 0.99, mean loss (loss_sum / ctr[1], NaN without a
+ *   batch that carried a loss), n, positives, status (bit 0: ctr[0] != n, bit 1: ctr[2] != 0).  The definitions are those of
+ *   builder/utils/metrics.py: exact curves over the distinct prediction values, AUROC 0 when a class is absent or n == 0, AP NaN
+ *   without positives, F1 = 2 tp / (predicted + positives) or 0, thresholds (double)p >= i / 100.0.  AUROC and the F1 values are
+ *   integer counts and one float64 division; AP is a float64 sum in a fixed order.  Equal inputs, in any order, give equal bits.
+ *   workspace: device memory of mtmp_eval_workspace_bytes(n) bytes (-1 for n outside 0 .. 2^24), 16-byte aligned, contents
+ *   irrelevant before and after.  A stable LSD radix sort by workgroups of mtmp_eval_sort_tile() keys; 18 launches.
+ * All argument errors return before anything touches a GPU. */
+int mtmp_eval_append(const float* values, const float* targets, long long count, int mode, const float* loss, float* pred,
+                     uint8_t* tgt, float* logit, long long capacity, long long* ctr, double* loss_sum, void* stream);
+int mtmp_eval_sort_tile(void);
+long long mtmp_eval_workspace_bytes(long long n);
+int mtmp_eval_metrics(const float* pred, const uint8_t* tgt, long long n, const long long* ctr, const double* loss_sum,
+                      void* workspace, long long workspace_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -128,6 +128,11 @@ SIGNATURES = {
     "mtmp_token_embed_bwd_workspace": (c_longlong, [c_longlong, c_int]),
     "mtmp_token_embed_bwd_chunk": (c_int, []),
     "mtmp_token_embed_bwd": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "mtmp_eval_append": (c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p,
+                                 c_void_p, c_void_p]),
+    "mtmp_eval_sort_tile": (c_int, []),
+    "mtmp_eval_workspace_bytes": (c_longlong, [c_longlong]),
+    "mtmp_eval_metrics": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p]),
     "mtmp_dropout_bwd": (c_int, [c_int, c_void_p, c_void_p, c_longlong, c_uint, c_void_p, c_float, c_void_p]),
 }
 

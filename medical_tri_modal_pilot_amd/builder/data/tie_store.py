@@ -249,6 +249,33 @@ class StoreWindowDataset(torch.utils.data.Dataset):
         return np.array([index, key, length], np.int32)          # 12 bytes: all a loader worker hands over
 
 
+class StoreWindowSweep(torch.utils.data.Dataset):
+    """EVERY window of the store as its own item, the way the reference's test data sets enumerate theirs (one item per
+    (patient, hour), dataset_new.py:1113-1166, :2500-2553): item ``i`` is the ``i``-th ``(patient, key, length)`` over the patients
+    in order and, inside a patient, over its present hours in order.  The length is ``min(key + 1, window_size)``; with
+    ``windows`` (one dict per patient, hour -> the stored ``win_size`` of that hour, as the test data set's index files record
+    it) the hours and the lengths are the list's."""
+
+    def __init__(self, store: TieEventStore, window_size: int = 24, windows: Optional[List[dict]] = None):
+        self.store, self.window_size = store, window_size
+        if windows is not None:
+            if len(windows) != store.n_patients:
+                raise ValueError(f"StoreWindowSweep: {len(windows)} window lists for {store.n_patients} patients")
+            items = [(p, int(k), int(w[k])) for p, w in enumerate(windows) for k in sorted(w)]
+        else:
+            items = []
+            for p in range(store.n_patients):
+                a, b = int(store.hour_ptr[p]), int(store.hour_ptr[p + 1])
+                items += [(p, k, min(k + 1, window_size)) for k in np.flatnonzero(store.present[a:b]).tolist()]
+        self.items = np.asarray(items, np.int32).reshape(-1, 3)
+
+    def __len__(self):
+        return self.items.shape[0]
+
+    def __getitem__(self, index: int):
+        return self.items[index].copy()                          # 12 bytes, like StoreWindowDataset's
+
+
 def collate_windows(samples, store: TieEventStore, tie_len: int = 1000, realtime: int = 1,
                     train_missing: bool = True) -> TieWindowBatch:
     """Stacks the triples of ``StoreWindowDataset`` and plans the batch (as a DataLoader ``collate_fn``:

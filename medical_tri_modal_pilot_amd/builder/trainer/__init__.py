@@ -1,5 +1,6 @@
 """``get_trainer`` with the reference's keyword surface (builder/trainer/__init__.py:14-47)."""
 from .trainer import missing_to_num, missing_trainer  # noqa: F401
+from .validate import validate  # noqa: F401
 
 
 def get_trainer(args, iteration, x, static, input_lengths, y, output_lengths, model, logger, device, scheduler,

@@ -199,16 +199,33 @@ def _staged_step(model, enc, optimizer, criterion, run_model, bounds):
     return [stage0] + [later(k) for k in range(1, n_stage)]
 
 
-def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, model, logger, device,
-                    scheduler=None, optimizer=None, criterion=None, scaler=None, flow_type=None, output_lengths=None,
-                    seq_lengths=None, x_img=None, x_txt=None, txt_lengths=None, imgtxt_time=None, missing=None,
-                    reports_tokens=None, reports_lengths=None, criterion_aux=None):
+class StepInputs:
+    """What prepare_step_inputs hands to a step: the device tensors of one batch, in the order the model takes them."""
+    __slots__ = ("data", "age", "gender", "input_lengths", "x_txt", "txt_lengths", "x_img", "missing_num", "img_time", "txt_time",
+                 "final_target", "feasible", "packed_extra", "deferred")
+
+    def tensors(self, target: bool = False) -> dict:
+        """the named inputs of run_model / of a captured step (``target``: with final_target)"""
+        t = dict(data=self.data, age=self.age, gender=self.gender, input_lengths=self.input_lengths, x_txt=self.x_txt,
+                 txt_lengths=self.txt_lengths, x_img=self.x_img, missing_num=self.missing_num, img_time=self.img_time,
+                 txt_time=self.txt_time)
+        if target:
+            t["final_target"] = self.final_target
+        t.update(self.packed_extra)
+        return t
+
+
+def prepare_step_inputs(args, train_x, static_x, input_lengths, train_y, model, device, graphed, defer_ok, output_lengths=None,
+                        x_img=None, x_txt=None, txt_lengths=None, imgtxt_time=None, missing=None) -> StepInputs:
+    """The input side of one step, shared by missing_trainer (training and its test flow) and builder/trainer/validate.py: fp16
+    rounding, ragged trim and length buckets, PackedTieBatch / TieWindowBatch / ReportBatch / TokenReportBatch / RawCxrBatch,
+    missing_to_num.  ``graphed``: the step will be replayed from a hipGraph (lengths are bucketed); ``defer_ok``: the fp16
+    rounding of device-resident fp32 tensors may ride on the copy into the graph's static buffers (StepInputs.deferred)."""
     img_time, txt_time = imgtxt_time
     # fp16 rounding of the event / time inputs (trainer.py:26-27, 2_train.py:164).  A device-resident fp32 tensor of a step
     # that will be replayed from a hipGraph is rounded by the copy into the graph's static buffers instead
     # (GraphedTrainStep.run round_fp16): two eager launches per tensor less in front of every step.
     deferred = set()
-    defer_ok = flow_type == "train" and _use_graph(args, flow_type, device, optimizer, scaler) and output_lengths is None
 
     def fp16_round(t, key):
         if (defer_ok and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
@@ -222,7 +239,6 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
     if isinstance(train_x, PackedTieBatch):
         # Ragged batch (builder/data): the events travel packed, there is nothing to trim; the padded
         # row count of the stream buffers is the batch maximum (bucketed for graph replays like the trim below).
-        graphed = _use_graph(args, flow_type, device, optimizer, scaler)
         max_len = int(torch.max(input_lengths))
         if graphed:
             max_len = graph_len_bucket(max_len, int(args.TIE_len))
@@ -235,7 +251,6 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
         # The lengths are the plan's: nothing waits for the device.  A model class says with ``takes_packed_tie = True`` that its
         # forward accepts a PackedTie (TRI_MBT_VSLTCLS and the siblings derived from it, unless they override it); a class
         # WITHOUT the attribute gets the padded tensor of the trim below -- always correct, at the price of the pad rows.
-        graphed = _use_graph(args, flow_type, device, optimizer, scaler)
         max_len = max(1, train_x.max_len)
         if graphed:
             max_len = graph_len_bucket(max_len, int(args.TIE_len))
@@ -251,7 +266,7 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
         # ragged trim, trainer.py:41-42 (at least one row: a batch of all-empty windows keeps one pad event behind kv_len --
         # pad rows feed nothing -- instead of zero-length launches)
         max_len = max(1, int(torch.max(input_lengths)))
-        if _use_graph(args, flow_type, device, optimizer, scaler):
+        if graphed:
             max_len = graph_len_bucket(max_len, train_x.shape[1])
         data = fp16_round(train_x[:, :max_len, :], "data")                    # 2_train.py:164
     if "rmse" in args.auxiliary_loss_type:
@@ -310,6 +325,23 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
     if cu_seqlens is not None:       # t_pad rides in the graph signature as the shape of an empty tensor
         packed_extra = dict(cu_seqlens=cu_seqlens, t_pad_marker=torch.empty(t_pad, 0, device=device))
 
+    s = StepInputs()
+    s.data, s.age, s.gender, s.input_lengths, s.x_txt, s.txt_lengths, s.x_img = data, age, gender, input_lengths, x_txt, txt_lengths, x_img
+    s.missing_num, s.img_time, s.txt_time, s.final_target, s.feasible = missing_num, img_time, txt_time, final_target, feasible
+    s.packed_extra, s.deferred = packed_extra, deferred
+    return s
+
+
+def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, model, logger, device,
+                    scheduler=None, optimizer=None, criterion=None, scaler=None, flow_type=None, output_lengths=None,
+                    seq_lengths=None, x_img=None, x_txt=None, txt_lengths=None, imgtxt_time=None, missing=None,
+                    reports_tokens=None, reports_lengths=None, criterion_aux=None):
+    graphed = _use_graph(args, flow_type, device, optimizer, scaler)
+    inp = prepare_step_inputs(args, train_x, static_x, input_lengths, train_y, model, device, graphed,
+                              flow_type == "train" and graphed and output_lengths is None, output_lengths, x_img, x_txt,
+                              txt_lengths, imgtxt_time, missing)
+    final_target, feasible, deferred = inp.final_target, inp.feasible, inp.deferred
+
     red = getattr(optimizer, "reducer", None)
     if red is not None and not getattr(red, "_mtmp_streams_set", False) and hasattr(model, "fusion_transformer"):
         red.extra_streams = list(model.fusion_transformer._side_streams(torch.device(device)) or [])
@@ -317,9 +349,7 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
 
     def run_model(t=None):
         if t is None:
-            t = dict(data=data, age=age, gender=gender, input_lengths=input_lengths, x_txt=x_txt,
-                     txt_lengths=txt_lengths, x_img=x_img, missing_num=missing_num, img_time=img_time,
-                     txt_time=txt_time, **packed_extra)
+            t = inp.tensors()
         x_in = t["data"] if "cu_seqlens" not in t else PackedTie(t["data"], t["cu_seqlens"], t["t_pad_marker"].shape[0])
         out, _, _ = model(x_in, None, None, None, None, t["age"], t["gender"], t["input_lengths"], t["x_txt"],
                           t["txt_lengths"], t["x_img"], t["missing_num"], feasible, t["img_time"], t["txt_time"],
@@ -329,8 +359,8 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
     if flow_type == "train" and _use_graph(args, flow_type, device, optimizer, scaler) and feasible is None:
         from medical_tri_modal_pilot_amd.graph import GraphedTrainStep
         gs = getattr(model, "_mtmp_graph_step", None)
-        if gs is None or gs.device != data.device:
-            gs = model._mtmp_graph_step = GraphedTrainStep(data.device, max_graphs=int(getattr(args, "hip_graph_max", 12)),
+        if gs is None or gs.device != inp.data.device:
+            gs = model._mtmp_graph_step = GraphedTrainStep(inp.data.device, max_graphs=int(getattr(args, "hip_graph_max", 12)),
                                                            fallback=bool(int(getattr(args, "hip_graph_fallback", 0))))
         # Data-parallel steps are captured as a few graphs cut at layer boundaries: the all-reduce of the gradient
         # buckets a stage completed starts right behind its replay and overlaps the next stage (ddp.py, staged mode).
@@ -340,9 +370,7 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
             red.staged = True
         if enc is not None and getattr(enc, "supports_segments", False):
             enc.graph_segments = bounds[1:-1]
-        inputs = dict(data=data, age=age, gender=gender, input_lengths=input_lengths, x_txt=x_txt,
-                      txt_lengths=txt_lengths, x_img=x_img, missing_num=missing_num, img_time=img_time,
-                      txt_time=txt_time, final_target=final_target, **packed_extra)
+        inputs = inp.tensors(target=True)
         if len(bounds) <= 2:
             def fwd_bwd(t):
                 if tuning.PREFORK_IMAGE_ENCODER and hasattr(model, "prefork"):

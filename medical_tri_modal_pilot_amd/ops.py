@@ -670,6 +670,40 @@ def report_token_ids(batch, device, out=None, tables=None):
     return out
 
 
+# ---- the device-side evaluator of a validation pass (csrc/evaluator.hip; builder/utils/device_evaluator.py owns the state) ----
+EVAL_SORT_TILE = 2048            # keys per workgroup of a sort pass (mtmp_eval_sort_tile(); tests size their cases by it)
+EVAL_MAX_CAPACITY = 1 << 24      # predictions one pass can hold (a guess at "more than enough": DESIGN 4, the validation pass)
+EVAL_LOGITS, EVAL_PROBS = 0, 1
+
+
+def eval_append(values, targets, mode, pred, tgt, logit, ctr, loss_sum, loss=None):
+    """One validation batch into the evaluator's buffers, ONE launch, no host value: ``values`` (float32, flat; ``mode``
+    EVAL_LOGITS | EVAL_PROBS) and ``targets`` (float32, flat) go behind the cursor ``ctr[0]``, which is read on the device -- the
+    launch can be captured in a hipGraph.  ``loss``: the batch's float32 mean loss on the device, added to ``loss_sum``."""
+    _gpu(values, targets, pred, tgt, logit, ctr, loss_sum, loss)
+    if values.dtype != torch.float32 or targets.dtype != torch.float32 or values.numel() != targets.numel():
+        raise ValueError("eval_append: values and targets are float32 tensors of one size")
+    if not (values.is_contiguous() and targets.is_contiguous()):
+        raise ValueError("eval_append: values and targets must be contiguous")
+    call("mtmp_eval_append", _p(values), _p(targets), values.numel(), int(mode), _p(loss), _p(pred), _p(tgt), _p(logit),
+         pred.numel(), _p(ctr), _p(loss_sum), _stream())
+
+
+def eval_workspace_bytes(n: int) -> int:
+    b = int(_lib.lib().mtmp_eval_workspace_bytes(int(n)))
+    if b < 0:
+        raise ValueError(f"eval_workspace_bytes: {n} predictions are outside 0 .. 2^24")
+    return b
+
+
+def eval_metrics(pred, tgt, n: int, ctr, loss_sum, workspace, out):
+    """The pass's metrics into ``out`` (float64 [8] on the device: auroc, ap, f1 at 0.01, best f1, mean loss, n, positives,
+    status), 18 launches, no host value: ``n`` is the HOST's count of stored predictions."""
+    _gpu(pred, tgt, ctr, loss_sum, workspace, out)
+    call("mtmp_eval_metrics", _p(pred), _p(tgt), int(n), _p(ctr), _p(loss_sum), _p(workspace), workspace.numel(), _p(out), _stream())
+    return out
+
+
 _token_embed_chunk = None
 
 

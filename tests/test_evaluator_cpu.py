@@ -1,0 +1,227 @@
+"""The device-side evaluator without a device: the numpy model (tests/evaluator_model.py) against scikit-learn and against
+builder/utils/metrics.py, the model's own sort and value rules, the new entry points' declarations and argument errors (the
+library loads without a GPU), and the StoreWindowSweep data set."""
+import ctypes
+import math
+import os
+import re
+import warnings
+
+import numpy as np
+import pytest
+import torch
+from sklearn.metrics import average_precision_score, roc_auc_score
+
+from tests import evaluator_model as M
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _same(a, b, tol):
+    return (math.isnan(a) and math.isnan(b)) or abs(a - b) <= tol
+
+
+@pytest.mark.parametrize("kind", M.KINDS)
+def test_model_against_sklearn_and_metrics_py(kind):
+    from medical_tri_modal_pilot_amd.builder.utils import metrics as R
+    for n in M.SIZES:
+        pred, tgt = M.case(kind, n)
+        auroc, ap, f1, best, _, nn, n_pos, status = M.metrics(pred, tgt)
+        assert (nn, n_pos, status) == (n, int(tgt.sum()), 0.0)
+        P, N = int(tgt.sum()), n - int(tgt.sum())
+        # scikit-learn, float64 scores: 1e-12
+        if P > 0 and N > 0:
+            assert abs(auroc - roc_auc_score(tgt, pred.astype(np.float64))) <= 1e-12, (kind, n)
+        else:
+            assert auroc == 0.0
+        if P > 0:
+            assert abs(ap - average_precision_score(tgt, pred.astype(np.float64))) <= 1e-12, (kind, n)
+        else:
+            assert math.isnan(ap)
+        # the package's own float32 metrics: 1e-6
+        tp, tt = torch.from_numpy(pred), torch.from_numpy(tgt)
+        assert _same(auroc, float(R.binary_auroc(tp, tt)), 1e-6), (kind, n)
+        assert _same(ap, float(R.binary_average_precision(tp, tt)), 1e-6), (kind, n)
+        assert _same(f1, float(R.binary_f1(tp, tt, 0.01)), 1e-6), (kind, n)
+        assert _same(best, float(R.best_f1_over_thresholds(tp, tt)), 1e-6), (kind, n)
+
+
+def test_model_against_the_curve_of_metrics_py_in_float64():
+    """the integer AUROC against _clf_curve + trapz in float64, AP against the same curve: the bound of the float64 sums"""
+    from medical_tri_modal_pilot_amd.builder.utils import metrics as R
+    for kind in M.KINDS:
+        for n in (1, 257, 4099, 70001):
+            pred, tgt = M.case(kind, n, seed=1)
+            auroc, ap = M.metrics(pred, tgt)[:2]
+            tps, fps, _ = R._clf_curve(torch.from_numpy(pred), torch.from_numpy(tgt))
+            if tps[-1] > 0 and fps[-1] > 0:
+                zero = tps.new_zeros(1)
+                want = float(torch.trapz(torch.cat([zero, tps / tps[-1]]), torch.cat([zero, fps / fps[-1]])))
+                assert abs(auroc - want) <= 1e-14, (kind, n)
+            if tps[-1] > 0:
+                recall = tps / tps[-1]
+                want = float(((recall - torch.cat([recall.new_zeros(1), recall[:-1]])) * (tps / (tps + fps))).sum())
+                assert abs(ap - want) <= 1e-11, (kind, n)
+
+
+def test_key_orders_every_float_and_the_radix_sort_is_the_stable_sort():
+    g = np.random.default_rng(5)
+    bits = g.integers(0, 1 << 32, 50000, dtype=np.uint64).astype(np.uint32)
+    special = np.array([0.0, 1e-45, -1e-45, 1e-39, -1e-39, 1.0, -1.0, M.FLT_MAX, -M.FLT_MAX, np.inf, -np.inf, 0.01, 0.5], np.float32)
+    p = np.concatenate([bits.view(np.float32), special])
+    p = p[~np.isnan(p)]
+    p = p[~((p == 0) & np.signbit(p))]                       # -0.0 never reaches the sort (the append stores +0.0)
+    k = M.sort_key(p)
+    assert k.dtype == np.uint32 and np.array_equal(M.key_to_float(k).view(np.uint32), p.view(np.uint32))
+    order = np.argsort(k, kind="stable")
+    assert np.all(np.diff(p[order].astype(np.float64)) <= 0)                    # descending floats
+    a, b = p[:-1], p[1:]
+    assert np.array_equal(k[:-1] < k[1:], a > b) and np.array_equal(k[:-1] == k[1:], a == b)
+    assert len({int(x) >> 24 for x in k}) > 200                                 # the top digit is exercised
+    vals = (g.random(p.size) < 0.5).astype(np.uint8)
+    kt = np.concatenate([k, k[:1000]])                                          # with ties: stability shows in the values
+    vt = np.concatenate([vals, 1 - vals[:1000]])
+    rk, rv = M.radix_sort(kt, vt)
+    sk, sv = M.stable_sort(kt, vt)
+    assert np.array_equal(rk, sk) and np.array_equal(rv, sv)
+    ends = M.tie_group_ends(np.array([9, 9, 7, 5, 5, 5, 1], np.uint32))
+    assert ends.tolist() == [False, True, True, False, False, True, True]
+
+
+def test_value_rules_of_the_append():
+    x = np.array([0.0, -0.0, 100.0, -100.0, np.inf, -np.inf, np.nan, 0.3, -2.5, 88.0, -745.0, -800.0], np.float32)
+    s = M.sigmoid_f32(x)
+    assert s.dtype == np.float32 and s[0] == s[1] == 0.5 and s[2] == 1.0 and s[4] == 1.0 and s[5] == 0.0 and np.isnan(s[6])
+    assert 0.0 < s[3] < 1e-43 and s[11] == 0.0                  # a denormal float32, then underflow to +0
+    assert s[7] == np.float32(1.0 / (1.0 + math.exp(-float(np.float32(0.3)))))
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        t = torch.nan_to_num(torch.tensor([np.nan, np.inf, -np.inf, -0.0, 2.0, -1.0])).numpy()
+    v = M.settle(np.array([np.nan, np.inf, -np.inf, -0.0, 2.0, -1.0], np.float32))
+    assert np.array_equal(v, t) and v[1] == M.FLT_MAX and v[2] == -M.FLT_MAX
+    assert v.view(np.uint32)[3] == 0 and t.view(np.uint32)[3] == 0x80000000       # the one rule nan_to_num does not have
+    st = M.State(5, keep_logits=True)
+    st.append([1.0, 2.0, 3.0], [0, 2, np.nan], 0, loss=np.float32(0.25))
+    st.append([0.5, 0.25, 0.125], [1, 0, 0], 1)
+    assert st.ctr.tolist() == [5, 1, 1, 0] and st.loss_sum == 0.25 and st.tgt.tolist() == [0, 1, 1, 1, 0]
+    assert st.pred[3] == 0.5 and st.logit.tolist() == [1.0, 2.0, 3.0, 0.0, 0.0]
+    assert M.metrics(st.pred, st.tgt, st.loss_sum, 1, stored=5, dropped=1)[4:] == [0.25, 5.0, 3.0, 2.0]
+    assert M.metrics(np.zeros(0, np.float32), np.zeros(0, np.uint8))[:4] == [0.0, pytest.approx(float("nan"), nan_ok=True), 0.0, 0.0]
+
+
+NAMES = ("mtmp_eval_append", "mtmp_eval_sort_tile", "mtmp_eval_workspace_bytes", "mtmp_eval_metrics")
+
+
+def test_new_entry_points_declared_listed_and_exported():
+    from medical_tri_modal_pilot_amd import _lib, ops
+    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
+    for name in NAMES:
+        m = re.search(r"\b(int|long long)\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
+        assert m, f"{name} is not declared in include/mtmp.h"
+        args = [a.strip() for a in m.group(2).split(",") if a.strip() != "void"]
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert restype is (ctypes.c_int if m.group(1) == "int" else ctypes.c_longlong) and len(args) == len(argtypes)
+        for decl, ct in zip(args, argtypes):
+            want = ctypes.c_void_p if "*" in decl else ctypes.c_longlong if decl.startswith("long long") else ctypes.c_int
+            assert ct is want, (name, decl, ct)
+    L = _lib.lib()
+    assert all(getattr(L, n) for n in NAMES) and L.mtmp_abi_version() == 6
+    assert L.mtmp_eval_sort_tile() == ops.EVAL_SORT_TILE and ops.EVAL_SORT_TILE % 256 == 0
+    mk = open(os.path.join(ROOT, "medical_tri_modal_pilot_amd", "csrc", "Makefile")).read()
+    assert re.search(r"^SRC\s*:=.*\bevaluator\.hip\b", mk, re.M)
+
+
+def test_workspace_query():
+    from medical_tri_modal_pilot_amd import _lib, ops
+    L = _lib.lib()
+    assert L.mtmp_eval_workspace_bytes(-1) == -1 and L.mtmp_eval_workspace_bytes((1 << 24) + 1) == -1
+    prev = 0
+    for n in (0, 1, ops.EVAL_SORT_TILE, ops.EVAL_SORT_TILE + 1, 70001, 1 << 24):
+        b = L.mtmp_eval_workspace_bytes(n)
+        assert b >= 10 * n and b % 16 == 0 and b >= prev and b == ops.eval_workspace_bytes(n)       # two key and two value arrays
+        prev = b
+    assert prev < 12 * (1 << 24)
+    with pytest.raises(ValueError, match="outside 0 .. 2\\^24"):
+        ops.eval_workspace_bytes((1 << 24) + 1)
+
+
+def test_entry_point_argument_errors():
+    """every refusal returns before anything touches a GPU; the message is the thread's last error"""
+    from medical_tri_modal_pilot_amd import _lib
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(4096)
+    base = (ctypes.addressof(buf) + 15) & ~15
+    p, odd4, odd8 = ctypes.c_void_p(base), ctypes.c_void_p(base + 2), ctypes.c_void_p(base + 4)
+
+    def run(fn, defaults, over):
+        a = dict(defaults)
+        a.update(over)
+        return getattr(L, fn)(*a.values()), L.mtmp_last_error().decode()
+    append = dict(values=p, targets=p, count=8, mode=0, loss=None, pred=p, tgt=p, logit=None, capacity=100, ctr=p, loss_sum=p, stream=None)
+    met = dict(pred=p, tgt=p, n=8, ctr=p, loss_sum=p, workspace=p, workspace_bytes=L.mtmp_eval_workspace_bytes(8), out=p, stream=None)
+    cases = [("mtmp_eval_append", append, o, w) for o, w in (
+                (dict(values=None), "null pointer"), (dict(targets=None), "null pointer"), (dict(pred=None), "null pointer"),
+                (dict(tgt=None), "null pointer"), (dict(ctr=None), "null pointer"), (dict(loss_sum=None), "null pointer"),
+                (dict(count=0), "count 0"), (dict(count=-3), "count -3"), (dict(capacity=0), "capacity 0"),
+                (dict(capacity=(1 << 24) + 1), "capacity 16777217"), (dict(mode=2), "mode 2"), (dict(pred=odd4), "4-byte aligned"),
+                (dict(logit=odd4), "4-byte aligned"), (dict(loss=odd4), "4-byte aligned"), (dict(ctr=odd8), "8-byte"),
+                (dict(loss_sum=odd8), "8-byte"))]
+    cases += [("mtmp_eval_metrics", met, o, w) for o, w in (
+                (dict(pred=None), "null pointer"), (dict(tgt=None), "null pointer"), (dict(ctr=None), "null pointer"),
+                (dict(loss_sum=None), "null pointer"), (dict(workspace=None), "null pointer"), (dict(out=None), "null pointer"),
+                (dict(n=-1), "n -1"), (dict(n=(1 << 24) + 1), "n 16777217"), (dict(pred=odd4), "4-byte aligned"),
+                (dict(out=odd8), "8-byte"), (dict(workspace=odd8), "16-byte"),
+                (dict(workspace_bytes=L.mtmp_eval_workspace_bytes(8) - 1), "the workspace holds"))]
+    for fn, defaults, over, word in cases:
+        rc, msg = run(fn, defaults, over)
+        assert rc != 0 and fn in msg and word in msg, (fn, over, rc, msg)
+
+
+def _args(**kw):
+    from medical_tri_modal_pilot_amd.control.config import parse_args
+    a = parse_args(["--input-types", "vslt_img_txt", "--model", "tri_mbt_vsltcls", "--modality-inclusion",
+                    "train-missing_test-missing", "--lr-init", "1e-5", "--batch-size", "4"])
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def test_device_evaluator_and_validate_refuse_by_name_without_a_device():
+    from medical_tri_modal_pilot_amd.builder.trainer import validate
+    from medical_tri_modal_pilot_amd.builder.utils.device_evaluator import DeviceEvaluator
+    with pytest.raises(RuntimeError, match="no CPU fallback"):
+        DeviceEvaluator(_args(), "cpu", 10)
+    with pytest.raises(ValueError, match="rmse"):
+        DeviceEvaluator(_args(auxiliary_loss_type="rmse"), "cuda:0", 10)
+    with pytest.raises(ValueError, match="capacity 16777217"):
+        DeviceEvaluator(_args(), "cuda:0", (1 << 24) + 1)
+
+    class Ev:
+        add_logits = metrics = None
+    with pytest.raises(ValueError, match="--ddp 1"):
+        validate(_args(ddp=1), None, [], "cuda:0", None, Ev())
+    with pytest.raises(ValueError, match="output_lengths / feasible"):
+        validate(_args(auxiliary_loss_input="x"), None, [], "cuda:0", None, Ev())
+    with pytest.raises(TypeError, match="DeviceEvaluator"):
+        validate(_args(), None, [], "cuda:0", None, object())
+
+
+def test_store_window_sweep_enumerates_the_present_hours():
+    from medical_tri_modal_pilot_amd.builder.data import StoreWindowSweep
+    from tests import tie_store_model as T
+    store, pats = T.new_synthetic_store(), T.synthetic_patients()
+    want = [(p, h, min(h + 1, 24)) for p, pat in enumerate(pats) for h, d in enumerate(pat["data_in_time"]) if d is not None]
+    ds = StoreWindowSweep(store)
+    assert len(ds) == len(want) == sum(int(store.present.sum()) for _ in (0,)) and len(want) > 30
+    got = [ds[i] for i in range(len(ds))]
+    assert all(g.dtype == np.int32 and g.shape == (3,) for g in got) and [tuple(g.tolist()) for g in got] == want
+    assert [tuple(g.tolist()) for g in (StoreWindowSweep(store, window_size=5)[i] for i in range(len(ds)))] == \
+        [(p, h, min(h + 1, 5)) for p, h, _ in want]
+    # the test data set's stored win_size per key: hours and lengths come from the list
+    windows = [{2: 3, 5: 1}, {25: 24, 0: 1, 7: 8}, {}]
+    sw = StoreWindowSweep(store, windows=windows)
+    assert [tuple(sw[i].tolist()) for i in range(len(sw))] == [(0, 2, 3), (0, 5, 1), (1, 0, 1), (1, 7, 8), (1, 25, 24)]
+    with pytest.raises(ValueError, match="2 window lists for 3 patients"):
+        StoreWindowSweep(store, windows=windows[:2])
+    plan = store.plan(np.stack([ds[i] for i in range(8)]).astype(np.int64), 64, 1)       # the items are what plan() takes
+    assert plan.batch_size == 8
