@@ -700,6 +700,29 @@ int mtmp_tie_window_gather(const double* ev_time, const float* ev_val, const uin
                            const long long* desc, const int32_t* cu_seqlens, float* out, int B, int max_len, int t_pad,
                            long long total_rows, long long out_rows, int padded, int realtime, int round_fp16, void* stream);
 
+/* ---- hourly carry-forward windows and their embedding, --vslt-type carryforward (additive; ABI stays 6).  The reference's loader
+ * cuts a [window_size][16] table of hourly carry-forward values per sample out of the patient's normalised table and pads it with
+ * zero rows (builder/data/dataset_new.py:2006-2011); its model embeds every row by Linear(16, 256) -> nn.LayerNorm -> ReLU
+ * (tri_mbt_vsltcls.py:51-57,179-181).  The table is `norm` of the event store above: a window is a row of `desc`.
+ *   mtmp_hourly_window_gather: desc int64 [B][2] device = (first_row, n_rows); out float32 [B][W][F].  Row r < n_rows of sample b
+ *   is norm[first_row + r][f_j], f_j = the j-th set bit of keep_bits (popcount(keep_bits) == F <= 18, else MTMP_ERR_ARG); with
+ *   round_fp16 float32 -> fp16 -> float32; every other row zeros.  ONE launch writes every element (no memset).  A descriptor row
+ *   with first_row < 0, n_rows < 0, n_rows > W or first_row + n_rows > n_hours has its sample written as zeros, not read out of
+ *   bounds. */
+int mtmp_hourly_window_gather(const float* norm, long long n_hours, const long long* desc, float* out, int B, int W, int F,
+                              unsigned keep_bits, int round_fp16, void* stream);
+/*   mtmp_hourly_embed_fwd: out[n][256] = ReLU(LN(x[n][F] . w[256][F]^T + b)) in `dtype`, 1 <= F <= 18; w = nn.Linear.weight as
+ *   stored; params float [3][256] = Linear bias, LayerNorm weight, LayerNorm bias; fp32 arithmetic, nn.LayerNorm semantics (biased
+ *   variance, eps 1e-5 inside the root).  One launch.
+ *   mtmp_hourly_embed_bwd: grads float [F + 3][256] overwritten = dW^T rows, db, dgamma, dbeta (x is data: no gradient).  Nothing
+ *   is saved by the forward but x: the pre-activation, the statistics and the ReLU gate are recomputed.  Two launches: per-workgroup
+ *   partial slabs in ws (mtmp_hourly_embed_bwd_ws_floats(n, F) floats), then their sum in a fixed order -- no float atomics,
+ *   bit-identical between runs. */
+int mtmp_hourly_embed_fwd(int dtype, const float* x, const float* w, const float* params, void* out, int n, int F, void* stream);
+int mtmp_hourly_embed_bwd_ws_floats(int n, int F);
+int mtmp_hourly_embed_bwd(int dtype, const float* x, const float* w, const float* params, const void* d_out, float* grads,
+                          float* ws, int n, int F, void* stream);
+
 /* ---- report token embeddings from a device-resident embedding store (additive; ABI stays 6): the reference reads a report's
  * [len][768] BioBERT embeddings from an h5 file per sample, appends zeros up to [128][768] and stacks the batch on the host
  * (builder/data/dataset_new.py:2135-2155).  Here every report is stored once (builder/data/report_store.py: CSR over reports ->

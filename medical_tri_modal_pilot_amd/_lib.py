@@ -122,6 +122,10 @@ SIGNATURES = {
     "mtmp_jpeg_store_entropy": (c_int, [c_void_p] * 8 + [c_int, c_int] + [c_longlong] * 4 + [c_void_p]),
     "mtmp_tie_window_gather": (c_int, [c_void_p] * 6 + [c_longlong, c_longlong] + [c_void_p] * 3 + [c_int] * 3 +
                                [c_longlong, c_longlong] + [c_int] * 3 + [c_void_p]),
+    "mtmp_hourly_window_gather": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_uint, c_int, c_void_p]),
+    "mtmp_hourly_embed_fwd": (c_int, [c_int] + [c_void_p] * 4 + [c_int, c_int, c_void_p]),
+    "mtmp_hourly_embed_bwd_ws_floats": (c_int, [c_int, c_int]),
+    "mtmp_hourly_embed_bwd": (c_int, [c_int] + [c_void_p] * 6 + [c_int, c_int, c_void_p]),
     "mtmp_report_gather": (c_int, [c_void_p, c_int, c_longlong, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
     "mtmp_report_ids_gather": (c_int, [c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "mtmp_token_embed_fwd": (c_int, [c_void_p, c_longlong, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),

@@ -4,7 +4,8 @@
 (/root/reference builder/data/dataset_new.py:1969-2030); ``PackedTieBatch`` replaces the zero-padded
 ``[B, TIE_len, 3]`` batch tensor by ``(events[sum T, 3], cu_seqlens[B + 1])`` on pinned host memory."""
 from .tie_dataset import (PackedTie, PackedTieBatch, SampleTieDataset, collate_packed, tie_window)  # noqa: F401
-from .tie_store import StoreWindowDataset, StoreWindowSweep, TieEventStore, TieWindowBatch, collate_windows  # noqa: F401
+from .tie_store import (HourlyWindowBatch, StoreWindowDataset, StoreWindowSweep, TieEventStore, TieWindowBatch,  # noqa: F401
+                        collate_hourly_windows, collate_windows, keep_mask)
 from .report_store import ReportBatch, ReportStore, TokenReportBatch, TokenReportStore, report_wanted  # noqa: F401
 from .cxr_store import CxrImage, CxrStore, CxrStoreBatch, image_wanted  # noqa: F401
 from .jpeg import JpegInfo, JpegPlan, parse_jpeg  # noqa: F401

@@ -15,6 +15,11 @@ What is stored, and why the result has the bits of ``tie_window``:
     integers 0..255 with a clear sign bit, whose float32 form is exact);
   * ``present`` [H]: a ``None`` hour is not an empty hour, the trimming depends on it;
   * ``hour_min`` [H] float64: the earliest event time of the hour (+inf without events), for the ``realtime != 1`` shift.
+
+The same store serves ``--vslt-type carryforward``: the loader's hourly table of a window (dataset_new.py:2006-2011) is a
+contiguous run of rows of ``norm`` in the kept columns, padded with zero rows -- ``TieEventStore.plan_hourly`` ->
+``HourlyWindowBatch`` (the same triples, the same refusals, the ``None``-hour trimming shared with ``plan`` for the text time) and
+``ops.hourly_windows`` (one launch, csrc/tie_store.hip).
 """
 import glob
 import os
@@ -60,6 +65,61 @@ class TieWindowBatch:
         d = np.stack([self.first_event, self.n_events, self.init_hour, self.first_hour, self.n_hours,
                       self.init_mask.astype(np.int64), self.t0, self.selected_key], axis=1).astype(np.int64)
         return torch.from_numpy(np.ascontiguousarray(d))
+
+
+DEFAULT_DROPPED = (6, 17)   # the two columns of the 18 whose names the default --vitalsign-labtest omits
+
+
+def keep_mask(feature_order: Sequence[str], wanted_names: Sequence[str]) -> np.ndarray:
+    """bool [len(feature_order)]: which columns of a pickle's table ``--vitalsign-labtest`` keeps (the reference's
+    ``args.vslt_mask``), from the pickle's own ``feature_order`` field."""
+    order = [str(n) for n in feature_order]
+    wanted = [str(n) for n in wanted_names]
+    unknown = [n for n in wanted if n not in order]
+    if unknown:
+        raise ValueError(f"keep_mask: {unknown} not in feature_order {order}")
+    return np.asarray([n in wanted for n in order], bool)
+
+
+def _keep_bits(keep) -> int:
+    """``keep`` (None | 18 booleans | column indices) -> the kernel's bit mask over the 18 columns."""
+    if keep is None:
+        cols = [f for f in range(N_FEAT) if f not in DEFAULT_DROPPED]
+    else:
+        k = np.asarray(keep)
+        if k.dtype == bool:
+            if k.shape != (N_FEAT,):
+                raise ValueError(f"plan_hourly: a boolean keep has {N_FEAT} entries, got {k.shape}")
+            cols = np.flatnonzero(k).tolist()
+        else:
+            if k.ndim != 1 or k.dtype.kind not in "iu":
+                raise ValueError(f"plan_hourly: keep is {N_FEAT} booleans or a list of column indices, got {k.dtype} {k.shape}")
+            cols = [int(c) for c in k]
+            if any(c < 0 or c >= N_FEAT for c in cols) or len(set(cols)) != len(cols) or cols != sorted(cols):
+                raise ValueError(f"plan_hourly: keep indices must be distinct, ascending and inside 0..{N_FEAT - 1}, got {cols}")
+    if not cols:
+        raise ValueError("plan_hourly: keep selects no column")
+    return sum(1 << int(c) for c in cols)
+
+
+class HourlyWindowBatch:
+    """The host plan of a batch of hourly carry-forward windows (``--vslt-type carryforward``): sample b is rows
+    ``first_row .. first_row + n_rows - 1`` of ``store.norm``, columns ``keep_bits``, then zero rows up to ``window_size``.
+    ``ops.hourly_windows`` writes the float32 [B, window_size, n_feat] table on the device; the lengths are here."""
+
+    def __init__(self, store, windows, first_row, n_rows, input_lengths, txt_time, static, window_size, keep_bits, realtime):
+        self.store, self.windows, self.first_row, self.n_rows = store, windows, first_row, n_rows
+        self.input_lengths, self.txt_time, self.static = input_lengths, txt_time, static
+        self.window_size, self.keep_bits, self.realtime = int(window_size), int(keep_bits), int(realtime)
+        self.n_feat = bin(self.keep_bits).count("1")
+
+    @property
+    def batch_size(self) -> int:
+        return int(self.input_lengths.numel())
+
+    def descriptor(self) -> torch.Tensor:
+        """int64 [B, 2]: (first_row, n_rows), the per-sample words of mtmp_hourly_window_gather."""
+        return torch.from_numpy(np.ascontiguousarray(np.stack([self.first_row, self.n_rows], axis=1).astype(np.int64)))
 
 
 class TieEventStore:
@@ -175,24 +235,26 @@ class TieEventStore:
         return self._dev
 
     # ------------------------------------------------------------------------------------------------------------ the plan
-    def plan(self, windows, tie_len: int, realtime: int, train_missing: bool = True) -> TieWindowBatch:
-        """``windows`` int [B, 3] = (patient, selected_key, rand_length) -> TieWindowBatch.  ``tie_window``'s control flow on the
-        hour-level arrays, vectorised over the batch."""
+    def _trim(self, windows, who: str, train_missing: bool, window_size: Optional[int] = None):
+        """The checks and the ``None``-hour trimming shared by ``plan`` and ``plan_hourly``: ``tie_window``'s control flow on the
+        hour-level arrays, vectorised over the batch.  Returns (w, refuse, base, first, early, late, L2, key2)."""
         w = np.asarray(windows)
         if w.ndim != 2 or w.shape[1] != 3 or w.shape[0] < 1 or w.dtype.kind not in "iu":
-            raise ValueError(f"plan: windows must be an integer array [B >= 1, 3], got {w.dtype} {w.shape}")
+            raise ValueError(f"{who}: windows must be an integer array [B >= 1, 3], got {w.dtype} {w.shape}")
         w = w.astype(np.int64)
         pat, key, L = w[:, 0], w[:, 1], w[:, 2]
 
         def refuse(bad, why):
             if bad.any():
                 b = int(np.flatnonzero(bad)[0])
-                raise ValueError(f"plan: window {b} (patient {int(pat[b])}, selected_key {int(key[b])}, rand_length {int(L[b])}) {why}")
+                raise ValueError(f"{who}: window {b} (patient {int(pat[b])}, selected_key {int(key[b])}, rand_length {int(L[b])}) {why}")
         refuse((pat < 0) | (pat >= self.n_patients), f"names a patient outside 0..{self.n_patients - 1}")
         base = self.hour_ptr[pat]
         refuse((key < 0) | (key >= self.hour_ptr[pat + 1] - base), "names an hour the patient does not have")
         refuse(L < 1, "has rand_length < 1")
         refuse(L > key + 1, "has rand_length > selected_key + 1")
+        if window_size is not None:
+            refuse(L > window_size, f"has rand_length > window_size {window_size}")
         first = key - L + 1                                   # sequenceGenerator's row 0: from the UNtrimmed key and length
         j = np.arange(int(L.max()), dtype=np.int64)[None, :]
         inside = j < L[:, None]
@@ -206,6 +268,13 @@ class TieEventStore:
         late = np.where(~head_none & tail_none, L - last_p - 1, 0)
         L2 = L - early
         key2 = key - late if train_missing else key.copy()
+        return w, refuse, base, first, early, late, L2, key2
+
+    def plan(self, windows, tie_len: int, realtime: int, train_missing: bool = True) -> TieWindowBatch:
+        """``windows`` int [B, 3] = (patient, selected_key, rand_length) -> TieWindowBatch.  ``tie_window``'s control flow on the
+        hour-level arrays, vectorised over the batch."""
+        w, refuse, base, first, early, late, L2, key2 = self._trim(windows, "plan", train_missing)
+        pat, key, L = w[:, 0], w[:, 1], w[:, 2]
         t0 = key2 - L2 + 1
         first_hour = base + first + early
         last_hour = base + key - late                         # tdl[early:-late]: `late` cuts the hours whatever train_missing is
@@ -224,6 +293,19 @@ class TieEventStore:
         txt_time = torch.from_numpy((-key2 if realtime == 1 else np.zeros_like(key2)).astype(np.float32))
         return TieWindowBatch(self, w, first_event, n_events, mask, init_hour, first_hour, last_hour - first_hour + 1, key2, t0,
                               first, torch.from_numpy(lens), cu, txt_time, torch.from_numpy(self.static[pat]), tie_len, realtime)
+
+
+    def plan_hourly(self, windows, window_size: int = 24, keep=None, realtime: int = 1,
+                    train_missing: bool = True) -> HourlyWindowBatch:
+        """``windows`` int [B, 3] = (patient, selected_key, rand_length) -> HourlyWindowBatch: the carry-forward branch of the
+        reference's loader (dataset_new.py:2006-2011).  Plane 0 of its result is ``norm[key - L + 1 : key + 1][:, keep]`` followed
+        by zero rows, its length the UNtrimmed ``rand_length``; only the text time sees the ``None``-hour trimming (``key2``)."""
+        bits = _keep_bits(keep)
+        w, _, base, first, _, _, _, key2 = self._trim(windows, "plan_hourly", train_missing, int(window_size))
+        pat, L = w[:, 0], w[:, 2]
+        txt_time = torch.from_numpy((-key2 if realtime == 1 else np.zeros_like(key2)).astype(np.float32))
+        return HourlyWindowBatch(self, w, base + first, L.copy(), torch.from_numpy(L.copy()), txt_time,
+                                 torch.from_numpy(self.static[pat]), window_size, bits, realtime)
 
 
 class StoreWindowDataset(torch.utils.data.Dataset):
@@ -281,3 +363,10 @@ def collate_windows(samples, store: TieEventStore, tie_len: int = 1000, realtime
     """Stacks the triples of ``StoreWindowDataset`` and plans the batch (as a DataLoader ``collate_fn``:
     ``functools.partial(collate_windows, store=store, tie_len=..., realtime=...)``)."""
     return store.plan(np.stack([np.asarray(s, np.int64).reshape(3) for s in samples]), tie_len, realtime, train_missing)
+
+
+def collate_hourly_windows(samples, store: TieEventStore, window_size: int = 24, keep=None, realtime: int = 1,
+                           train_missing: bool = True) -> HourlyWindowBatch:
+    """The ``collate_fn`` twin of ``collate_windows`` for ``--vslt-type carryforward``: stacks the triples and plans the batch."""
+    return store.plan_hourly(np.stack([np.asarray(s, np.int64).reshape(3) for s in samples]), window_size, keep, realtime,
+                             train_missing)

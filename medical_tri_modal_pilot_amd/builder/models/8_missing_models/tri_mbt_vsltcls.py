@@ -353,7 +353,12 @@ class TRI_MBT_VSLTCLS(nn.Module):
         txt_time = txt_time.float()
         it = tt = None
         if self.args.vslt_type == "carryforward":
-            vslt_embedding = self.vslt_enc(x).to(dt)
+            if tuning.HIP_HOURLY_EMBED and x.is_cuda:
+                # the hourly table's Linear -> LayerNorm -> ReLU (:51-57,179-181) as one HIP launch each way (ops.HourlyEmbedFn)
+                enc = self.vslt_enc
+                vslt_embedding = ops.HourlyEmbedFn.apply(x, enc[0].weight, enc[0].bias, enc[1].weight, enc[1].bias, dt)
+            else:
+                vslt_embedding = self.vslt_enc(x).to(dt)
         else:
             joint = self._joint_embeddings(x, img_time, txt_time, dt) if self.args.imgtxt_time == 1 else None
             if joint is not None:

@@ -314,11 +314,12 @@ MTMP_DEV TieChain tie_load_chain(const float* prm, int chain, int lane) {
     const float* base = prm + chain * 4 * D + 4 * lane;
     return TieChain{ld4f(base), ld4f(base + D), ld4f(base + 2 * D), ld4f(base + 3 * D)};
 }
-// forward of one chain for one event; returns pre-ReLU y, and xh / rstd for the backward
-MTMP_DEV void tie_chain_fwd(const TieChain& c, float s, float (&y)[4], float (&xh)[4], float& rstd) {
-    float u[4], su = 0.f;
+// nn.LayerNorm of one row of 256 pre-activations, 4 per lane (biased variance, eps inside the root): pre-ReLU y, and xh / rstd for
+// the backward.  Shared by the TIE chains (F = 1) and the hourly embedding (F <= 18).
+MTMP_DEV void tie_ln_row(const float (&u)[4], const f32x4& g, const f32x4& be, float (&y)[4], float (&xh)[4], float& rstd) {
+    float su = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { u[i] = fmaf(s, c.w[i], c.b[i]); su += u[i]; }
+    for (int i = 0; i < 4; ++i) su += u[i];
     su = wave_sum(su);
     const float mu = su * (1.0f / D);
     float sv = 0.f;
@@ -327,7 +328,14 @@ MTMP_DEV void tie_chain_fwd(const TieChain& c, float s, float (&y)[4], float (&x
     sv = wave_sum(sv);
     rstd = rsqrtf(sv * (1.0f / D) + 1e-5f);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { xh[i] = (u[i] - mu) * rstd; y[i] = fmaf(xh[i], c.g[i], c.be[i]); }
+    for (int i = 0; i < 4; ++i) { xh[i] = (u[i] - mu) * rstd; y[i] = fmaf(xh[i], g[i], be[i]); }
+}
+// forward of one chain for one event; returns pre-ReLU y, and xh / rstd for the backward
+MTMP_DEV void tie_chain_fwd(const TieChain& c, float s, float (&y)[4], float (&xh)[4], float& rstd) {
+    float u[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) u[i] = fmaf(s, c.w[i], c.b[i]);
+    tie_ln_row(u, c.g, c.be, y, xh, rstd);
 }
 
 // Row map of the PACKED event layout (the ragged collate): the batch's events are stored back to
@@ -465,6 +473,100 @@ __global__ __launch_bounds__(256) void tie_bwd_kernel(const float* ev, const flo
         row[8 * D + i] = ((ftab_acc[i] + ftab_acc[20 * D + i]) + ftab_acc[2 * 20 * D + i]) + ftab_acc[3 * 20 * D + i];
     __syncthreads();
     flush_partials<8>(acc, row, lds, lane, wave);
+}
+
+// ------------------------------------------------------------------------------------------
+// Hourly carry-forward embedding (tri_mbt_vsltcls.py:51-57,179-181): E[r,:] = ReLU(LN(x[r,:F] . W^T + b)), the TIE value chain
+// with F <= 18 inputs per row instead of one.  One wave per row; a lane keeps the 4 F weights of its 4 columns in registers (the
+// loops run to HOURLY_F with zeros behind F: adding 0 * 0 changes no sum) and reads the row's F inputs at a wave-uniform address.
+constexpr int HOURLY_F = 18;
+constexpr int HOURLY_NV = HOURLY_F + 3;        // accumulator rows of the backward: dW^T[18], db, dgamma, dbeta
+constexpr int HOURLY_BWD_BLOCKS = 64;          // slab rows: launch_slab_reduce sums <= 64 rows in ONE launch
+static_assert(HOURLY_BWD_BLOCKS <= 64, "the backward is two launches only while the slab has one reduction level");
+
+struct HourlyPrm { float w[HOURLY_F][4]; f32x4 b, g, be; };
+
+MTMP_DEV HourlyPrm hourly_load(const float* w, const float* prm, int F, int lane) {
+    HourlyPrm p;
+#pragma unroll
+    for (int f = 0; f < HOURLY_F; ++f)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) p.w[f][i] = f < F ? w[(size_t)(4 * lane + i) * F + f] : 0.f;
+    p.b = ld4f(prm + 4 * lane);
+    p.g = ld4f(prm + D + 4 * lane);
+    p.be = ld4f(prm + 2 * D + 4 * lane);
+    return p;
+}
+// pre-activation of one row: u = b + sum_f x[f] w[:, f] (xs: the row's inputs, zeros behind F)
+MTMP_DEV void hourly_row(const HourlyPrm& p, const float* xr, int F, float (&xs)[HOURLY_F], float (&u)[4]) {
+#pragma unroll
+    for (int f = 0; f < HOURLY_F; ++f) xs[f] = f < F ? xr[f] : 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) u[i] = p.b[i];
+#pragma unroll
+    for (int f = 0; f < HOURLY_F; ++f)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) u[i] = fmaf(xs[f], p.w[f][i], u[i]);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void hourly_fwd_kernel(const float* x, const float* w, const float* prm, T* out, int n, int F) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const HourlyPrm p = hourly_load(w, prm, F, lane);
+    for (int row = blockIdx.x * 4 + wave; row < n; row += gridDim.x * 4) {
+        float xs[HOURLY_F], u[4], y[4], xh[4], rstd;
+        hourly_row(p, x + (size_t)row * F, F, xs, u);
+        tie_ln_row(u, p.g, p.be, y, xh, rstd);
+        store4<T>(out + (size_t)row * D + 4 * lane, fmaxf(y[0], 0.f), fmaxf(y[1], 0.f), fmaxf(y[2], 0.f), fmaxf(y[3], 0.f));
+    }
+}
+
+// Nothing is saved by the forward but x: the pre-activation, the statistics and the ReLU gate are recomputed.  Slab row of a
+// workgroup: [F + 3][256] = dW^T rows, db, dgamma, dbeta (the layout of `grads`), the four waves summed in wave order.
+template <typename T>
+__global__ __launch_bounds__(256) void hourly_bwd_kernel(const float* x, const float* w, const float* prm, const T* dE, float* slab,
+                                                         int n, int F) {
+    __shared__ __attribute__((aligned(16))) float lds[4 * HOURLY_NV * D];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const HourlyPrm p = hourly_load(w, prm, F, lane);
+    float acc[HOURLY_NV][4];
+#pragma unroll
+    for (int v = 0; v < HOURLY_NV; ++v)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[v][i] = 0.f;
+    for (int row = blockIdx.x * 4 + wave; row < n; row += gridDim.x * 4) {
+        float xs[HOURLY_F], u[4], y[4], xh[4], rstd, g[4], sg = 0.f, sgx = 0.f;
+        const f32x4 d = load4<T>(dE + (size_t)row * D + 4 * lane);
+        hourly_row(p, x + (size_t)row * F, F, xs, u);
+        tie_ln_row(u, p.g, p.be, y, xh, rstd);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float dy = y[i] > 0.f ? d[i] : 0.f;
+            acc[HOURLY_F + 1][i] += dy * xh[i];
+            acc[HOURLY_F + 2][i] += dy;
+            g[i] = dy * p.g[i];
+            sg += g[i];
+            sgx += g[i] * xh[i];
+        }
+        wave_sum2(sg, sgx);
+        const float mg = sg * (1.0f / D), mgx = sgx * (1.0f / D);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float du = rstd * (g[i] - mg - xh[i] * mgx);
+            acc[HOURLY_F][i] += du;
+#pragma unroll
+            for (int f = 0; f < HOURLY_F; ++f) acc[f][i] = fmaf(du, xs[f], acc[f][i]);
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < HOURLY_NV; ++v)
+        *reinterpret_cast<f32x4*>(lds + (wave * HOURLY_NV + v) * D + 4 * lane) = f32x4{acc[v][0], acc[v][1], acc[v][2], acc[v][3]};
+    __syncthreads();
+    float* row = slab + (size_t)blockIdx.x * (F + 3) * D;
+    for (int i = threadIdx.x; i < (F + 3) * D; i += 256) {
+        const int v = i >> 8, src = ((v < F ? v : HOURLY_F + (v - F)) << 8) + (i & 255);
+        row[i] = lds[src] + lds[HOURLY_NV * D + src] + lds[2 * HOURLY_NV * D + src] + lds[3 * HOURLY_NV * D + src];
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -622,6 +724,42 @@ extern "C" int mtmp_tie_time_embed_bwd_partials(int dtype, const float* events, 
                    "mtmp_tie_time_embed_bwd_partials: bad argument (n=%d n_time=%d n_time_a=%d)", n, n_time, n_time_a);
     return launch_tie_bwd_partials(dtype, events, params, d_out, ws, n, nullptr, 0, (hipStream_t)stream,
                                    "mtmp_tie_time_embed_bwd_partials", true, time_events, d_time_a, d_time_b, n_time, n_time_a);
+}
+
+// ---- hourly carry-forward embedding (--vslt-type carryforward): out[n][256] = ReLU(LN(x[n][F] . w[256][F]^T + b)) in dtype,
+// 1 <= F <= 18; params float [3][256] = Linear bias, LayerNorm weight, LayerNorm bias.  One launch.
+namespace {
+int hourly_bwd_blocks(int n) { return max(1, min((n + 3) / 4, HOURLY_BWD_BLOCKS)); }
+}
+extern "C" int mtmp_hourly_embed_fwd(int dtype, const float* x, const float* w, const float* params, void* out, int n, int F,
+                                     void* stream) {
+    MTMP_CHECK_ARG(x && w && params && out && n > 0 && F >= 1 && F <= HOURLY_F, "mtmp_hourly_embed_fwd: bad argument (n=%d F=%d)", n, F);
+    const int nb = max(1, min((n + 3) / 4, 2048));
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == 0) hipLaunchKernelGGL(hourly_fwd_kernel<float>, dim3(nb), dim3(256), 0, st, x, w, params, (float*)out, n, F);
+    else if (dtype == 1) hipLaunchKernelGGL(hourly_fwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, x, w, params, (bf16*)out, n, F);
+    else { mtmp_set_error("mtmp_hourly_embed_fwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
+    MTMP_CHECK_LAUNCH("mtmp_hourly_embed_fwd");
+    return MTMP_OK;
+}
+
+extern "C" int mtmp_hourly_embed_bwd_ws_floats(int n, int F) { return hourly_bwd_blocks(n) * (F + 3) * D; }
+
+// grads float [F + 3][256] overwritten: dW^T rows, db, dgamma, dbeta.  ws: mtmp_hourly_embed_bwd_ws_floats(n, F) floats.  Two
+// launches: per-workgroup partial slabs (at most 64 rows), then their sum in a fixed order -- bit-identical between runs.
+extern "C" int mtmp_hourly_embed_bwd(int dtype, const float* x, const float* w, const float* params, const void* d_out,
+                                     float* grads, float* ws, int n, int F, void* stream) {
+    MTMP_CHECK_ARG(x && w && params && d_out && grads && ws && n > 0 && F >= 1 && F <= HOURLY_F,
+                   "mtmp_hourly_embed_bwd: bad argument (n=%d F=%d)", n, F);
+    const int nb = hourly_bwd_blocks(n);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == 0) hipLaunchKernelGGL(hourly_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, x, w, params, (const float*)d_out, ws, n, F);
+    else if (dtype == 1) hipLaunchKernelGGL(hourly_bwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, x, w, params, (const bf16*)d_out, ws, n, F);
+    else { mtmp_set_error("mtmp_hourly_embed_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
+    MTMP_CHECK_LAUNCH("mtmp_hourly_embed_bwd");
+    launch_slab_reduce(ws, nb, (F + 3) * D, nullptr, grads, st);     // nb <= 64: one level, the tail is not used
+    MTMP_CHECK_LAUNCH("mtmp_hourly_embed_bwd(reduce)");
+    return MTMP_OK;
 }
 
 extern "C" int mtmp_stream_input_ws_floats(int rows) { return (max(1, min((rows + 15) / 16, 1024)) + RED_GROUPS) * 7 * D; }

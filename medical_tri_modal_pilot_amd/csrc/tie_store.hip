@@ -118,7 +118,52 @@ __global__ __launch_bounds__(THREADS) void tie_window_gather_kernel(TieStore st,
     }
 }
 
+// mtmp_hourly_window_gather   the hourly carry-forward windows (--vslt-type carryforward) from the same store: sample b is rows
+//   first_row .. first_row + n_rows - 1 of `norm`, the columns whose bits are set in keep_bits, then zero rows up to W.  One thread
+//   per output float; every element of out is written (no memset in front).
+__global__ __launch_bounds__(THREADS) void hourly_window_gather_kernel(const float* __restrict__ norm, long long n_hours,
+                                                                       const long long* __restrict__ desc, float* __restrict__ out,
+                                                                       long long total, int W, int F, unsigned keep_bits,
+                                                                       int round_fp16) {
+    const long long e = (long long)blockIdx.x * THREADS + threadIdx.x;
+    if (e >= total) return;
+    const int j = (int)(e % F);
+    const long long t = e / F;
+    const int r = (int)(t % W);
+    const long long b = t / W;
+    const long long first = desc[2 * b], n = desc[2 * b + 1];
+    const bool sane = first >= 0 && n >= 0 && n <= W && first <= n_hours - n;
+    float v = 0.f;
+    if (sane && r < n) {
+        int k = 0, seen = 0;
+#pragma unroll
+        for (int f = 0; f < N_FEAT; ++f) {
+            const int s = keep_bits >> f & 1u;
+            if (s && seen == j) k = f;
+            seen += s;
+        }
+        v = round_out(norm[(first + r) * N_FEAT + k], round_fp16);
+    }
+    out[e] = v;
+}
+
 }  // namespace
+
+extern "C" int mtmp_hourly_window_gather(const float* norm, long long n_hours, const long long* desc, float* out, int B, int W, int F,
+                                         unsigned keep_bits, int round_fp16, void* stream) {
+    MTMP_CHECK_ARG(norm && desc && out, "mtmp_hourly_window_gather: null pointer");
+    MTMP_CHECK_ARG(B > 0 && B <= (1 << 20) && n_hours > 0 && W >= 1 && W <= (1 << 16) && F >= 1 && F <= N_FEAT,
+                   "mtmp_hourly_window_gather: bad argument (B=%d hours=%lld W=%d F=%d)", B, n_hours, W, F);
+    MTMP_CHECK_ARG((keep_bits >> N_FEAT) == 0 && __builtin_popcount(keep_bits) == F,
+                   "mtmp_hourly_window_gather: keep_bits 0x%x does not select F=%d of the %d columns", keep_bits, F, N_FEAT);
+    const long long total = (long long)B * W * F;
+    const long long blocks = (total + THREADS - 1) / THREADS;
+    MTMP_CHECK_ARG(blocks <= 0x7fffffffLL, "mtmp_hourly_window_gather: %lld workgroups", blocks);
+    hipLaunchKernelGGL(hourly_window_gather_kernel, dim3((unsigned)blocks), dim3(THREADS), 0, (hipStream_t)stream, norm, n_hours,
+                       desc, out, total, W, F, keep_bits, round_fp16);
+    MTMP_CHECK_LAUNCH("mtmp_hourly_window_gather");
+    return MTMP_OK;
+}
 
 extern "C" int mtmp_tie_window_gather(const double* ev_time, const float* ev_val, const uint8_t* ev_feat, const float* norm,
                                       const double* delta, const double* hour_min, long long n_events, long long n_hours,

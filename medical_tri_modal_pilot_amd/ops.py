@@ -616,6 +616,36 @@ def tie_windows(batch, device, t_pad: int, bucket: int = 0, padded: bool = False
     return out if padded else PackedTie(out, cu, int(t_pad))
 
 
+# ---- hourly carry-forward windows (--vslt-type carryforward) from the same store (csrc/tie_store.hip) ----------------------
+def hourly_windows(batch, device, round_fp16: bool = True, out=None, tables=None):
+    """HourlyWindowBatch (builder/data/tie_store.py: the host plan of a batch of (patient, selected_key, rand_length) windows) ->
+    the float32 ``[B, window_size, n_feat]`` table the reference's loader cuts and pads on the host (plane 0 of its carry-forward
+    item), in ONE launch that writes all of it (no memset): row ``r < rand_length`` is the patient's normalised hour
+    ``selected_key - rand_length + 1 + r`` in the kept columns, every other row zeros.  round_fp16: the trainer's
+    ``.half().float()``.  The store must be on ``device`` (``store.to(device)``, once).  One small host-to-device copy (the
+    descriptor), no device value is waited for.  out: a buffer to write into; tables: the descriptor already on the device
+    (tools/bench_hourly.py times the launch alone, the tests hand over descriptors the plan would never make)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"medical_tri_modal_pilot_amd ops run on an MI355X only (hourly_windows on {device}); there is no CPU fallback")
+    store = batch.store
+    dv = store.device_arrays()
+    B, W, F = batch.batch_size, batch.window_size, batch.n_feat
+    desc = batch.descriptor().to(device, non_blocking=True) if tables is None else tables
+    if store.device != desc.device:
+        raise RuntimeError(f"hourly_windows: the event store is on {store.device}, not on {desc.device}: call store.to(device) once")
+    if tuple(desc.shape) != (B, 2) or desc.dtype != torch.int64 or not desc.is_contiguous():
+        raise ValueError(f"hourly_windows: the descriptor must be a contiguous int64 tensor {(B, 2)}")
+    if out is None:
+        out = torch.empty((B, W, F), dtype=torch.float32, device=desc.device)
+    elif tuple(out.shape) != (B, W, F) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != desc.device:
+        raise ValueError(f"hourly_windows: out must be a contiguous float32 tensor {(B, W, F)} on {device}")
+    with torch.cuda.device(desc.device), kernel_marks("hourly_window_gather", B):
+        call("mtmp_hourly_window_gather", _p(dv["norm"]), store.n_hours, _p(desc), _p(out), B, W, F, batch.keep_bits,
+             int(round_fp16), _stream())
+    return out
+
+
 # ---- report token embeddings from the device-resident embedding store (csrc/report_store.hip) ----------------------------
 def report_tokens(batch, device, dtype, out=None, tables=None):
     """ReportBatch (builder/data/report_store.py: the host plan of a batch of report indices) -> the ``[B, max_tokens, width]``
@@ -1086,6 +1116,38 @@ class TieEmbed(torch.autograd.Function):
         g = grads
         v = sink_param_grads(ctx.value_chain, [g[0].view(ctx.wshape[0]), g[1], g[2], g[3]])
         return (None, v[0], v[1], v[2], v[3], g[4].view(ctx.wshape[1]), g[5], g[6], g[7], g[8:28], None)
+
+
+class HourlyEmbedFn(torch.autograd.Function):
+    """tri_mbt_vsltcls.py:51-57,179-181 (--vslt-type carryforward): vslt_enc = Linear(F, 256) -> nn.LayerNorm -> ReLU of the
+    hourly table x [B, W, F] fp32 (data: no gradient), one launch forward and two backward.  The backward keeps x alone and
+    recomputes the rest; the four gradients go to the flat buffer through sink_param_grads, as TieEmbed's value chain does."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, gamma, beta, dtype):
+        _gpu(x, w)
+        B, W, F = x.shape
+        if tuple(w.shape) != (D_MODEL, F) or not 1 <= F <= 18:
+            raise ValueError(f"HourlyEmbedFn: x {tuple(x.shape)} needs a weight [{D_MODEL}, F <= 18], got {tuple(w.shape)}")
+        xs = _c(x.float()).view(B * W, F)
+        wf = _c(w.detach().float())
+        prm = torch.stack([b.detach(), gamma.detach(), beta.detach()]).float().contiguous()
+        out = torch.empty(B, W, D_MODEL, dtype=dtype, device=x.device)
+        call("mtmp_hourly_embed_fwd", _dt(out), _p(xs), _p(wf), _p(prm), _p(out), B * W, F, _stream())
+        ctx.save_for_backward(xs, wf, prm)
+        ctx.chain = [w, b, gamma, beta]
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        xs, wf, prm = ctx.saved_tensors
+        n, F = xs.shape
+        d_out = _c(d_out)
+        grads = torch.empty(F + 3, D_MODEL, dtype=torch.float32, device=xs.device)
+        ws = torch.empty(_lib.lib().mtmp_hourly_embed_bwd_ws_floats(n, F), dtype=torch.float32, device=xs.device)
+        call("mtmp_hourly_embed_bwd", _dt(d_out), _p(xs), _p(wf), _p(prm), _p(d_out), _p(grads), _p(ws), n, F, _stream())
+        v = sink_param_grads(ctx.chain, [grads[:F].t(), grads[F], grads[F + 1], grads[F + 2]])
+        return (None, v[0], v[1], v[2], v[3], None)
 
 
 class TimeEmbed(torch.autograd.Function):

@@ -61,19 +61,31 @@ def fill_state_dict(sd):
 
 
 def make_batch(seed: int, B: int, T: int, *, ragged: bool = True, missing_mode: str = "mixed",
-               multiimages: int = 0, txt_tokens: int = 128, img_size: int = 224, n_images: int = 3):
+               multiimages: int = 0, txt_tokens: int = 128, img_size: int = 224, n_images: int = 3, vslt_type: str = "TIE",
+               n_feat: int = 16):
     """Synthetic tri-modal batch following SURVEY.md §8d (seeded, CPU generator).
-    Returns a dict of CPU tensors with the trainer-level (post-unpack) meaning."""
+    Returns a dict of CPU tensors with the trainer-level (post-unpack) meaning.  ``vslt_type="carryforward"``: ``x`` is the
+    loader's [B, 3, T, n_feat] hourly item (T = the window size) -- plane 0 values in [0, 1] with zero rows behind the length,
+    planes 1 and 2 (mask, delta: read by no model here) zeros -- and ``input_lengths`` lies in 1..T."""
+    if vslt_type not in ("TIE", "carryforward"):
+        raise ValueError(f"make_batch: vslt_type is TIE or carryforward, got {vslt_type}")
     g = torch.Generator().manual_seed(seed)
     U = lambda *s: torch.rand(*s, generator=g)
-    if ragged:
+    if vslt_type == "carryforward":
+        lens = torch.randint(1, T + 1, (B,), generator=g) if ragged else torch.full((B,), T, dtype=torch.long)
+        if ragged:
+            lens[0] = T
+    elif ragged:
         lens = torch.randint(3, T + 1, (B,), generator=g)
         lens[0] = T
     else:
         lens = torch.full((B,), T, dtype=torch.long)
-    x = torch.zeros(B, T, 3)
+    x = torch.zeros(B, 3, T, n_feat) if vslt_type == "carryforward" else torch.zeros(B, T, 3)
     for b in range(B):
         n = int(lens[b])
+        if vslt_type == "carryforward":
+            x[b, 0, :n] = U(n, n_feat)
+            continue
         x[b, :n, 0] = torch.sort(-24.0 * U(n))[0]
         x[b, :n, 1] = U(n)
         x[b, :n, 2] = torch.randint(0, 18, (n,), generator=g).float()

@@ -20,6 +20,10 @@ build-only flags wired in:
     --tie-store 1     the vital-sign windows come from a synthetic device-resident event store (synthetic.make_tie_store: None
                       hours at both ends, empty present hours, windows over 1000 events): the loader hands over (patient, hour,
                       length) triples, builder/data/tie_store.py plans them, ops.tie_windows gathers in front of the step
+    --vslt-type carryforward
+                      the hourly carry-forward table instead of TIE events: [B, 3, window_size, 16] host batches
+                      (synthetic.make_batch vslt_type="carryforward"), or with --tie-store 1 the same triples planned by
+                      TieEventStore.plan_hourly and gathered by ops.hourly_windows; ops.HourlyEmbedFn embeds the rows
     --report-store 1  the report embeddings come from a synthetic device-resident embedding store (synthetic.make_report_store):
                       the loader hands over one report index per sample, builder/data/report_store.py plans them,
                       ops.report_tokens gathers in front of the step, in the model's compute type
@@ -91,10 +95,12 @@ def synthetic_loader(args, n_iters: int, rank: int, epoch: int, tie_store=None, 
     multi = int(args.multiimages)
     B = int(args.batch_size if batch_size is None else batch_size)
     epoch_seed = seed_base + 7919 * rank + 104729 * epoch
+    hourly = args.vslt_type == "carryforward"
     for it in range(n_iters):
-        bt = make_batch(1234 + epoch_seed + it, B, int(args.TIE_len), ragged=True,
+        bt = make_batch(1234 + epoch_seed + it, B, int(args.window_size if hourly else args.TIE_len), ragged=True,
                         missing_mode="mixed" if "missing" in args.modality_inclusion else "none", multiimages=multi,
-                        img_size=int(args.image_size), n_images=int(getattr(args, "n_images", 3)))
+                        img_size=int(args.image_size), n_images=int(getattr(args, "n_images", 3)),
+                        vslt_type="carryforward" if hourly else "TIE", n_feat=len(args.vitalsign_labtest))
         static = torch.stack([bt["gen"], bt["age"]], 1)
         if int(getattr(args, "raw_images", 0)) in (1, 2, 3):
             from .builder.data.cxr_transform import collate_raw_cxr, transform_from_args
@@ -118,9 +124,13 @@ def synthetic_loader(args, n_iters: int, rank: int, epoch: int, tie_store=None, 
                 triples = [sweep[(it * B + j) % len(sweep)] for j in range(B)]
             else:
                 random.seed(977 + epoch_seed + it)
-                ds = StoreWindowDataset(tie_store)
+                ds = StoreWindowDataset(tie_store, int(args.window_size))
                 triples = [ds[random.randrange(len(ds))] for _ in range(B)]
-            wb = tie_store.plan(triples, int(args.TIE_len), int(args.realtime), "train-missing" in args.modality_inclusion)
+            if hourly:          # the hourly table of the same windows (ops.hourly_windows gathers it in front of the step)
+                wb = tie_store.plan_hourly(triples, int(args.window_size), None, int(args.realtime),
+                                           "train-missing" in args.modality_inclusion)
+            else:
+                wb = tie_store.plan(triples, int(args.TIE_len), int(args.realtime), "train-missing" in args.modality_inclusion)
             bt["x"], static, bt["input_lengths"] = wb, wb.static, wb.input_lengths
             if int(args.realtime) == 1:
                 bt["txt_time"] = wb.txt_time
@@ -244,7 +254,7 @@ def main(argv=None):
         logger = _Logger(DeviceEvaluator(args, device, val_iters * val_bs * int(args.output_dim)))
         if tie_store is not None:
             from .builder.data.tie_store import StoreWindowSweep
-            sweep = StoreWindowSweep(tie_store)
+            sweep = StoreWindowSweep(tie_store, int(args.window_size))
     model.train()                                                                                    # 2_train.py:128
     iteration = 0
     for epoch in range(1, int(args.epochs) + 1):

@@ -2,8 +2,8 @@
 
 Each switch chooses the order in which independent launches are issued, or which of two launch sequences meant to be equivalent
 runs.  The defaults below are what the tests and bench.py run, and the only settings they run: no test reads or sets one of these
-attributes.  The other settings are exercised only through ``tools/dbg/ab_patch.py`` (and the tools/dbg probes that flip one), so
-treat a non-default setting as unverified until such a run has compared it.  Each default is the faster setting as measured on
+attributes (HIP_HOURLY_EMBED excepted: its other setting is the reference's own torch chain, and a test runs both).  The other
+settings are exercised only through ``tools/dbg/ab_patch.py`` (and the tools/dbg probes that flip one), so treat a non-default setting as unverified until such a run has compared it.  Each default is the faster setting as measured on
 MI355X -- the measurement is named beside it and lives in DESIGN.md section 9 ("Built, measured, not kept").  They are module
 attributes so that ab_patch.py can flip one and measure both settings on one machine in one session (machines differ by up to
 5 %: an A/B across two sessions says nothing); product code reads them at call time, nothing else writes them.
@@ -42,3 +42,8 @@ FUSED_INPUT_TAIL = True
 # touched rows written into the flat gradient) instead of F.embedding + cast and embedding_dense_backward + AccumulateGrad (a dense
 # [30000, 256] gradient built from zero and added: ~90 MB of traffic).  Forward bits are equal; profiles/token_embed.txt.
 HIP_TOKEN_EMBED = True
+# tri_mbt_vsltcls (--vslt-type carryforward): the hourly table's Linear(16, 256) -> LayerNorm -> ReLU as ops.HourlyEmbedFn (one
+# launch forward, two backward, gradients into the flat buffer) instead of the torch chain (about ten launches each way plus four
+# accumulations).  The one switch BOTH of whose settings the tests run (tests/test_carryforward_model_gpu.py): off is the torch
+# chain the reference defines.  profiles/carryforward.txt.
+HIP_HOURLY_EMBED = True

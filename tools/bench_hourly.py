@@ -1,0 +1,189 @@
+"""Times of the hourly carry-forward path (--vslt-type carryforward: builder/data/tie_store.py plan_hourly, csrc/tie_store.hip,
+csrc/elementwise.hip) on one MI355X against what it replaces: the figures of profiles/carryforward.txt.
+
+    python tools/bench_hourly.py [--batch 64] [--rounds 20] [--steps 20] [--out FILE]
+
+At B 64, W 24, F 16, bf16, on synthetic.make_tie_store: mtmp_hourly_window_gather alone (``tables=``: the descriptor already on the
+device); ops.hourly_windows against the host path of the same windows (numpy slice, pad to [B, 3, 24, 16], ``.half().float()`` of
+plane 0, upload); ops.HourlyEmbedFn forward + backward against the torch chain Linear -> LayerNorm -> ReLU -> cast with the same
+gradient hand-over; the training step of ``train.py --vslt-type carryforward --tie-store 1 --hip-graph 1`` (6 layers) with
+tuning.HIP_HOURLY_EMBED on and off.  Device events (wall time around a synchronise for the two host paths), warm-up, and the two
+versions of every pair alternating in one process; per version the median and the min..max of its repeats, so that a difference
+can be read against the spread.  Needs a GPU; there is no fallback."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def pick_windows(store, B, rng):
+    w = []
+    while len(w) < B:
+        p = int(rng.integers(store.n_patients))
+        a, b = int(store.hour_ptr[p]), int(store.hour_ptr[p + 1])
+        key = int(rng.integers(0, b - a))
+        L = int(rng.integers(1, min(key + 1, 24) + 1))
+        if store.present[a + key - L + 1:a + key + 1].any():
+            w.append((p, key, L))
+    return np.asarray(w, np.int64)
+
+
+def device_us(fn, reps=10):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return 1e3 * e0.elapsed_time(e1) / reps
+
+
+def wall_us(fn):
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return 1e6 * (time.perf_counter() - t)
+
+
+def alternate(fa, fb, rounds, timer):
+    """rounds x (a, b), after a warm-up of both; returns the two lists of times"""
+    for _ in range(3):
+        timer(fa), timer(fb)
+    ta, tb = [], []
+    for _ in range(rounds):
+        ta.append(timer(fa))
+        tb.append(timer(fb))
+    return ta, tb
+
+
+def fmt(ts, unit="us"):
+    s = sorted(ts)
+    d = 3 if unit == "ms" else 1
+    return f"median {s[len(s) // 2]:.{d}f} {unit} (min {s[0]:.{d}f}, max {s[-1]:.{d}f}, {len(s)} repeats)"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--rounds", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from medical_tri_modal_pilot_amd import ops, synthetic, tuning
+    from medical_tri_modal_pilot_amd.builder.trainer import get_trainer
+    from medical_tri_modal_pilot_amd.builder.utils.cosine_annealing_with_warmup_v2 import CosineAnnealingWarmupRestarts
+    from medical_tri_modal_pilot_amd.control.config import build_parser
+    from medical_tri_modal_pilot_amd.train import _Logger, build_training
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+    say("command: python tools/bench_hourly.py " + " ".join(sys.argv[1:]))
+    B, W, F, dt = a.batch, 24, 16, torch.bfloat16
+    store = synthetic.make_tie_store(4099, 64).to(dev)
+    wins = pick_windows(store, B, np.random.default_rng(3))
+    batch = store.plan_hourly(wins, W, None, 1)
+    cols = [f for f in range(18) if batch.keep_bits >> f & 1]
+    say(f"store: {store.n_patients} patients, {store.n_hours} patient-hours, norm {store.norm.nbytes} bytes; batch B {B}, W {W}, F {F}, "
+        f"lengths {int(batch.input_lengths.min())}..{int(batch.input_lengths.max())}")
+
+    # ---- 1. the gather launch alone
+    desc = batch.descriptor().to(dev)
+    out = torch.empty(B, W, F, device=dev)
+    for _ in range(3):
+        ops.hourly_windows(batch, dev, out=out, tables=desc)
+    ts = [device_us(lambda: ops.hourly_windows(batch, dev, out=out, tables=desc)) for _ in range(a.rounds)]
+    say(f"mtmp_hourly_window_gather alone (descriptor on the device, 10 launches back to back per repeat): {fmt(ts)} per launch")
+
+    # ---- 2. ops.hourly_windows against the host path of the same windows
+    def host_path():
+        x = np.zeros((B, 3, W, F), np.float32)
+        for b, (p, key, L) in enumerate(wins.tolist()):
+            r0 = int(store.hour_ptr[p]) + key - L + 1
+            x[b, 0, :L] = store.norm[r0:r0 + L][:, cols]
+        t = torch.from_numpy(x).permute(1, 0, 2, 3)
+        return t[0].half().float().to(dev, non_blocking=True)
+    assert torch.equal(host_path(), ops.hourly_windows(batch, dev))
+    ta, tb = alternate(lambda: ops.hourly_windows(batch, dev), host_path, a.rounds, wall_us)
+    say(f"ops.hourly_windows (descriptor copy + launch + synchronise, wall): {fmt(ta)}")
+    say(f"host path (numpy slice, pad to [B, 3, {W}, {F}], .half().float(), upload + synchronise, wall): {fmt(tb)}; results are equal")
+    tp = []
+    for _ in range(a.rounds):
+        t = time.perf_counter()
+        store.plan_hourly(wins, W, None, 1)
+        tp.append(1e6 * (time.perf_counter() - t))
+    say(f"store.plan_hourly (host): {fmt(tp)} per batch")
+
+    # ---- 3. the embedding, forward + backward, against the torch chain
+    g = torch.Generator().manual_seed(1)
+    x = ops.hourly_windows(batch, dev)
+    prm = [(torch.randn(256, F, generator=g) * 0.4), 0.05 * torch.randn(256, generator=g), 1 + 0.1 * torch.randn(256, generator=g),
+           0.1 * torch.randn(256, generator=g)]
+    pa = [q.clone().to(dev).requires_grad_() for q in prm]
+    pb = [q.clone().to(dev).requires_grad_() for q in prm]
+    dy = torch.randn(B, W, 256, generator=g).to(dev).to(dt)
+
+    def hip_chain():
+        for q in pa:
+            q.grad = None
+        ops.HourlyEmbedFn.apply(x, *pa, dt).backward(dy)
+
+    def torch_chain():
+        for q in pb:
+            q.grad = None
+        torch.relu(torch.nn.functional.layer_norm(torch.nn.functional.linear(x, pb[0], pb[1]), (256,), pb[2], pb[3])).to(dt).backward(dy)
+    ta, tb = alternate(hip_chain, torch_chain, a.rounds, device_us)
+    err = max(float((u.grad - v.grad).abs().max() / v.grad.abs().max()) for u, v in zip(pa, pb))
+    say(f"ops.HourlyEmbedFn forward + backward, n = {B * W} rows (3 kernel launches + the gradient transpose): {fmt(ta)}")
+    say(f"torch chain forward + backward (Linear, LayerNorm, ReLU, cast; autograd): {fmt(tb)}; largest relative gradient difference {err:.1e}")
+
+    # ---- 4. the training step, switch on and off
+    argv = ["--input-types", "vslt_img_txt", "--model", "tri_mbt_vsltcls", "--modality-inclusion", "train-missing_test-missing",
+            "--batch-size", str(B), "--transformer-num-layers", "6", "--vslt-type", "carryforward", "--imgtxt-time", "1",
+            "--mbt-only-vslt", "1", "--compute-dtype", "bf16", "--hip-graph", "1", "--synthetic", "1"]
+    bt = synthetic.make_batch(99, B, W, missing_mode="none", vslt_type="carryforward")
+    runs = {}
+    for on in (True, False):
+        torch.manual_seed(0)
+        args = build_parser().parse_args(argv)
+        model, opt, crit = build_training(args, dev, False)
+        model.train()
+        sched = CosineAnnealingWarmupRestarts(opt, first_cycle_steps=args.t_0 * 100, cycle_mult=args.t_mult, max_lr=args.lr_init * 8,
+                                              min_lr=1e-6, warmup_steps=args.t_up * 100, gamma=args.gamma)
+        runs[on] = dict(args=args, model=model, opt=opt, crit=crit, sched=sched, it=0, loss=None)
+
+    def steps(on):
+        r = runs[on]
+        tuning.HIP_HOURLY_EMBED = on                     # read by forward(): frozen into the graph at its capture
+        for _ in range(a.steps):
+            r["it"] += 1
+            _, r["loss"] = get_trainer(args=r["args"], iteration=r["it"], x=batch, static=batch.static,
+                                       input_lengths=batch.input_lengths, y=bt["y"], output_lengths=None, model=r["model"],
+                                       logger=_Logger(), device=dev, scheduler=r["sched"], optimizer=r["opt"], criterion=r["crit"],
+                                       x_txt=bt["txt"], x_img=bt["img"], txt_lengths=bt["txt_lengths"],
+                                       imgtxt_time=(bt["img_time"], batch.txt_time), scaler=None, missing=bt["missing"],
+                                       flow_type="train", reports_tokens=None, reports_lengths=None, criterion_aux=(None, None))
+    timer = lambda fn: wall_us(fn) / 1e3 / a.steps
+    ta, tb = alternate(lambda: steps(True), lambda: steps(False), max(6, a.rounds // 2), timer)
+    tuning.HIP_HOURLY_EMBED = True
+    for on, ts_ in ((True, ta), (False, tb)):
+        st = runs[on]["model"]._mtmp_graph_step.stats()
+        say(f"training step, HIP_HOURLY_EMBED {'on ' if on else 'off'} (6 layers, B {B}, bf16, hipGraph: {st['captures']} capture, "
+            f"{st['replays']} replays; {a.steps} steps per repeat, wall / steps): {fmt(ts_, 'ms')}; last loss {runs[on]['loss']:.5f}")
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
