@@ -30,6 +30,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from . import resolve_device
 from .jpeg import (DEFAULT_SUBSEQ_BITS, JPG_AC, JPG_BPR, JPG_COEF, JPG_DC, JPG_DST, JPG_H, JPG_NBLK, JPG_NSEG, JPG_QT, JPG_RI,
                    JPG_SEG0, JPG_STREAM, JPG_W, JPG_WORDS, MAX_STAGE_BYTES, MAX_SUBSEQ, huff_table_words, parse_jpeg)
 
@@ -219,9 +220,7 @@ class CxrStore:
         """Upload streams, segment rows and tables, build the sync table on the device (mtmp_jpeg_sync_points, chunk by chunk),
         read the status words back ONCE.  An image whose stream does not yield its blocks is refused by name, and the store stays
         on the host."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = resolve_device(device)
         if device == self.device:
             return self
         if device.type != "cuda":

@@ -14,6 +14,8 @@ rounding the bf16 build's projection applies to its input anyway.  The gather co
 import numpy as np
 import torch
 
+from . import resolve_device
+
 DESC_WORDS = 2      # int64 words per sample of the kernel's descriptor (include/mtmp.h, mtmp_report_gather): first row, rows
 
 
@@ -24,33 +26,91 @@ def report_wanted(args, file_name: str) -> bool:
                  or ('test-missing' in args.modality_inclusion and "txt" in args.input_types)) and ("txt1" in file_name))
 
 
-class ReportBatch:
-    """The host plan of a batch of reports: everything but the embeddings.  ``ops.report_tokens`` turns it into the
-    ``[B, max_tokens, width]`` tensor on the device; the lengths and the missing flags are here without a device sync."""
+class _ReportBatch:
+    """What the report plans share.  A subclass declares ``berttype`` (the ``--berttype`` of the models that read it), ``holds``
+    (its noun in the trainer's messages), ``model_lengths`` (the attribute the model's key mask reads) and ``gather`` (the one launch
+    that makes the device tensor): the trainer's text input is driven by these four."""
 
     def __init__(self, store, report_idx, first_token, n_tokens, txt_lengths, missing):
         self.store, self.report_idx = store, report_idx
         self.first_token, self.n_tokens = first_token, n_tokens          # int64 [B] each; 0 tokens when missing
         self.txt_lengths, self.missing = txt_lengths, missing            # int64 [B]; float32 [B], column 2 of the loader's `missing`
-        self.max_tokens, self.width = store.max_tokens, store.width
 
     @property
     def batch_size(self) -> int:
         return int(self.txt_lengths.numel())
 
     def descriptor(self) -> torch.Tensor:
-        """int64 [B, DESC_WORDS]: the per-sample words of mtmp_report_gather."""
+        """int64 [B, DESC_WORDS]: the per-sample words of mtmp_report_gather and mtmp_report_ids_gather."""
         return torch.from_numpy(np.ascontiguousarray(np.stack([self.first_token, self.n_tokens], axis=1).astype(np.int64)))
 
 
-class ReportStore:
+class _ReportStoreBase:
+    """What the report stores share: ``tok_ptr`` int64 [R + 1] (host, numpy), the key -> index map, the plan on the counts."""
+
+    def __init__(self, tok_ptr, index):
+        self.tok_ptr, self._index = tok_ptr, index
+        self.device = torch.device("cpu")
+
+    @staticmethod
+    def _csr(counts, rows, empty):
+        """per-report arrays -> (tok_ptr, their concatenation; ``empty`` without a report)"""
+        tok_ptr = np.zeros(len(counts) + 1, np.int64)
+        np.cumsum(np.asarray(counts, np.int64), out=tok_ptr[1:])
+        return tok_ptr, np.concatenate(rows, axis=0) if rows else empty
+
+    @property
+    def n_reports(self) -> int:
+        return int(self.tok_ptr.shape[0] - 1)
+
+    @property
+    def n_tokens(self) -> int:
+        return int(self.tok_ptr[-1])
+
+    def _resolve(self, report_idx, missing_comb):
+        """The text branch's control flow on the counts alone, vectorised over the batch -> (report index, first row, rows, missing)
+        of every sample; no embedding and no id is touched."""
+        idx = np.asarray(report_idx)
+        if idx.ndim != 1 or idx.shape[0] < 1 or idx.dtype.kind not in "iu":
+            raise ValueError(f"plan: report_idx must be an integer array [B >= 1], got {idx.dtype} {idx.shape}")
+        idx = idx.astype(np.int64)
+        if (idx >= self.n_reports).any():
+            b = int(np.flatnonzero(idx >= self.n_reports)[0])
+            raise ValueError(f"plan: sample {b} names report {int(idx[b])}, the store holds 0..{self.n_reports - 1}")
+        have = idx >= 0
+        at = np.where(have, idx, 0)
+        first = self.tok_ptr[at] if self.n_reports else np.zeros_like(at)
+        n = (self.tok_ptr[at + 1] - first) if self.n_reports else np.zeros_like(at)
+        miss = ~have | (n == 0)
+        if missing_comb is not None:
+            mc = np.broadcast_to(np.asarray(missing_comb), idx.shape)
+            miss = miss | (mc == 1) | (mc == 3)
+        n = np.where(miss, 0, n).astype(np.int64)
+        first = np.where(miss, 0, first).astype(np.int64)
+        return idx, first, n, miss
+
+
+class ReportBatch(_ReportBatch):
+    """The host plan of a batch of reports: everything but the embeddings.  ``ops.report_tokens`` turns it into the
+    ``[B, max_tokens, width]`` tensor on the device; the lengths and the missing flags are here without a device sync."""
+    berttype, holds, model_lengths = "biobert", "BioBERT token embeddings", "txt_lengths"
+
+    def __init__(self, store, report_idx, first_token, n_tokens, txt_lengths, missing):
+        super().__init__(store, report_idx, first_token, n_tokens, txt_lengths, missing)
+        self.max_tokens, self.width = store.max_tokens, store.width
+
+    def gather(self, device, dtype):
+        from medical_tri_modal_pilot_amd import ops
+        return ops.report_tokens(self, device, dtype)
+
+
+class ReportStore(_ReportStoreBase):
     """CSR form of all reports' token embeddings: ``tok_ptr`` int64 [R + 1] (host, numpy) and ``emb`` [total_tokens, width]
     (a torch tensor: float32 on the host after building, float32 or bfloat16 wherever ``to`` put it)."""
 
     def __init__(self, tok_ptr, emb, index, width: int = 768, max_tokens: int = 128):
-        self.tok_ptr, self.emb, self._index = tok_ptr, emb, index
-        self.width, self.max_tokens = int(width), int(max_tokens)
-        self.device = torch.device("cpu")
+        super().__init__(tok_ptr, index)
+        self.emb, self.width, self.max_tokens = emb, int(width), int(max_tokens)
 
     # ------------------------------------------------------------------------------------------------------------ building
     @classmethod
@@ -84,9 +144,7 @@ class ReportStore:
             index[key] = len(counts)
             counts.append(a.shape[0])
             rows.append(a)
-        tok_ptr = np.zeros(len(counts) + 1, np.int64)
-        np.cumsum(np.asarray(counts, np.int64), out=tok_ptr[1:])
-        emb = np.concatenate(rows, axis=0) if rows else np.zeros((0, width), np.float32)
+        tok_ptr, emb = cls._csr(counts, rows, np.zeros((0, width), np.float32))
         return cls(tok_ptr, torch.from_numpy(np.ascontiguousarray(emb)), index, width, max_tokens)
 
     def index_of(self, text: str) -> int:
@@ -96,14 +154,6 @@ class ReportStore:
         return self._index.get(key, -1) if key else -1
 
     # ------------------------------------------------------------------------------------------------------------ placement
-    @property
-    def n_reports(self) -> int:
-        return int(self.tok_ptr.shape[0] - 1)
-
-    @property
-    def n_tokens(self) -> int:
-        return int(self.tok_ptr[-1])
-
     @property
     def dtype(self) -> torch.dtype:
         return self.emb.dtype
@@ -118,9 +168,7 @@ class ReportStore:
         embeddings move (no host copy is kept); ``tok_ptr`` stays on the host for ``plan``."""
         if dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"ReportStore.to: float32 or bfloat16, got {dtype}")
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = resolve_device(device)
         if device == self.device and dtype == self.emb.dtype:
             return self
         if self.device.type != "cpu" or self.emb.dtype != torch.float32:
@@ -135,23 +183,7 @@ class ReportStore:
         """``report_idx`` int [B]: the report of every sample, -1 where ``report_wanted`` is false or ``index_of`` gave -1;
         ``missing_comb``: the loader's per-sample (or one for all) modality combination, 1 and 3 drop the report (:2148-2149).
         The text branch's control flow on the token counts, vectorised over the batch."""
-        idx = np.asarray(report_idx)
-        if idx.ndim != 1 or idx.shape[0] < 1 or idx.dtype.kind not in "iu":
-            raise ValueError(f"plan: report_idx must be an integer array [B >= 1], got {idx.dtype} {idx.shape}")
-        idx = idx.astype(np.int64)
-        if (idx >= self.n_reports).any():
-            b = int(np.flatnonzero(idx >= self.n_reports)[0])
-            raise ValueError(f"plan: sample {b} names report {int(idx[b])}, the store holds 0..{self.n_reports - 1}")
-        have = idx >= 0
-        at = np.where(have, idx, 0)
-        first = self.tok_ptr[at] if self.n_reports else np.zeros_like(at)
-        n = (self.tok_ptr[at + 1] - first) if self.n_reports else np.zeros_like(at)
-        miss = ~have | (n == 0)
-        if missing_comb is not None:
-            mc = np.broadcast_to(np.asarray(missing_comb), idx.shape)
-            miss = miss | (mc == 1) | (mc == 3)
-        n = np.where(miss, 0, n).astype(np.int64)
-        first = np.where(miss, 0, first).astype(np.int64)
+        idx, first, n, miss = self._resolve(report_idx, missing_comb)
         return ReportBatch(self, idx, first, n, torch.from_numpy(n.copy()), torch.from_numpy(miss.astype(np.float32)))
 
 
@@ -168,35 +200,30 @@ class ReportStore:
 # ``tokens.append(3)`` change the list INSIDE ``txtDict``, so the same report grows by a BOS and an EOS on every read -- the store
 # reproduces a FIRST read, of a copy it made; (2) a key that ``txtDict`` lacks raises ``KeyError`` in ``__getitem__`` (the data set's
 # ``__init__`` drops such files beforehand, :300-308) -- here ``index_of`` gives -1 and the plan treats the sample as missing.
-class TokenReportBatch:
+class TokenReportBatch(_ReportBatch):
     """The host plan of a batch of token-id reports: everything but the ids.  ``ops.report_token_ids`` turns it into the int32
-    ``[B, max_length]`` tensor on the device; the lengths and the missing flags are here without a device sync."""
+    ``[B, max_length]`` tensor on the device; the lengths and the missing flags are here without a device sync.  ``txt_lengths`` is
+    the reference's textLength, UNTRIMMED; the model gets ``key_lengths``, so that its key count textLength + 2 never names more
+    rows than the stream has (the mask is the same: all L rows)."""
+    berttype, holds, model_lengths = "bert", "token ids", "key_lengths"
 
     def __init__(self, store, report_idx, first_token, n_tokens, txt_lengths, key_lengths, missing):
-        self.store, self.report_idx = store, report_idx
-        self.first_token, self.n_tokens = first_token, n_tokens          # int64 [B] each; 0 ids when missing
-        self.txt_lengths = txt_lengths                                   # int64 [B]: the reference's textLength, UNTRIMMED
+        super().__init__(store, report_idx, first_token, n_tokens, txt_lengths, missing)
         self.key_lengths = key_lengths                                   # int64 [B]: min(textLength, L - 2), what the model's mask reads
-        self.missing = missing                                           # float32 [B], column 2 of the loader's `missing`
         self.max_length = store.max_length
 
-    @property
-    def batch_size(self) -> int:
-        return int(self.txt_lengths.numel())
-
-    def descriptor(self) -> torch.Tensor:
-        """int64 [B, DESC_WORDS]: the per-sample words of mtmp_report_ids_gather."""
-        return torch.from_numpy(np.ascontiguousarray(np.stack([self.first_token, self.n_tokens], axis=1).astype(np.int64)))
+    def gather(self, device, dtype=None):
+        from medical_tri_modal_pilot_amd import ops
+        return ops.report_token_ids(self, device)
 
 
-class TokenReportStore:
+class TokenReportStore(_ReportStoreBase):
     """CSR form of all reports' token ids: ``tok_ptr`` int64 [R + 1] (host, numpy) and ``ids`` int32 [total] (a torch tensor: on
     the host after building, on the device after ``to``)."""
 
     def __init__(self, tok_ptr, ids, index, vocab: int = 30000, max_length: int = 128):
-        self.tok_ptr, self.ids, self._index = tok_ptr, ids, index
-        self.vocab, self.max_length = int(vocab), int(max_length)
-        self.device = torch.device("cpu")
+        super().__init__(tok_ptr, index)
+        self.ids, self.vocab, self.max_length = ids, int(vocab), int(max_length)
 
     @classmethod
     def from_mapping(cls, mapping, vocab: int = 30000, max_length: int = 128):
@@ -224,22 +251,12 @@ class TokenReportStore:
             index[k] = len(counts)
             counts.append(a.shape[0])
             rows.append(a.astype(np.int32))
-        tok_ptr = np.zeros(len(counts) + 1, np.int64)
-        np.cumsum(np.asarray(counts, np.int64), out=tok_ptr[1:])
-        ids = np.concatenate(rows) if rows else np.zeros(0, np.int32)
+        tok_ptr, ids = cls._csr(counts, rows, np.zeros(0, np.int32))
         return cls(tok_ptr, torch.from_numpy(np.ascontiguousarray(ids, np.int32)), index, vocab, max_length)
 
     def index_of(self, pat_id, chid) -> int:
         """index of the report ``txtDict[(int(pat_id), int(chid))]``; -1 for a key the store does not hold"""
         return self._index.get((int(pat_id), int(chid)), -1)
-
-    @property
-    def n_reports(self) -> int:
-        return int(self.tok_ptr.shape[0] - 1)
-
-    @property
-    def n_tokens(self) -> int:
-        return int(self.tok_ptr[-1])
 
     @property
     def nbytes(self) -> int:
@@ -248,9 +265,7 @@ class TokenReportStore:
 
     def to(self, device):
         """Upload the ids once (no host copy is kept); ``tok_ptr`` stays on the host for ``plan``."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = resolve_device(device)
         if device != self.device:
             self.ids = self.ids.to(device)
             self.device = self.ids.device
@@ -260,22 +275,6 @@ class TokenReportStore:
         """``report_idx`` int [B]: the report of every sample, -1 where ``report_wanted`` is false or ``index_of`` gave -1;
         ``missing_comb``: the loader's per-sample (or one for all) modality combination, 1 and 3 drop the report (:2159).
         The same control flow as ``ReportStore.plan``, on the id counts alone: no id is touched."""
-        idx = np.asarray(report_idx)
-        if idx.ndim != 1 or idx.shape[0] < 1 or idx.dtype.kind not in "iu":
-            raise ValueError(f"plan: report_idx must be an integer array [B >= 1], got {idx.dtype} {idx.shape}")
-        idx = idx.astype(np.int64)
-        if (idx >= self.n_reports).any():
-            b = int(np.flatnonzero(idx >= self.n_reports)[0])
-            raise ValueError(f"plan: sample {b} names report {int(idx[b])}, the store holds 0..{self.n_reports - 1}")
-        have = idx >= 0
-        at = np.where(have, idx, 0)
-        first = self.tok_ptr[at] if self.n_reports else np.zeros_like(at)
-        n = (self.tok_ptr[at + 1] - first) if self.n_reports else np.zeros_like(at)
-        miss = ~have | (n == 0)
-        if missing_comb is not None:
-            mc = np.broadcast_to(np.asarray(missing_comb), idx.shape)
-            miss = miss | (mc == 1) | (mc == 3)
-        n = np.where(miss, 0, n).astype(np.int64)
-        first = np.where(miss, 0, first).astype(np.int64)
+        idx, first, n, miss = self._resolve(report_idx, missing_comb)
         return TokenReportBatch(self, idx, first, n, torch.from_numpy(n.copy()),
                                 torch.from_numpy(np.minimum(n, self.max_length - 2)), torch.from_numpy(miss.astype(np.float32)))

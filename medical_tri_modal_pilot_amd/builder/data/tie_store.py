@@ -30,6 +30,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
+from . import resolve_device
+
 N_FEAT = 18
 DESC_WORDS = 8      # int64 words per sample of the kernel's descriptor (include/mtmp.h, mtmp_tie_window_gather)
 (DESC_FIRST_EVENT, DESC_N_EVENTS, DESC_INIT_HOUR, DESC_FIRST_HOUR, DESC_N_HOURS, DESC_MASK, DESC_T0, DESC_KEY) = range(DESC_WORDS)
@@ -218,9 +220,7 @@ class TieEventStore:
 
     def to(self, device):
         """Upload once.  The events move (no host copy is kept); the hour-level arrays stay on the host as well."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = resolve_device(device)
         if device.type == "cpu" or device == self.device:
             return self
         self.ev_time, self.ev_val, self.ev_feat = (t.to(device) for t in (self.ev_time, self.ev_val, self.ev_feat))

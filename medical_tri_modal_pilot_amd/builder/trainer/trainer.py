@@ -18,7 +18,7 @@ import torch
 from medical_tri_modal_pilot_amd import ops, tuning
 from medical_tri_modal_pilot_amd.builder.data.cxr_transform import RawCxrBatch
 from medical_tri_modal_pilot_amd.builder.data.tie_dataset import PackedTie, PackedTieBatch
-from medical_tri_modal_pilot_amd.builder.data.report_store import ReportBatch, TokenReportBatch
+from medical_tri_modal_pilot_amd.builder.data.report_store import _ReportBatch
 from medical_tri_modal_pilot_amd.builder.data.tie_store import HourlyWindowBatch, TieWindowBatch
 
 GRAPH_LEN_BUCKET = 128
@@ -215,12 +215,85 @@ class StepInputs:
         return t
 
 
+def _vslt_input(args, train_x, input_lengths, model, device, graphed, fp16_round):
+    """The vital-sign input -> (data, cu_seqlens, t_pad); the last two are None unless the model gets a PackedTie.  The store
+    batches (TieWindowBatch, HourlyWindowBatch) are host plans: their one gather launch runs here, eagerly in front of the step,
+    fp16 rounding included, and fills the captured graph's static input; the lengths are the plan's, nothing waits for the device."""
+    if isinstance(train_x, HourlyWindowBatch):        # a fixed shape: no length buckets
+        if args.vslt_type != "carryforward":
+            raise ValueError(f"a HourlyWindowBatch holds hourly carry-forward tables; a model built with --vslt-type {args.vslt_type} "
+                             "reads events (TieEventStore.plan)")
+        if train_x.n_feat != len(args.vitalsign_labtest):
+            raise ValueError(f"the HourlyWindowBatch keeps {train_x.n_feat} columns, --vitalsign-labtest names "
+                             f"{len(args.vitalsign_labtest)}")
+        if train_x.window_size != int(args.window_size):
+            raise ValueError(f"the HourlyWindowBatch has window_size {train_x.window_size}, --window-size is {args.window_size}")
+        return ops.hourly_windows(train_x, device, round_fp16=True), None, None
+    if args.vslt_type == "carryforward":
+        if isinstance(train_x, (PackedTieBatch, TieWindowBatch)):
+            raise ValueError(f"a {type(train_x).__name__} holds TIE events; --vslt-type carryforward reads hourly tables "
+                             "(TieEventStore.plan_hourly)")
+        return train_x.permute(1, 0, 2, 3)[0].half().float().to(device, non_blocking=True), None, None
+    if not isinstance(train_x, (PackedTieBatch, TieWindowBatch)):
+        # ragged trim, trainer.py:41-42 (at least one row: a batch of all-empty windows keeps one pad event behind kv_len --
+        # pad rows feed nothing -- instead of zero-length launches)
+        max_len = max(1, int(torch.max(input_lengths)))
+        if graphed:
+            max_len = graph_len_bucket(max_len, train_x.shape[1])
+        return fp16_round(train_x[:, :max_len, :], "data"), None, None                    # 2_train.py:164
+    # The events travel packed (builder/data, SURVEY 8 f-1), there is nothing to trim; the padded row count of the stream buffers
+    # is the batch maximum, bucketed for graph replays like the trim above.
+    packed = isinstance(train_x, PackedTieBatch)             # packed on the host; a TieWindowBatch is gathered here
+    max_len = int(torch.max(input_lengths)) if packed else max(1, train_x.max_len)
+    if graphed:
+        max_len = graph_len_bucket(max_len, int(args.TIE_len))
+    bucket = GRAPH_EVENT_BUCKET if graphed else 0
+    if packed:
+        pk = train_x.on_device(device, max_len, bucket)                                    # fp16 rounding inside
+    elif getattr(model, "takes_packed_tie", False):
+        # A model class says with ``takes_packed_tie = True`` that its forward accepts a PackedTie (TRI_MBT_VSLTCLS and the siblings
+        # derived from it, unless they override it): one launch writes what on_device above hands over, event bucket and zero tail
+        # included.  A class WITHOUT the attribute gets the padded tensor -- always correct, at the price of the pad rows.
+        pk = ops.tie_windows(train_x, device, max_len, bucket)
+    else:
+        return ops.tie_windows(train_x, device, max_len, padded=True), None, None
+    return pk.events, pk.cu_seqlens, pk.t_pad
+
+
+def _txt_input(args, x_txt, txt_lengths, model, device):
+    """The text input -> (x_txt on the device, the lengths the model gets, still where they were).  A report plan
+    (builder/data/report_store.py: ReportBatch, TokenReportBatch) says itself which ``--berttype`` reads it, what it holds, which
+    of its length vectors the model gets and which launch gathers it -- eagerly in front of the step, filling the captured graph's
+    static input.  The caller's lengths are checked against the plan's on the host: nothing waits for the device."""
+    if not isinstance(x_txt, _ReportBatch):
+        return x_txt.to(device, non_blocking=True), txt_lengths
+    who, berttype = type(x_txt).__name__, getattr(args, "berttype", "biobert")
+    if berttype != x_txt.berttype:
+        reads = next((c.holds for c in _ReportBatch.__subclasses__() if c.berttype == berttype), "another form of report")
+        raise ValueError(f"a {who} holds {x_txt.holds}; a model built with --berttype {berttype} reads {reads}")
+    if txt_lengths is not None:
+        if torch.is_tensor(txt_lengths) and txt_lengths.is_cuda:          # comparing it would make the host wait for the device
+            raise ValueError(f"with a {who}, txt_lengths is None or a host tensor (the plan's own lengths are on the host)")
+        if not torch.equal(torch.as_tensor(txt_lengths).long(), x_txt.txt_lengths):
+            raise ValueError(f"txt_lengths differs from the lengths of the {who}'s plan (pass None, or the plan's own)")
+    return x_txt.gather(device, getattr(model, "compute_dtype", torch.float32)), getattr(x_txt, x_txt.model_lengths)
+
+
+def _img_input(x_img, device):
+    """The image input on the device.  A RawCxrBatch holds uint8 images as decoded (builder/data/cxr_transform.py): the loader's
+    equalize / resize / affine / crop chain runs here, eagerly in front of the step -- source sizes vary from batch to batch, so it
+    stays outside the captured graph, whose static image input it fills like a float batch from the host would."""
+    on_device = x_img.to(device, non_blocking=True)
+    return ops.cxr_prepare(on_device) if isinstance(x_img, RawCxrBatch) else on_device
+
+
 def prepare_step_inputs(args, train_x, static_x, input_lengths, train_y, model, device, graphed, defer_ok, output_lengths=None,
                         x_img=None, x_txt=None, txt_lengths=None, imgtxt_time=None, missing=None) -> StepInputs:
     """The input side of one step, shared by missing_trainer (training and its test flow) and builder/trainer/validate.py: fp16
-    rounding, ragged trim and length buckets, PackedTieBatch / TieWindowBatch / HourlyWindowBatch / ReportBatch / TokenReportBatch / RawCxrBatch,
-    missing_to_num.  ``graphed``: the step will be replayed from a hipGraph (lengths are bucketed); ``defer_ok``: the fp16
-    rounding of device-resident fp32 tensors may ride on the copy into the graph's static buffers (StepInputs.deferred)."""
+    rounding, then _vslt_input, target / missing_to_num / static, _txt_input, _img_input -- the order of the launches, which is the
+    order the captured graphs' static inputs are filled in.  ``graphed``: the step will be replayed from a hipGraph (lengths are
+    bucketed); ``defer_ok``: the fp16 rounding of device-resident fp32 tensors may ride on the copy into the graph's static buffers
+    (StepInputs.deferred)."""
     img_time, txt_time = imgtxt_time
     # fp16 rounding of the event / time inputs (trainer.py:26-27, 2_train.py:164).  A device-resident fp32 tensor of a step
     # that will be replayed from a hipGraph is rounded by the copy into the graph's static buffers instead
@@ -233,120 +306,32 @@ def prepare_step_inputs(args, train_x, static_x, input_lengths, train_y, model, 
             deferred.add(key)
             return t
         return t.half().float().to(device, non_blocking=True)
-    img_time = fp16_round(img_time, "img_time")
-    txt_time = fp16_round(txt_time, "txt_time")
-    cu_seqlens = None
-    if isinstance(train_x, HourlyWindowBatch):
-        # Hourly carry-forward windows of the device-resident event store (builder/data/tie_store.py plan_hourly): the batch is its
-        # host plan, the [B, window_size, n_feat] table is gathered here, eagerly in front of the step like ops.tie_windows' events
-        # -- one launch, fp16 rounding included, that fills the captured graph's static input (a fixed shape: no length buckets).
-        # The lengths are the plan's: nothing waits for the device.
-        if args.vslt_type != "carryforward":
-            raise ValueError(f"a HourlyWindowBatch holds hourly carry-forward tables; a model built with --vslt-type {args.vslt_type} "
-                             "reads events (TieEventStore.plan)")
-        if train_x.n_feat != len(args.vitalsign_labtest):
-            raise ValueError(f"the HourlyWindowBatch keeps {train_x.n_feat} columns, --vitalsign-labtest names "
-                             f"{len(args.vitalsign_labtest)}")
-        if train_x.window_size != int(args.window_size):
-            raise ValueError(f"the HourlyWindowBatch has window_size {train_x.window_size}, --window-size is {args.window_size}")
-        data = ops.hourly_windows(train_x, device, round_fp16=True)
-    elif isinstance(train_x, (PackedTieBatch, TieWindowBatch)) and args.vslt_type == "carryforward":
-        raise ValueError(f"a {type(train_x).__name__} holds TIE events; --vslt-type carryforward reads hourly tables "
-                         "(TieEventStore.plan_hourly)")
-    elif isinstance(train_x, PackedTieBatch):
-        # Ragged batch (builder/data): the events travel packed, there is nothing to trim; the padded
-        # row count of the stream buffers is the batch maximum (bucketed for graph replays like the trim below).
-        max_len = int(torch.max(input_lengths))
-        if graphed:
-            max_len = graph_len_bucket(max_len, int(args.TIE_len))
-        pk = train_x.on_device(device, max_len, GRAPH_EVENT_BUCKET if graphed else 0)   # fp16 rounding inside
-        data, cu_seqlens, t_pad = pk.events, pk.cu_seqlens, pk.t_pad
-    elif isinstance(train_x, TieWindowBatch):
-        # Windows of the device-resident event store (builder/data/tie_store.py): the batch is its host plan, the events are
-        # gathered here, eagerly in front of the step like ops.cxr_prepare's images -- one launch that writes what on_device
-        # above hands over (fp16 rounding, event bucket and zero tail included) and fills the captured graph's static input.
-        # The lengths are the plan's: nothing waits for the device.  A model class says with ``takes_packed_tie = True`` that its
-        # forward accepts a PackedTie (TRI_MBT_VSLTCLS and the siblings derived from it, unless they override it); a class
-        # WITHOUT the attribute gets the padded tensor of the trim below -- always correct, at the price of the pad rows.
-        max_len = max(1, train_x.max_len)
-        if graphed:
-            max_len = graph_len_bucket(max_len, int(args.TIE_len))
-        if getattr(model, "takes_packed_tie", False):
-            pk = ops.tie_windows(train_x, device, max_len, GRAPH_EVENT_BUCKET if graphed else 0)
-            data, cu_seqlens, t_pad = pk.events, pk.cu_seqlens, pk.t_pad
-        else:
-            data = ops.tie_windows(train_x, device, max_len, padded=True)
-    elif args.vslt_type == "carryforward":
-        train_x = train_x.permute(1, 0, 2, 3)
-        data = train_x[0].half().float().to(device, non_blocking=True)
-    else:
-        # ragged trim, trainer.py:41-42 (at least one row: a batch of all-empty windows keeps one pad event behind kv_len --
-        # pad rows feed nothing -- instead of zero-length launches)
-        max_len = max(1, int(torch.max(input_lengths)))
-        if graphed:
-            max_len = graph_len_bucket(max_len, train_x.shape[1])
-        data = fp16_round(train_x[:, :max_len, :], "data")                    # 2_train.py:164
-    if "rmse" in args.auxiliary_loss_type:
-        final_target = train_y[0].float().to(device, non_blocking=True)
-    else:
-        final_target = train_y.float().to(device, non_blocking=True)
-    missing_num = _missing_ids(args, missing, device)
-    static_x = static_x.permute(1, 0)
-    age = static_x[1].float().to(device, non_blocking=True)
-    gender = static_x[0].float().to(device, non_blocking=True)
-    if isinstance(x_txt, ReportBatch):
-        # Reports of the device-resident embedding store (builder/data/report_store.py): the batch is its host plan, the token
-        # rows are gathered here, eagerly in front of the step like ops.cxr_prepare's images and ops.tie_windows' events -- one
-        # launch that writes the [B, 128, 768] tensor the loader would have padded on the host, in the model's compute type (the
-        # bf16 build's projection finds its input already cast), and fills the captured graph's static input.  The lengths are
-        # the plan's: nothing waits for the device.
-        if getattr(args, "berttype", "biobert") != "biobert":
-            raise ValueError("a ReportBatch holds BioBERT token embeddings; a model built with --berttype "
-                             f"{args.berttype} reads token ids")
-        if txt_lengths is not None:
-            if torch.is_tensor(txt_lengths) and txt_lengths.is_cuda:          # comparing it would make the host wait for the device
-                raise ValueError("with a ReportBatch, txt_lengths is None or a host tensor (the plan's own lengths are on the host)")
-            if not torch.equal(torch.as_tensor(txt_lengths).long(), x_txt.txt_lengths):
-                raise ValueError("txt_lengths differs from the lengths of the ReportBatch's plan (pass None, or the plan's own)")
-        txt_lengths = x_txt.txt_lengths
-        x_txt = ops.report_tokens(x_txt, device, getattr(model, "compute_dtype", torch.float32))
-    elif isinstance(x_txt, TokenReportBatch):
-        # Token-id reports of the device-resident store (--berttype bert): the same hand-over, the int32 [B, L] ids -- BOS, the
-        # report trimmed to L - 2 ids, EOS, zeros -- written by one launch in front of the step.  The caller's lengths are the
-        # reference's UNTRIMMED textLength and are checked against the plan's; the model gets key_lengths = min(textLength, L - 2),
-        # so that its key count textLength + 2 never names more rows than the stream has (the mask is the same: all L rows).
-        if getattr(args, "berttype", "biobert") != "bert":
-            raise ValueError("a TokenReportBatch holds token ids; a model built with --berttype "
-                             f"{getattr(args, 'berttype', 'biobert')} reads BioBERT token embeddings")
-        if txt_lengths is not None:
-            if torch.is_tensor(txt_lengths) and txt_lengths.is_cuda:          # comparing it would make the host wait for the device
-                raise ValueError("with a TokenReportBatch, txt_lengths is None or a host tensor (the plan's own lengths are on the host)")
-            if not torch.equal(torch.as_tensor(txt_lengths).long(), x_txt.txt_lengths):
-                raise ValueError("txt_lengths differs from the lengths of the TokenReportBatch's plan (pass None, or the plan's own)")
-        txt_lengths = x_txt.key_lengths
-        x_txt = ops.report_token_ids(x_txt, device)
-    else:
-        x_txt = x_txt.to(device, non_blocking=True)
-    if isinstance(x_img, RawCxrBatch):
-        # uint8 images as decoded (builder/data/cxr_transform.py): the loader's equalize / resize / affine / crop chain runs here,
-        # eagerly in front of the step -- source sizes vary from batch to batch, so it stays outside the captured graph, whose
-        # static image input it fills like a float batch from the host would.
-        x_img = ops.cxr_prepare(x_img.to(device, non_blocking=True))
-    else:
-        x_img = x_img.to(device, non_blocking=True)
-    input_lengths = input_lengths.to(device, non_blocking=True)
-    txt_lengths = txt_lengths.to(device, non_blocking=True)
-    feasible = None if output_lengths is None else output_lengths.type(torch.IntTensor).to(device, non_blocking=True)
-
-    packed_extra = {}
-    if cu_seqlens is not None:       # t_pad rides in the graph signature as the shape of an empty tensor
-        packed_extra = dict(cu_seqlens=cu_seqlens, t_pad_marker=torch.empty(t_pad, 0, device=device))
-
     s = StepInputs()
-    s.data, s.age, s.gender, s.input_lengths, s.x_txt, s.txt_lengths, s.x_img = data, age, gender, input_lengths, x_txt, txt_lengths, x_img
-    s.missing_num, s.img_time, s.txt_time, s.final_target, s.feasible = missing_num, img_time, txt_time, final_target, feasible
-    s.packed_extra, s.deferred = packed_extra, deferred
+    s.img_time, s.txt_time = fp16_round(img_time, "img_time"), fp16_round(txt_time, "txt_time")
+    s.data, cu_seqlens, t_pad = _vslt_input(args, train_x, input_lengths, model, device, graphed, fp16_round)
+    s.final_target = (train_y[0] if "rmse" in args.auxiliary_loss_type else train_y).float().to(device, non_blocking=True)
+    s.missing_num = _missing_ids(args, missing, device)
+    static_x = static_x.permute(1, 0)
+    s.age = static_x[1].float().to(device, non_blocking=True)
+    s.gender = static_x[0].float().to(device, non_blocking=True)
+    s.x_txt, txt_lengths = _txt_input(args, x_txt, txt_lengths, model, device)
+    s.x_img = _img_input(x_img, device)
+    s.input_lengths = input_lengths.to(device, non_blocking=True)
+    s.txt_lengths = txt_lengths.to(device, non_blocking=True)
+    s.feasible = None if output_lengths is None else output_lengths.type(torch.IntTensor).to(device, non_blocking=True)
+    # t_pad rides in the graph signature as the shape of an empty tensor
+    s.packed_extra = {} if cu_seqlens is None else dict(cu_seqlens=cu_seqlens, t_pad_marker=torch.empty(t_pad, 0, device=device))
+    s.deferred = deferred
     return s
+
+
+def _run_model(model, t, feasible, flow_type, reports_tokens=None, reports_lengths=None):
+    """THE call of the model on the named tensors of StepInputs.tensors() / of a captured step (missing_trainer and
+    builder/trainer/validate.py): the PackedTie is put together again when ``cu_seqlens`` is there.  Returns the squeezed logits."""
+    x_in = t["data"] if "cu_seqlens" not in t else PackedTie(t["data"], t["cu_seqlens"], t["t_pad_marker"].shape[0])
+    out, _, _ = model(x_in, None, None, None, None, t["age"], t["gender"], t["input_lengths"], t["x_txt"], t["txt_lengths"],
+                      t["x_img"], t["missing_num"], feasible, t["img_time"], t["txt_time"], flow_type, reports_tokens, reports_lengths)
+    return out.squeeze()
 
 
 def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, model, logger, device,
@@ -365,13 +350,7 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
         red._mtmp_streams_set = True
 
     def run_model(t=None):
-        if t is None:
-            t = inp.tensors()
-        x_in = t["data"] if "cu_seqlens" not in t else PackedTie(t["data"], t["cu_seqlens"], t["t_pad_marker"].shape[0])
-        out, _, _ = model(x_in, None, None, None, None, t["age"], t["gender"], t["input_lengths"], t["x_txt"],
-                          t["txt_lengths"], t["x_img"], t["missing_num"], feasible, t["img_time"], t["txt_time"],
-                          flow_type, reports_tokens, reports_lengths)
-        return out.squeeze()
+        return _run_model(model, inp.tensors() if t is None else t, feasible, flow_type, reports_tokens, reports_lengths)
 
     if flow_type == "train" and _use_graph(args, flow_type, device, optimizer, scaler) and feasible is None:
         from medical_tri_modal_pilot_amd.graph import GraphedTrainStep

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from medical_tri_modal_pilot_amd import ops
+from medical_tri_modal_pilot_amd.builder.data import resolve_device
 
 METRIC_NAMES = ("auroc", "ap", "f1", "best_f1", "loss", "n", "n_pos", "status")
 
@@ -27,11 +28,9 @@ class DeviceEvaluator(object):
         if "rmse" in getattr(args, "auxiliary_loss_type", ""):
             raise ValueError("DeviceEvaluator: 'rmse' in args.auxiliary_loss_type -- the rmse list is not kept on the device "
                              "(the trainer never hands one over); keep builder.utils.metrics.Evaluator for that")
-        device = torch.device(device)
+        device = resolve_device(device)
         if device.type != "cuda":
             raise RuntimeError(f"DeviceEvaluator runs on an MI355X only (device {device}); there is no CPU fallback")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
         capacity = int(capacity)
         if not 1 <= capacity <= ops.EVAL_MAX_CAPACITY:
             raise ValueError(f"DeviceEvaluator: capacity {capacity} is not in 1 .. {ops.EVAL_MAX_CAPACITY} (2^24)")

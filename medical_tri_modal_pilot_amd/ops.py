@@ -579,6 +579,34 @@ def _cxr_prepare_random(raw):
     return out
 
 
+# ---- the gathers of the device-resident input stores: one preamble, then one launch each ------------------------------------
+def _store_gather(name, batch, device, kind, specs, tables, shape, dtype, out):
+    """What ``tie_windows``, ``hourly_windows``, ``report_tokens`` and ``report_token_ids`` do before their launch.  ``specs``: one
+    ``(label, host, shape, dtype)`` per table the kernel reads, ``host()`` being the plan's host tensor; ``tables``: those tensors
+    already on the device, or None to upload them (small non-blocking copies, no device value is waited for).  Refuses a device
+    that is no GPU, a store that is not where the tables are, and a table or an ``out`` of another shape, type or layout -- all on
+    the host, before anything is launched.  Everything is allocated and entered on the TABLES' device, so that "cuda" and "cuda:0"
+    behave alike: returns ``(tables, out)``, and the caller launches under ``torch.cuda.device(out.device)``."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"medical_tri_modal_pilot_amd ops run on an MI355X only ({name} on {device}); there is no CPU fallback")
+    if tables is None:
+        tables = [spec[1]().to(device, non_blocking=True) for spec in specs]
+    dev = tables[0].device
+    if batch.store.device != dev:
+        raise RuntimeError(f"{name}: the {kind} store is on {batch.store.device}, not on {dev}: call store.to(device) once")
+    if len(tables) != len(specs):
+        raise ValueError(f"{name}: tables holds {len(tables)} tensors, want {', '.join(spec[0] for spec in specs)}")
+    for t, spec in zip(tables, specs):
+        if tuple(t.shape) != spec[2] or t.dtype != spec[3] or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name}: the {spec[0]} must be a contiguous {str(spec[3])[6:]} tensor {spec[2]} on {dev}")
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"{name}: out must be a contiguous {str(dtype)[6:]} tensor {shape} on {dev}")
+    return tables, out
+
+
 # ---- TIE event windows from the device-resident event store (csrc/tie_store.hip) -----------------------------------------
 def tie_windows(batch, device, t_pad: int, bucket: int = 0, padded: bool = False, round_fp16: bool = True, out=None, tables=None):
     """TieWindowBatch (builder/data/tie_store.py: the host plan of a batch of (patient, selected_key, rand_length) windows) ->
@@ -590,28 +618,14 @@ def tie_windows(batch, device, t_pad: int, bucket: int = 0, padded: bool = False
     (descriptor, cu_seqlens), no device value is waited for.  out: an event buffer to write into (tests); tables: the
     descriptor and cu_seqlens already on the device (tools/bench_tie_store.py times the launch alone)."""
     from .builder.data.tie_dataset import PackedTie
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"medical_tri_modal_pilot_amd ops run on an MI355X only (tie_windows on {device}); there is no CPU fallback")
-    store = batch.store
+    store, B, total = batch.store, batch.batch_size, batch.total_rows
+    shape = (B, int(t_pad), 3) if padded else (-(-total // bucket) * bucket if bucket > 0 else total, 3)
+    specs = (("descriptor", batch.descriptor, (B, 8), torch.int64), ("cu_seqlens", lambda: batch.cu_seqlens, (B + 1,), torch.int32))
+    (desc, cu), out = _store_gather("tie_windows", batch, device, "event", specs, tables, shape, torch.float32, out)
     dv = store.device_arrays()
-    B, max_len, total = batch.batch_size, batch.max_len, batch.total_rows
-    if tables is None:
-        tables = (batch.descriptor().to(device, non_blocking=True), batch.cu_seqlens.to(device, non_blocking=True))
-    desc, cu = tables
-    if store.device != desc.device:
-        raise RuntimeError(f"tie_windows: the event store is on {store.device}, not on {desc.device}: call store.to(device) once")
-    if padded:
-        shape = (B, int(t_pad), 3)
-    else:
-        shape = (-(-total // bucket) * bucket if bucket > 0 else total, 3)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != desc.device:
-        raise ValueError(f"tie_windows: out must be a contiguous float32 tensor {shape} on {device}")
-    with torch.cuda.device(device), kernel_marks("tie_window_gather", B):
+    with torch.cuda.device(out.device), kernel_marks("tie_window_gather", B):
         call("mtmp_tie_window_gather", _p(store.ev_time), _p(store.ev_val), _p(store.ev_feat), _p(dv["norm"]), _p(dv["delta"]),
-             _p(dv["hour_min"]), store.n_events, store.n_hours, _p(desc), _p(cu), _p(out), B, max_len, int(t_pad), total,
+             _p(dv["hour_min"]), store.n_events, store.n_hours, _p(desc), _p(cu), _p(out), B, batch.max_len, int(t_pad), total,
              0 if padded else shape[0], int(padded), batch.realtime, int(round_fp16), _stream())
     return out if padded else PackedTie(out, cu, int(t_pad))
 
@@ -625,24 +639,12 @@ def hourly_windows(batch, device, round_fp16: bool = True, out=None, tables=None
     ``.half().float()``.  The store must be on ``device`` (``store.to(device)``, once).  One small host-to-device copy (the
     descriptor), no device value is waited for.  out: a buffer to write into; tables: the descriptor already on the device
     (tools/bench_hourly.py times the launch alone, the tests hand over descriptors the plan would never make)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"medical_tri_modal_pilot_amd ops run on an MI355X only (hourly_windows on {device}); there is no CPU fallback")
-    store = batch.store
-    dv = store.device_arrays()
-    B, W, F = batch.batch_size, batch.window_size, batch.n_feat
-    desc = batch.descriptor().to(device, non_blocking=True) if tables is None else tables
-    if store.device != desc.device:
-        raise RuntimeError(f"hourly_windows: the event store is on {store.device}, not on {desc.device}: call store.to(device) once")
-    if tuple(desc.shape) != (B, 2) or desc.dtype != torch.int64 or not desc.is_contiguous():
-        raise ValueError(f"hourly_windows: the descriptor must be a contiguous int64 tensor {(B, 2)}")
-    if out is None:
-        out = torch.empty((B, W, F), dtype=torch.float32, device=desc.device)
-    elif tuple(out.shape) != (B, W, F) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != desc.device:
-        raise ValueError(f"hourly_windows: out must be a contiguous float32 tensor {(B, W, F)} on {device}")
-    with torch.cuda.device(desc.device), kernel_marks("hourly_window_gather", B):
-        call("mtmp_hourly_window_gather", _p(dv["norm"]), store.n_hours, _p(desc), _p(out), B, W, F, batch.keep_bits,
-             int(round_fp16), _stream())
+    store, B, W, F = batch.store, batch.batch_size, batch.window_size, batch.n_feat
+    (desc,), out = _store_gather("hourly_windows", batch, device, "event", (("descriptor", batch.descriptor, (B, 2), torch.int64),),
+                                 tables if tables is None else (tables,), (B, W, F), torch.float32, out)
+    with torch.cuda.device(out.device), kernel_marks("hourly_window_gather", B):
+        call("mtmp_hourly_window_gather", _p(store.device_arrays()["norm"]), store.n_hours, _p(desc), _p(out), B, W, F,
+             batch.keep_bits, int(round_fp16), _stream())
     return out
 
 
@@ -655,21 +657,10 @@ def report_tokens(batch, device, dtype, out=None, tables=None):
     ``device`` (``store.to(device, dtype)``, once).  One small host-to-device copy (the descriptor), no device value is waited
     for.  out: a buffer to write into; tables: the descriptor already on the device (tools/bench_report_store.py times the
     launch alone, the tests hand over descriptors the plan would never make)."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"medical_tri_modal_pilot_amd ops run on an MI355X only (report_tokens on {device}); there is no CPU fallback")
-    store = batch.store
-    B, L, W = batch.batch_size, batch.max_tokens, batch.width
-    desc = batch.descriptor().to(device, non_blocking=True) if tables is None else tables
-    if store.device != desc.device:
-        raise RuntimeError(f"report_tokens: the report store is on {store.device}, not on {desc.device}: call store.to(device) once")
-    if tuple(desc.shape) != (B, 2) or desc.dtype != torch.int64 or not desc.is_contiguous():
-        raise ValueError(f"report_tokens: the descriptor must be a contiguous int64 tensor {(B, 2)}")
-    if out is None:
-        out = torch.empty((B, L, W), dtype=dtype, device=device)
-    elif tuple(out.shape) != (B, L, W) or out.dtype != dtype or not out.is_contiguous() or out.device != desc.device:
-        raise ValueError(f"report_tokens: out must be a contiguous {dtype} tensor {(B, L, W)} on {device}")
-    with torch.cuda.device(device), kernel_marks("report_gather", B):
+    store, B, L, W = batch.store, batch.batch_size, batch.max_tokens, batch.width
+    (desc,), out = _store_gather("report_tokens", batch, device, "report", (("descriptor", batch.descriptor, (B, 2), torch.int64),),
+                                 tables if tables is None else (tables,), (B, L, W), dtype, out)
+    with torch.cuda.device(out.device), kernel_marks("report_gather", B):
         call("mtmp_report_gather", _p(store.emb), _dt(store.emb), store.n_tokens, _p(desc), _p(out), _dt(out), B, L, W, _stream())
     return out
 
@@ -681,21 +672,10 @@ def report_token_ids(batch, device, out=None, tables=None):
     EOS, zeros; every 1 written as 0), in ONE launch that writes all of it (no memset).  The same contract as ``report_tokens``:
     the store must be on ``device`` (``store.to(device)``, once), one small host-to-device copy (the descriptor), no device value
     is waited for.  out: a buffer to write into; tables: the descriptor already on the device."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError(f"medical_tri_modal_pilot_amd ops run on an MI355X only (report_token_ids on {device}); there is no CPU fallback")
-    store = batch.store
-    B, L = batch.batch_size, batch.max_length
-    desc = batch.descriptor().to(device, non_blocking=True) if tables is None else tables
-    if store.device != desc.device:
-        raise RuntimeError(f"report_token_ids: the token store is on {store.device}, not on {desc.device}: call store.to(device) once")
-    if tuple(desc.shape) != (B, 2) or desc.dtype != torch.int64 or not desc.is_contiguous():
-        raise ValueError(f"report_token_ids: the descriptor must be a contiguous int64 tensor {(B, 2)}")
-    if out is None:
-        out = torch.empty((B, L), dtype=torch.int32, device=device)
-    elif tuple(out.shape) != (B, L) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != desc.device:
-        raise ValueError(f"report_token_ids: out must be a contiguous int32 tensor {(B, L)} on {device}")
-    with torch.cuda.device(device), kernel_marks("report_ids_gather", B):
+    store, B, L = batch.store, batch.batch_size, batch.max_length
+    (desc,), out = _store_gather("report_token_ids", batch, device, "token", (("descriptor", batch.descriptor, (B, 2), torch.int64),),
+                                 tables if tables is None else (tables,), (B, L), torch.int32, out)
+    with torch.cuda.device(out.device), kernel_marks("report_ids_gather", B):
         call("mtmp_report_ids_gather", _p(store.ids), store.n_tokens, _p(desc), _p(out), B, L, _stream())
     return out
 

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools._timing import Lines, median, wall_ms  # noqa: E402
 from tools.bench_jpeg import images, median_pair, pil_decode  # noqa: E402
 
 
@@ -30,11 +31,9 @@ def median_wall(fa, fb, rounds, after=lambda: None):
     ts = ([], [])
     for _ in range(rounds):
         for i, fn in enumerate((fa, fb)):
-            t0 = time.perf_counter()
-            fn()
-            ts[i].append((time.perf_counter() - t0) * 1e3)
+            ts[i].append(wall_ms(fn, sync=False))
             after()
-    return sorted(ts[0])[rounds // 2], sorted(ts[1])[rounds // 2]
+    return median(ts[0]), median(ts[1])
 
 
 def main():
@@ -53,8 +52,9 @@ def main():
     from medical_tri_modal_pilot_amd.synthetic import jpeg_encode
     import PIL
     where = torch.cuda.get_device_name(0) if gpu else "no GPU: planning half only"
-    lines = [f"torch {torch.__version__}, {where}, PIL {PIL.__version__}; {a.images} images, quality 75; kernels: median of "
-             f"{a.rounds} rounds of 5 launches, device events; host: median of {a.host_rounds} wall times; the two forms alternate"]
+    say = Lines()
+    say(f"torch {torch.__version__}, {where}, PIL {PIL.__version__}; {a.images} images, quality 75; kernels: median of "
+        f"{a.rounds} rounds of 5 launches, device events; host: median of {a.host_rounds} wall times; the two forms alternate")
     tr = CxrTransform(224, "resize_crop", True)
     dev = torch.device("cuda", 0) if gpu else None
     for h, w in ((260, 312), (586, 586)):
@@ -72,12 +72,13 @@ def main():
         sent_st = common(raw_st) + raw_st.stored.nbytes
         jp = raw_by.jpeg
         sent_by = common(raw_by) + nb(raw_by.pixels, jp.streams, jp.desc, jp.segs, jp.tables)
-        lines += [f"{a.images} x {h} x {w}: files {sum(len(f) for f in files)} bytes; store: streams {store.nbytes_streams}, sync table "
+        for s in [f"{a.images} x {h} x {w}: files {sum(len(f) for f in files)} bytes; store: streams {store.nbytes_streams}, sync table "
                   f"{store.nbytes_sync} ({store.nbytes_sync / store.nbytes_streams:.3f} of the streams), all {store.nbytes} bytes against "
                   f"{a.images * h * w} bytes of uint8 pixels ({store.nbytes / (a.images * h * w):.3f}); from_files (parse, once) {t_parse:.1f} ms",
                   f"  planning half (collate_raw_cxr alone): handles {plan_st:8.3f} ms, file bytes {plan_by:8.3f} ms",
                   f"  bytes over the link per batch: handles {sent_st} (store rows and prefix {raw_st.stored.nbytes}), file bytes {sent_by} "
-                  f"(zero pixel buffer {raw_by.pixels.numel()}, streams {jp.streams.numel()})"]
+                  f"(zero pixel buffer {raw_by.pixels.numel()}, streams {jp.streams.numel()})"]:
+            say(s)
         if not gpu:
             continue
         from medical_tri_modal_pilot_amd import ops
@@ -111,16 +112,13 @@ def main():
             raw = collate_raw_cxr(samples, tr, 0).to(dev, non_blocking=True)
             ops.jpeg_decode(raw)
         w_st, w_by = median_wall(lambda: batch(s_handles), lambda: batch(s_bytes), a.host_rounds, torch.cuda.synchronize)
-        lines += [f"  mtmp_jpeg_store_entropy ({sb.lanes} lanes, {-(-sb.lanes // 256)} workgroups of 256): {t_st * 1e3:9.1f} us;  mtmp_jpeg_entropy "
+        for s in [f"  mtmp_jpeg_store_entropy ({sb.lanes} lanes, {-(-sb.lanes // 256)} workgroups of 256): {t_st * 1e3:9.1f} us;  mtmp_jpeg_entropy "
                   f"(subseq_bits {S}, {p.segs.shape[0]} workgroups, its defaults): {t_par * 1e3:9.1f} us;  ratio {t_par / t_st:.2f}",
                   f"  samples -> device-ready batch (collate_raw_cxr, .to(device), the decoder's enqueue): handles {w_st:8.3f} ms, file bytes "
                   f"{w_by:8.3f} ms",
-                  f"  store.to(device), once (upload, sync table, status read-back): {store.build_ms:8.2f} ms"]
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        with open(a.out, "w") as fh:
-            fh.write(text + "\n")
+                  f"  store.to(device), once (upload, sync table, status read-back): {store.build_ms:8.2f} ms"]:
+            say(s)
+    say.write(a.out)
 
 
 if __name__ == "__main__":

@@ -13,12 +13,12 @@ can be read against the spread.  Needs a GPU; there is no fallback."""
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools._timing import Lines, device_ms, median, wall_ms  # noqa: E402
 
 
 def pick_windows(store, B, rng):
@@ -33,22 +33,8 @@ def pick_windows(store, B, rng):
     return np.asarray(w, np.int64)
 
 
-def device_us(fn, reps=10):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return 1e3 * e0.elapsed_time(e1) / reps
-
-
-def wall_us(fn):
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    fn()
-    torch.cuda.synchronize()
-    return 1e6 * (time.perf_counter() - t)
+def device_10(fn):
+    return device_ms(fn, 10)
 
 
 def alternate(fa, fb, rounds, timer):
@@ -63,9 +49,9 @@ def alternate(fa, fb, rounds, timer):
 
 
 def fmt(ts, unit="us"):
-    s = sorted(ts)
-    d = 3 if unit == "ms" else 1
-    return f"median {s[len(s) // 2]:.{d}f} {unit} (min {s[0]:.{d}f}, max {s[-1]:.{d}f}, {len(s)} repeats)"
+    """``ts`` in ms, printed in ``unit``"""
+    k, d = (1.0, 3) if unit == "ms" else (1e3, 1)
+    return f"median {k * median(ts):.{d}f} {unit} (min {k * min(ts):.{d}f}, max {k * max(ts):.{d}f}, {len(ts)} repeats)"
 
 
 def main():
@@ -82,11 +68,7 @@ def main():
     from medical_tri_modal_pilot_amd.train import _Logger, build_training
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
+    say = Lines()
     say("command: python tools/bench_hourly.py " + " ".join(sys.argv[1:]))
     B, W, F, dt = a.batch, 24, 16, torch.bfloat16
     store = synthetic.make_tie_store(4099, 64).to(dev)
@@ -101,7 +83,7 @@ def main():
     out = torch.empty(B, W, F, device=dev)
     for _ in range(3):
         ops.hourly_windows(batch, dev, out=out, tables=desc)
-    ts = [device_us(lambda: ops.hourly_windows(batch, dev, out=out, tables=desc)) for _ in range(a.rounds)]
+    ts = [device_10(lambda: ops.hourly_windows(batch, dev, out=out, tables=desc)) for _ in range(a.rounds)]
     say(f"mtmp_hourly_window_gather alone (descriptor on the device, 10 launches back to back per repeat): {fmt(ts)} per launch")
 
     # ---- 2. ops.hourly_windows against the host path of the same windows
@@ -113,14 +95,10 @@ def main():
         t = torch.from_numpy(x).permute(1, 0, 2, 3)
         return t[0].half().float().to(dev, non_blocking=True)
     assert torch.equal(host_path(), ops.hourly_windows(batch, dev))
-    ta, tb = alternate(lambda: ops.hourly_windows(batch, dev), host_path, a.rounds, wall_us)
+    ta, tb = alternate(lambda: ops.hourly_windows(batch, dev), host_path, a.rounds, wall_ms)
     say(f"ops.hourly_windows (descriptor copy + launch + synchronise, wall): {fmt(ta)}")
     say(f"host path (numpy slice, pad to [B, 3, {W}, {F}], .half().float(), upload + synchronise, wall): {fmt(tb)}; results are equal")
-    tp = []
-    for _ in range(a.rounds):
-        t = time.perf_counter()
-        store.plan_hourly(wins, W, None, 1)
-        tp.append(1e6 * (time.perf_counter() - t))
+    tp = [wall_ms(lambda: store.plan_hourly(wins, W, None, 1), sync=False) for _ in range(a.rounds)]
     say(f"store.plan_hourly (host): {fmt(tp)} per batch")
 
     # ---- 3. the embedding, forward + backward, against the torch chain
@@ -141,7 +119,7 @@ def main():
         for q in pb:
             q.grad = None
         torch.relu(torch.nn.functional.layer_norm(torch.nn.functional.linear(x, pb[0], pb[1]), (256,), pb[2], pb[3])).to(dt).backward(dy)
-    ta, tb = alternate(hip_chain, torch_chain, a.rounds, device_us)
+    ta, tb = alternate(hip_chain, torch_chain, a.rounds, device_10)
     err = max(float((u.grad - v.grad).abs().max() / v.grad.abs().max()) for u, v in zip(pa, pb))
     say(f"ops.HourlyEmbedFn forward + backward, n = {B * W} rows (3 kernel launches + the gradient transpose): {fmt(ta)}")
     say(f"torch chain forward + backward (Linear, LayerNorm, ReLU, cast; autograd): {fmt(tb)}; largest relative gradient difference {err:.1e}")
@@ -172,17 +150,14 @@ def main():
                                        x_txt=bt["txt"], x_img=bt["img"], txt_lengths=bt["txt_lengths"],
                                        imgtxt_time=(bt["img_time"], batch.txt_time), scaler=None, missing=bt["missing"],
                                        flow_type="train", reports_tokens=None, reports_lengths=None, criterion_aux=(None, None))
-    timer = lambda fn: wall_us(fn) / 1e3 / a.steps
+    timer = lambda fn: wall_ms(fn) / a.steps
     ta, tb = alternate(lambda: steps(True), lambda: steps(False), max(6, a.rounds // 2), timer)
     tuning.HIP_HOURLY_EMBED = True
     for on, ts_ in ((True, ta), (False, tb)):
         st = runs[on]["model"]._mtmp_graph_step.stats()
         say(f"training step, HIP_HOURLY_EMBED {'on ' if on else 'off'} (6 layers, B {B}, bf16, hipGraph: {st['captures']} capture, "
             f"{st['replays']} replays; {a.steps} steps per repeat, wall / steps): {fmt(ts_, 'ms')}; last loss {runs[on]['loss']:.5f}")
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    say.write(a.out)
 
 
 if __name__ == "__main__":

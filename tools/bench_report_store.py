@@ -16,16 +16,12 @@ computed from the shapes.  Every gathered batch is compared with the parent path
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def med(xs):
-    return sorted(xs)[len(xs) // 2]
+from tools._timing import Lines, device_ms, median as med, wall_ms  # noqa: E402
 
 
 def main():
@@ -44,30 +40,8 @@ def main():
     torch.cuda.set_device(dev)
     F32, BF16 = torch.float32, torch.bfloat16
     B, L, W = a.batch, 128, 768
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    def dev_time(fn):
-        """ms per call: device events around `inner` calls back to back"""
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.inner):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / a.inner
-
-    def wall_time(fn):
-        """ms of one call that ends in a synchronise, by the host clock"""
-        torch.cuda.synchronize()
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        return 1e3 * (time.perf_counter() - t)
-
+    say, wall_time = Lines(), wall_ms
+    dev_time = lambda fn: device_ms(fn, a.inner)
     say(f"device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; B {B}, L {L}, W {W}; {a.rounds} alternating rounds, "
         f"device-event figures over {a.inner} calls back to back")
     # the store: B distinct reports of L tokens (the `full` workload reads every one of them once: no report is served from a
@@ -146,15 +120,9 @@ def main():
                       f"{1e3 * min(t_launch[k]):.1f}, max {1e3 * max(t_launch[k]):.1f}: an upper bound on the kernel, the window holds the "
                       f"host's enqueue of every launch)")
             say(s)
-        tp = []
-        for _ in range(a.rounds):
-            t = time.perf_counter()
-            stores[F32].plan(idx)
-            tp.append(time.perf_counter() - t)
-        say(f"[{kind}] store.plan on the host: {1e6 * med(tp):.0f} us per batch")
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        tp = [wall_ms(lambda: stores[F32].plan(idx), sync=False) for _ in range(a.rounds)]
+        say(f"[{kind}] store.plan on the host: {1e3 * med(tp):.0f} us per batch")
+    say.write(a.out)
 
 
 if __name__ == "__main__":

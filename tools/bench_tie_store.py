@@ -13,12 +13,12 @@ the host path's first.  Needs a GPU; there is no fallback."""
 import argparse
 import os
 import sys
-import time
 
 import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from tools._timing import Lines, device_ms, median, wall_ms  # noqa: E402
 
 
 def pick_windows(store, patients, B, kind, rng):
@@ -35,13 +35,9 @@ def pick_windows(store, patients, B, kind, rng):
     return np.asarray(w, np.int64)
 
 
-def median(fn, rounds):
-    ts = []
-    for _ in range(rounds):
-        t = time.perf_counter()
-        fn()
-        ts.append(time.perf_counter() - t)
-    return sorted(ts)[rounds // 2]
+def host_ms(fn, rounds):
+    """median ms of ``fn`` by the host clock alone (host work, or a call that synchronises by itself)"""
+    return median([wall_ms(fn, sync=False) for _ in range(rounds)])
 
 
 def main():
@@ -60,11 +56,7 @@ def main():
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     torch.set_num_threads(1)
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
+    say = Lines()
     patients, fmin, fmax = synthetic.make_tie_patients(4099, 64)
     store = TieEventStore.from_patients(patients, fmin, fmax).to(dev)
     say(f"store: {store.n_patients} patients, {store.n_hours} patient-hours, {store.n_events} events, {store.nbytes} bytes on the device = "
@@ -102,23 +94,16 @@ def main():
         lens = batch.input_lengths
         say(f"[{kind}] B {B}, TIE-len {T}: rows {int(lens.min())}..{int(lens.max())}, mean {float(lens.float().mean()):.0f}, "
             f"{batch.total_rows} in the batch; gather == host path")
-        t_rows, t_host = median(host_rows, a.rounds), median(host_path, a.rounds)
-        say(f"[{kind}] host path, one core: tie_window x {B} {1e3 * t_rows:.2f} ms, with collate_packed + on_device(bucket 4096) "
-            f"{1e3 * t_host:.2f} ms per batch = {1e3 * t_host / B:.3f} ms per sample")
-        say(f"[{kind}] store.plan: {1e6 * median(lambda: store.plan(wins, T, 1), a.rounds):.0f} us per batch")
-        t_call = median(lambda: (ops.tie_windows(batch, dev, 1000, bucket=4096), torch.cuda.synchronize()), a.rounds)
+        t_rows, t_host = host_ms(host_rows, a.rounds), host_ms(host_path, a.rounds)
+        say(f"[{kind}] host path, one core: tie_window x {B} {t_rows:.2f} ms, with collate_packed + on_device(bucket 4096) "
+            f"{t_host:.2f} ms per batch = {t_host / B:.3f} ms per sample")
+        say(f"[{kind}] store.plan: {1e3 * host_ms(lambda: store.plan(wins, T, 1), a.rounds):.0f} us per batch")
+        t_call = host_ms(lambda: (ops.tie_windows(batch, dev, 1000, bucket=4096), torch.cuda.synchronize()), a.rounds)
         desc, cu = batch.descriptor().to(dev), batch.cu_seqlens.to(dev)
-        ts = []
-        for _ in range(a.rounds + 2):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(5):
-                ops.tie_windows(batch, dev, 1000, bucket=4096, out=got.events, tables=(desc, cu))
-            e1.record()
-            torch.cuda.synchronize()
-            ts.append(e0.elapsed_time(e1) / 5)
-        say(f"[{kind}] mtmp_tie_window_gather alone: {1e3 * sorted(ts[2:])[a.rounds // 2]:.1f} us per launch (device events, 5 launches back "
-            f"to back); ops.tie_windows with its two small copies and a synchronise: {1e6 * t_call:.0f} us wall")
+        launch = lambda: ops.tie_windows(batch, dev, 1000, bucket=4096, out=got.events, tables=(desc, cu))
+        ts = [device_ms(launch, 5) for _ in range(a.rounds + 2)]
+        say(f"[{kind}] mtmp_tie_window_gather alone: {1e3 * median(ts[2:]):.1f} us per launch (device events, 5 launches back "
+            f"to back); ops.tie_windows with its two small copies and a synchronise: {1e3 * t_call:.0f} us wall")
         # between replayed steps: the trainer gathers in front of every step; the marks bracket the launch on the stream
         bt = synthetic.make_batch(99, B, T, missing_mode="none")
         ops.marks_enable(dev, only=("k.tie_window_gather",))
@@ -136,12 +121,10 @@ def main():
             m = ops.marks_read()
             in_step.append(m[f"k.tie_window_gather.N{B}.0.e"] - m[f"k.tie_window_gather.N{B}.0.s"])
         ops.marks_disable()
-        say(f"[{kind}] mtmp_tie_window_gather in front of replayed hipGraph steps (6 layers, bf16): median {sorted(in_step)[len(in_step) // 2]:.1f} us "
+        say(f"[{kind}] mtmp_tie_window_gather in front of replayed hipGraph steps (6 layers, bf16): median {median(in_step):.1f} us "
             f"between its stamps (the last of {a.steps} steps, five times: {', '.join(f'{v:.1f}' for v in in_step)}; the first group "
             f"holds the capture)")
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    say.write(a.out)
 
 
 if __name__ == "__main__":

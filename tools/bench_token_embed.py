@@ -22,10 +22,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-
-def med(xs):
-    return sorted(xs)[len(xs) // 2]
+from tools._timing import Lines, device_ms, median as med  # noqa: E402
 
 
 def main():
@@ -44,22 +41,8 @@ def main():
     F32, BF16 = torch.float32, torch.bfloat16
     L, V, D = 128, 30000, 256
     C = ops.token_embed_chunk()
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    def dev_time(fn):
-        """ms per call: device events around `inner` calls back to back"""
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(a.inner):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / a.inner
-
+    say = Lines()
+    dev_time = lambda fn: device_ms(fn, a.inner)
     say(f"device: {torch.cuda.get_device_name(0)}; torch {torch.__version__}; L {L}, V {V}, D {D}, chunk {C}; {a.rounds} alternating "
         f"rounds, device-event figures over {a.inner} calls back to back")
     host = synthetic.make_token_report_store(5011, n_reports=a.reports)
@@ -141,9 +124,7 @@ def main():
             for k in variants:
                 say(f"[B {B} {tag}] {k}: {1e3 * med(times[k]):.1f} us per call (min {1e3 * min(times[k]):.1f}, max "
                     f"{1e3 * max(times[k]):.1f}); about {moved[k] / 1e6:.2f} MB of device traffic by the shapes")
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    say.write(a.out)
 
 
 if __name__ == "__main__":

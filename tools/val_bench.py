@@ -14,17 +14,16 @@ import argparse
 import math
 import os
 import sys
-import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from tools._timing import Lines, median, wall_ms  # noqa: E402
 
 
 def stats(xs):
-    s = sorted(xs)
-    return s[len(s) // 2], s[0], s[-1]
+    return median(xs), min(xs), max(xs)
 
 
 def main():
@@ -45,11 +44,7 @@ def main():
     from medical_tri_modal_pilot_amd.train import _Logger, build_training
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
+    say = Lines()
 
     say(f"validation pass on {torch.cuda.get_device_name(0)}: windows of >= {a.window_s} s, {a.windows} per variant, alternating")
     for wl in a.workloads.split(","):
@@ -90,11 +85,8 @@ def main():
             return r["loss"], r["performance_metric"]
 
         def timed(fn, k):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            out = fn(k)
-            torch.cuda.synchronize()
-            return (time.perf_counter() - t0) * 1e3 / k, out
+            out = []
+            return wall_ms(lambda: out.append(fn(k))) / k, out[0]
 
         # warm every shape (lazy initialisation, the eval graph's warm-up step and capture), then size K per variant
         eager_pass(3)
@@ -141,19 +133,14 @@ def main():
         for rep in range(a.metric_reps + 1):
             for name, ev in (("Evaluator", old), ("DeviceEvaluator", new)):
                 new._metrics = None
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                res[name] = ev.performance_metric()
-                torch.cuda.synchronize()
+                ms = wall_ms(lambda: res.update({name: ev.performance_metric()}))
                 if rep:                                  # the first repetition warms
-                    tm[name].append((time.perf_counter() - t0) * 1e3)
+                    tm[name].append(ms)
         say(f"performance_metric() at {n} stored predictions ({a.metric_reps} repetitions after one warm-up):")
         for name in tm:
             m, lo, hi = stats(tm[name])
             say(f"  {name:16s}: {m:9.3f} ms (min {lo:.3f} .. max {hi:.3f}) -> {[float(v) for v in res[name]]}")
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    say.write(a.out)
 
 
 if __name__ == "__main__":
