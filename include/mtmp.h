@@ -258,6 +258,37 @@ int mtmp_head_bwd_scatter(int cls_dtype, const float* d_out, const void* cls, co
  * dlogit[b] = (sigmoid(o_b) - t_b) / n; logits / target / dlogit float[n]. */
 int mtmp_bce_logits_mean(const float* logits, const float* target, float* loss, float* dlogit, int n, void* stream);
 
+/* Three-row LayerNorm head (tri_mbt_v1.py:154-159,271-281; tri_mbt_vnoshavgtr.py / tri_mbt_vnoshnoavgtr.py: one head per row):
+ * out[m][b] = fc_m(cat[LN(cls_m[b]), ReLU(LN(ie_demo.0(age, gender)))]), fc_m = Linear(512,256) -> LayerNorm -> ReLU -> Linear(256,1),
+ * rows m = 0, 1, 2 = vslt, image, text; fp32, 1 <= B <= 256; three launches forward, four backward, no float atomics.
+ * cls[3]: the CLS rows of the three streams in cls_dtype (MTMP_F32 | MTMP_BF16), row b of stream m at cls[m] + b * cls_ld[m]
+ * elements (16-byte aligned base, cls_ld[m] >= 256 and a multiple of 4).  params: 6 + 6 * n_sets device pointers (float):
+ * ie_demo.0.weight[256][2], ie_demo.0.bias, ie_demo.1.{weight,bias}, layer_norms_after_concat.{weight,bias}, then per set
+ * {0.weight[256][512], 0.bias, 1.weight, 1.bias, 3.weight[256], 3.bias[1]}; n_sets = 3: set m for row m, n_sets = 1: one set
+ * shared by the three rows.  out float[3][B].  ws_fwd: mtmp_head3_ws_floats(B) floats, written by the forward, read by the backward.
+ * backward: d_out float[3][B]; dcls[3]: [B][256] contiguous each, in cls_dtype; dst: one destination per entry of params
+ * (overwritten; slices of the flat gradient buffer, or scratch) -- a shared set and the first six get the three rows' contributions
+ * summed in the fixed order m = 0, 1, 2.  ws_bwd: mtmp_head3_bwd_ws_floats(B) floats. */
+int mtmp_head3_ws_floats(int B);
+int mtmp_head3_bwd_ws_floats(int B);
+int mtmp_head3_fwd(int cls_dtype, const void* const* cls, const long long* cls_ld, const float* age, const float* gender,
+                   const void* const* params, int n_sets, float* out, float* ws, int B, float ln_eps, void* stream);
+int mtmp_head3_bwd(int cls_dtype, const float* d_out, const void* const* cls, const long long* cls_ld, const float* age,
+                   const float* gender, const void* const* params, int n_sets, const float* ws_fwd, void* const* dcls,
+                   float* const* dst, float* ws_bwd, int B, float ln_eps, void* stream);
+
+/* Mean of the three logits over the modalities present under the pattern id missing_num[b] (trainer.py:68-77,224-229;
+ * tri_mbt_v1.py:272-281): S(0) = {0,1,2}, S(1) = {0,1}, S(2) = {0,2}, S(3) = {0}; o / d_o float[3][B], out / d_out float[B],
+ * missing_num int64[B] (read as id & 3: nothing is indexed by it).  d_o[m][b] = d_out[b] / |S| inside the set, 0 outside. */
+int mtmp_candidate_mean_fwd(const float* o, const long long* missing_num, float* out, int B, void* stream);
+int mtmp_candidate_mean_bwd(const float* d_out, const long long* missing_num, float* d_o, int B, void* stream);
+
+/* BCEWithLogitsLoss(reduction="mean") over the present (row, sample) pairs (trainer.py:169-174): loss[0] = (1/n) sum_b sum_{m in
+ * S(missing_num[b])} bce(logits[m][b], target[b]) with n = sum_b |S| counted on the device; dlogit float[3][B] = (sigmoid - target) / n
+ * inside the sets, 0 outside.  One launch, any B > 0, no host synchronisation. */
+int mtmp_bce_masked_mean(const float* logits, const float* target, const long long* missing_num, float* loss, float* dlogit, int B,
+                         void* stream);
+
 /* Stream-ordered time stamp: a one-lane kernel on `stream` stores the 100 MHz wall clock into *slot.  Also works inside a
  * captured hipGraph, where HIP events cannot be timed -- bench.py brackets the roofline kernel of the replayed steps with it. */
 int mtmp_timestamp(unsigned long long* slot, void* stream);

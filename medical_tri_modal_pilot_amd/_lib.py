@@ -99,6 +99,13 @@ SIGNATURES = {
     "mtmp_head_fwd_t": (c_int, [c_int] + [c_void_p] * 6 + [c_int, c_float, c_float, c_float, c_int, c_void_p, c_void_p]),
     "mtmp_head_bwd_scatter": (c_int, [c_int] + [c_void_p] * 9 + [c_int, c_float, c_int, c_void_p]),
     "mtmp_bce_logits_mean": (c_int, [c_void_p] * 4 + [c_int, c_void_p]),
+    "mtmp_head3_ws_floats": (c_int, [c_int]),
+    "mtmp_head3_bwd_ws_floats": (c_int, [c_int]),
+    "mtmp_head3_fwd": (c_int, [c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_void_p, c_int, c_float, c_void_p]),
+    "mtmp_head3_bwd": (c_int, [c_int] + [c_void_p] * 6 + [c_int] + [c_void_p] * 4 + [c_int, c_float, c_void_p]),
+    "mtmp_candidate_mean_fwd": (c_int, [c_void_p] * 3 + [c_int, c_void_p]),
+    "mtmp_candidate_mean_bwd": (c_int, [c_void_p] * 3 + [c_int, c_void_p]),
+    "mtmp_bce_masked_mean": (c_int, [c_void_p] * 5 + [c_int, c_void_p]),
     "mtmp_timestamp": (c_int, [c_void_p, c_void_p]),
     "mtmp_swin_ln_linear": (c_int, [c_int] + [c_void_p] * 6 + [c_longlong, c_int, c_int, c_float, c_void_p]),
     "mtmp_swin_ln_linear_live": (c_int, [c_int] + [c_void_p] * 6 + [c_longlong, c_int, c_int, c_float, c_void_p, c_void_p]),

@@ -27,6 +27,7 @@ from .tri_mbt_vsltcls import flat_layout
 
 class TRI_MBT_V2(TRI_MBT_V1):
     TRAINS_ENCODER_IN_REFERENCE = True
+    hip_tri_head = False          # a BatchNorm head over 3 B rows: its own torch form
 
     def __init__(self, args):
         if args.berttype != "bert":

@@ -20,6 +20,7 @@ _ABSENT = torch.tensor([[False, False, False], [False, False, True], [False, Tru
 
 class TRI_MBT_VFLEXIBLE(TRI_MBT_V1):
     flex_temperature = 1.0
+    hip_tri_head = False          # softmax-weighted means: the torch head below
 
     def __init__(self, args):
         super().__init__(args)

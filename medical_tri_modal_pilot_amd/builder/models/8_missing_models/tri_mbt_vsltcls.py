@@ -120,6 +120,7 @@ class TRI_MBT_VSLTCLS(nn.Module):
         self.n_images = int(getattr(args, "n_images", 3)) if self.args.multiimages == 1 else 1
 
     head_fusable = True        # ie_demo = Linear -> LayerNorm -> ReLU: what ops.HeadFn fuses (a sibling may differ)
+    head_min_train_batch = 2   # BatchNorm1d needs two rows in training mode (a sibling with a LayerNorm head: 1)
     # forward accepts a PackedTie in place of the padded x.  The trainer asks before it hands windows of the event store over
     # (trainer.py); a sibling that reads the padded tensor sets False, and a model class that does not define the flag at all is
     # given the padded form too.
@@ -259,12 +260,12 @@ class TRI_MBT_VSLTCLS(nn.Module):
         age, gen = age.float(), gen.float()
         # head + ie_demo as six HIP launches (ops.HeadFn) when the demographic embedding feeds nothing but the head
         fused_head = (self.head_fusable and age.is_cuda and B <= ops.HEAD_MAX_B and self.args.vslt_type != "QIE"
-                      and "rmse" not in self.args.auxiliary_loss_type and (B > 1 or not self.training))
+                      and "rmse" not in self.args.auxiliary_loss_type and (B >= self.head_min_train_batch or not self.training))
         if (not fused_head and self.head_fusable and age.is_cuda and self.training and not getattr(self, "_warned_torch_head", False)
                 and self.args.vslt_type != "QIE" and "rmse" not in self.args.auxiliary_loss_type):
             import warnings
             self._warned_torch_head = True
-            warnings.warn(f"TRI_MBT_VSLTCLS: batch of {B} is outside the fused head kernels' range (2 <= B <= {ops.HEAD_MAX_B} in "
+            warnings.warn(f"{type(self).__name__}: batch of {B} is outside the fused head kernels' range ({self.head_min_train_batch} <= B <= {ops.HEAD_MAX_B} in "
                           "training): the classifier head runs as torch ops (same results, ~60 more small launches per step)")
         if not fused_head:
             demographic = torch.stack([age, gen], dim=1)

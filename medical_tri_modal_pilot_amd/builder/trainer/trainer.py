@@ -143,7 +143,7 @@ def _stage_bounds(args, enc, ddp: bool):
     return sorted(set([0, n_fl] + [round(n_fl * k / want) for k in range(1, want)]))
 
 
-def _staged_step(model, enc, optimizer, criterion, run_model, bounds):
+def _staged_step(model, enc, optimizer, criterion, run_model, bounds, args=None):
     """The stage callables of graph.GraphedTrainStep for a step cut at ``bounds``: stage 0 = zero_grad, forward, loss
     and the backward of the head and the LAST group of fusion layers, down to the stream buffers in front of that
     group (mbt_encoder.py segment_boundaries); stage k = the backward of the next group down; the last stage also
@@ -168,7 +168,7 @@ def _staged_step(model, enc, optimizer, criterion, run_model, bounds):
         if tuning.PREFORK_IMAGE_ENCODER and hasattr(model, "prefork"):
             model.prefork(t["x_img"])
         optimizer.zero_grad()
-        step_loss = ops.bce_with_logits(criterion, run_model(t), t["final_target"])
+        step_loss = train_loss(args, criterion, run_model(t), t)
         carry["loss"] = step_loss.detach()
         gs_ = getattr(model, "_mtmp_graph_step", None)
         if gs_ is not None:
@@ -334,6 +334,28 @@ def _run_model(model, t, feasible, flow_type, reports_tokens=None, reports_lengt
     return out.squeeze()
 
 
+def unaveraged_heads(args) -> bool:
+    """The model hands out the three modality heads' logits [3, B, 1] un-averaged -- keyed on the model's name like the reference's
+    trainer (trainer.py:169,223)."""
+    return "mbt_vnoshnoavgtr" in str(getattr(args, "model", ""))
+
+
+def train_loss(args, criterion, output, t):
+    """The training loss on the squeezed logits.  Un-averaged heads (trainer.py:169-174): the target repeated over the three rows and
+    the criterion over the logits of the modalities that are present -- ops.bce_masked_mean counts them on the device, so there is
+    neither a data-dependent shape nor a host synchronisation and the step can be captured."""
+    if unaveraged_heads(args):
+        return ops.bce_masked_mean(criterion, output.reshape(3, -1), t["final_target"], t["missing_num"])
+    return ops.bce_with_logits(criterion, output, t["final_target"])
+
+
+def eval_logits(args, output, t):
+    """The logits the test flow scores.  Un-averaged heads (trainer.py:223-229): per sample the mean over the present modalities."""
+    if unaveraged_heads(args):
+        return ops.candidate_mean(output.reshape(3, -1).float(), t["missing_num"])
+    return output
+
+
 def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, model, logger, device,
                     scheduler=None, optimizer=None, criterion=None, scaler=None, flow_type=None, output_lengths=None,
                     seq_lengths=None, x_img=None, x_txt=None, txt_lengths=None, imgtxt_time=None, missing=None,
@@ -372,14 +394,14 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
                 if tuning.PREFORK_IMAGE_ENCODER and hasattr(model, "prefork"):
                     model.prefork(t["x_img"])            # the image encoder's stream forks at the head of the step
                 optimizer.zero_grad()
-                step_loss = ops.bce_with_logits(criterion, run_model(t), t["final_target"])
+                step_loss = train_loss(args, criterion, run_model(t), t)
                 gs.publish_loss(step_loss)           # the host takes the value from here (gs.wait_loss below)
                 torch.autograd.backward([step_loss], [ops.unit_grad(step_loss)])
                 ops.mark("bwd.e")                    # (tools/dbg/timeline.py; nothing is launched unless marks are enabled)
                 return step_loss.detach()
             loss = gs.run(inputs, fwd_bwd, optimizer.flat.params, reducer=red, round_fp16=deferred)
         else:
-            loss = gs.run(inputs, _staged_step(model, enc, optimizer, criterion, run_model, bounds),
+            loss = gs.run(inputs, _staged_step(model, enc, optimizer, criterion, run_model, bounds, args),
                           optimizer.flat.params, reducer=red, round_fp16=deferred)
         optimizer.step()
         scheduler.step(iteration)
@@ -395,14 +417,14 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
             model.fusion_transformer.graph_segments = None
         optimizer.zero_grad()
         output = run_model()
-        loss = ops.bce_with_logits(criterion, output, final_target)
+        loss = train_loss(args, criterion, output, inp.tensors(target=True))
         torch.autograd.backward([loss], [ops.unit_grad(loss)])
         optimizer.step()
         scheduler.step(iteration)
         logger.log_lr(scheduler.get_lr()[0], iteration)
     else:
         with torch.no_grad():
-            output = run_model()
+            output = eval_logits(args, run_model(), inp.tensors())
             loss = ops.bce_with_logits(criterion, output, final_target)
             output = torch.sigmoid(output)
         logger.evaluator.add_batch(final_target, output)

@@ -1572,6 +1572,156 @@ def bce_with_logits(criterion, output, target):
     return criterion(output, target)
 
 
+# ----------------------------------------------------------------------------- three-row head (csrc/head3.hip)
+def _cls_rows3(t: torch.Tensor) -> torch.Tensor:
+    """A [B, 256] view the head kernels read in place (fp32 | bf16, unit column stride, 16-byte aligned rows), else a copy."""
+    t = t.detach()
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        t = t.float()
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.stride(0) < D_MODEL or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+class TriHeadFn(torch.autograd.Function):
+    """The LayerNorm head on the CLS rows of the three streams (tri_mbt_v1.py:271-281 without the candidate mean; one head per
+    row in tri_mbt_vnoshavgtr.py / tri_mbt_vnoshnoavgtr.py) with the ie_demo chain: logits [3, B] fp32, rows vslt, image, text.
+    apply(cls0, cls1, cls2 [B, 256] fp32 | bf16 -- views ``outputs[m][:, 0, :]`` are read in place --, age [B], gender [B],
+    *parameters): ie_demo.0.{weight,bias}, ie_demo.1.{weight,bias}, layer_norms_after_concat.{weight,bias}, then ONE head's
+    {0.weight, 0.bias, 1.weight, 1.bias, 3.weight, 3.bias} (shared by the three rows: 12 parameters) or three heads' (24).
+    Three launches forward, four backward; the gradients go to their slices of the flat gradient buffer when they can be
+    overwritten (_sink_dsts), to autograd otherwise."""
+
+    @staticmethod
+    def forward(ctx, cls0, cls1, cls2, age, gender, *prm):
+        _gpu(cls0, cls1, cls2)
+        B = cls0.shape[0]
+        if B > HEAD_MAX_B:
+            raise ValueError(f"TriHeadFn handles up to {HEAD_MAX_B} rows per rank (got {B})")
+        if len(prm) not in (12, 24):
+            raise ValueError(f"TriHeadFn takes 12 (one shared head) or 24 (three heads) parameters, got {len(prm)}")
+        cls = [_cls_rows3(t) for t in (cls0, cls1, cls2)]
+        if cls[1].dtype != cls[0].dtype or cls[2].dtype != cls[0].dtype:
+            cls = [t.float().contiguous() for t in cls]
+        age, gender = _c(age.detach().float()), _c(gender.detach().float())
+        P = [_c(t.detach().float()) for t in prm]
+        n_sets = (len(prm) - 6) // 6
+        out = torch.empty(3, B, dtype=torch.float32, device=cls[0].device)
+        ws = torch.empty(_lib.lib().mtmp_head3_ws_floats(B), dtype=torch.float32, device=cls[0].device)
+        call("mtmp_head3_fwd", _dt(cls[0]), _ptrs(cls), (ctypes.c_longlong * 3)(*[t.stride(0) for t in cls]), _p(age), _p(gender),
+             _ptrs(P), n_sets, _p(out), _p(ws), B, 1e-5, _stream())
+        ctx.save_for_backward(age, gender, ws, *cls, *P)
+        ctx.shapes = [t.shape for t in prm]
+        ctx.prm = list(prm)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        age, gender, ws, c0, c1, c2, *P = ctx.saved_tensors
+        cls = [c0, c1, c2]
+        B, dev = c0.shape[0], c0.device
+        d_out = _c(d_out.float())
+        dcls = [torch.empty(B, D_MODEL, dtype=c0.dtype, device=dev) for _ in range(3)]
+        wsb = torch.empty(_lib.lib().mtmp_head3_bwd_ws_floats(B), dtype=torch.float32, device=dev)
+        sk = _sink_dsts(ctx.prm)
+        dsts = sk[2] if sk is not None else [torch.empty(t.numel(), dtype=torch.float32, device=dev) for t in ctx.prm]
+        call("mtmp_head3_bwd", _dt(c0), _p(d_out), _ptrs(cls), (ctypes.c_longlong * 3)(*[t.stride(0) for t in cls]), _p(age),
+             _p(gender), _ptrs(P), (len(P) - 6) // 6, _p(ws), _ptrs(dcls), _ptrs(dsts), _p(wsb), B, 1e-5, _stream())
+        if sk is not None:
+            sk[0].mark_ready(sk[1])
+            grads = (None,) * len(dsts)
+        else:
+            grads = tuple(t.view(sh) for t, sh in zip(dsts, ctx.shapes))
+        return (dcls[0], dcls[1], dcls[2], None, None) + grads
+
+
+def _present_rows(missing_num: torch.Tensor) -> torch.Tensor:
+    """bool [3, B]: the modalities present under the pattern ids (trainer.py:68-77) -- vslt always, image iff id < 2, report iff the
+    id is even; with --fullmodal-definition txt1_img1 this is ``missing.T == 0`` of the loader's flags."""
+    c = missing_num.long() & 3
+    return torch.stack([torch.ones_like(c, dtype=torch.bool), c < 2, (c & 1) == 0])
+
+
+def _ids64(missing_num: torch.Tensor, device) -> torch.Tensor:
+    return _c(missing_num.detach().to(device=device, dtype=torch.int64))
+
+
+class CandidateMeanFn(torch.autograd.Function):
+    """Per sample the mean of the three logits over the modalities that are present (tri_mbt_v1.py:272-281, trainer.py:224-229:
+    the four candidate means gathered by ``missing_num``): apply(o [3, B] fp32, missing_num [B]) -> [B].  One launch each way."""
+
+    @staticmethod
+    def forward(ctx, o, missing_num):
+        _gpu(o)
+        if o.dim() != 2 or o.shape[0] != 3 or missing_num.numel() != o.shape[1]:
+            raise ValueError(f"CandidateMeanFn: logits [3, B] and missing_num [B], got {tuple(o.shape)} and {tuple(missing_num.shape)}")
+        o = _c(o.detach().float())
+        ids = _ids64(missing_num, o.device)
+        out = torch.empty(o.shape[1], dtype=torch.float32, device=o.device)
+        call("mtmp_candidate_mean_fwd", _p(o), _p(ids), _p(out), o.shape[1], _stream())
+        ctx.save_for_backward(ids)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        (ids,) = ctx.saved_tensors
+        d_out = _c(d_out.float().reshape(-1))
+        d_o = torch.empty(3, ids.numel(), dtype=torch.float32, device=d_out.device)
+        call("mtmp_candidate_mean_bwd", _p(d_out), _p(ids), _p(d_o), ids.numel(), _stream())
+        return d_o, None
+
+
+def candidate_mean(o, missing_num):
+    """CandidateMeanFn on the GPU, the reference's stack-and-gather form elsewhere."""
+    if o.is_cuda and o.dtype == torch.float32:
+        return CandidateMeanFn.apply(o, missing_num)
+    cands = torch.stack([o.mean(0), torch.stack([o[0], o[1]]).mean(0), torch.stack([o[0], o[2]]).mean(0), o[0]])
+    return cands[missing_num.to(o.device).long(), torch.arange(o.shape[1], device=o.device)]
+
+
+class BceMaskedMean(torch.autograd.Function):
+    """BCEWithLogitsLoss(reduction="mean") over the logits of the modalities that are present (trainer.py:169-174:
+    ``criterion(output[missing == 0], target.repeat(3, 1)[missing == 0])``) without the data-dependent shape: the present
+    (row, sample) pairs are counted on the device, so nothing waits for it and the step can be captured.
+    apply(logits [3, B] fp32, target [B], missing_num [B]) -> scalar; one launch forward, one scale backward."""
+
+    @staticmethod
+    def forward(ctx, logits, target, missing_num):
+        _gpu(logits)
+        o, t = _c(logits.detach().float()), _c(target.detach().float().reshape(-1))
+        ids = _ids64(missing_num, o.device)
+        loss = torch.empty(1, dtype=torch.float32, device=o.device)
+        d = torch.empty_like(o)
+        call("mtmp_bce_masked_mean", _p(o), _p(t), _p(ids), _p(loss), _p(d), o.shape[1], _stream())
+        ctx.save_for_backward(d)
+        ctx.shape = logits.shape
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        # (handed out once, like BceLogitsMean's)
+        if g is _UNIT_GRAD.get((g.device.type, g.device.index, g.dtype)) and not getattr(ctx, "handed_out", False):
+            ctx.handed_out = True
+            return d.view(ctx.shape), None, None
+        return (d * g).view(ctx.shape), None, None
+
+
+def bce_masked_mean(criterion, output, target, missing_num):
+    """The training loss of TRI_MBT_VNOSHNOAVGTR: criterion over the logits [3, B] of the present modalities, the target repeated
+    over the rows.  Through BceMaskedMean when it is the plain mean-reduced BCEWithLogitsLoss on the GPU, else the reference's
+    boolean-index form."""
+    if output.dim() != 2 or output.shape[0] != 3 or target.numel() != output.shape[1] or missing_num.numel() != output.shape[1]:
+        raise ValueError(f"bce_masked_mean: logits [3, B], target [B], missing_num [B]; got {tuple(output.shape)}, "
+                         f"{tuple(target.shape)}, {tuple(missing_num.shape)}")
+    if (isinstance(criterion, torch.nn.BCEWithLogitsLoss) and criterion.reduction == "mean" and criterion.weight is None
+            and criterion.pos_weight is None and output.is_cuda and output.dtype == torch.float32):
+        return BceMaskedMean.apply(output, target, missing_num)
+    mask = _present_rows(missing_num.to(output.device))
+    y3 = target.reshape(1, -1).expand(3, -1)
+    return criterion(output[mask], y3[mask])
+
+
 # ----------------------------------------------------------------------------- stream input (K4)
 class StreamInputFn(torch.autograd.Function):
     """mbt_encoder.py:697-729 + the [bottleneck | CLS | tokens] concatenation of :745 as one launch each way.

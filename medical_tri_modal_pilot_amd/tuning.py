@@ -2,7 +2,7 @@
 
 Each switch chooses the order in which independent launches are issued, or which of two launch sequences meant to be equivalent
 runs.  The defaults below are what the tests and bench.py run, and the only settings they run: no test reads or sets one of these
-attributes (HIP_HOURLY_EMBED excepted: its other setting is the reference's own torch chain, and a test runs both).  The other
+attributes (HIP_HOURLY_EMBED and HIP_TRI_HEAD excepted: their other setting is the reference's own torch chain, and a test runs both).  The other
 settings are exercised only through ``tools/dbg/ab_patch.py`` (and the tools/dbg probes that flip one), so treat a non-default setting as unverified until such a run has compared it.  Each default is the faster setting as measured on
 MI355X -- the measurement is named beside it and lives in DESIGN.md section 9 ("Built, measured, not kept").  They are module
 attributes so that ab_patch.py can flip one and measure both settings on one machine in one session (machines differ by up to
@@ -47,3 +47,9 @@ HIP_TOKEN_EMBED = True
 # accumulations).  The one switch BOTH of whose settings the tests run (tests/test_carryforward_model_gpu.py): off is the torch
 # chain the reference defines.  profiles/carryforward.txt.
 HIP_HOURLY_EMBED = True
+# tri_mbt_v1 / tri_mbt_vnoshavgtr (and tri_mbt_vnoshnoavgtr, whose masked loss needs a capturable chain either way): the three-row
+# LayerNorm head and the candidate mean as ops.TriHeadFn + ops.CandidateMeanFn (csrc/head3.hip: three launches forward, four
+# backward, one each way for the mean) instead of the torch chain stack -> LayerNorm -> cat -> Linear -> LayerNorm -> ReLU -> Linear
+# -> four means -> gather plus ie_demo.  Like HIP_HOURLY_EMBED, BOTH settings are run by the tests (tests/test_noshnoavgtr_gpu.py):
+# off is the torch chain the reference defines.  profiles/tri_head.txt.
+HIP_TRI_HEAD = True
