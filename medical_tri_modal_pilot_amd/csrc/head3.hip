@@ -11,27 +11,15 @@
 //                 per workgroup, a wave = one feature x all rows) -> head3_out (one wave per row: LayerNorm, ReLU, dot with w2)
 //   backward (4): head3_row_bwd (one wave per row: dh through ReLU and LayerNorm) -> head3_fc_bwd (feature-parallel: every
 //                 per-feature gradient and dW1) -> head3_x_bwd (workgroup per sample: dx = dh W1, the LayerNorm backwards, d cls_m,
-//                 per-sample partials of the row-summed gradients) -> head3_rows_scatter (slab -> destinations, fixed order)
+//                 per-sample partials of the row-summed gradients) -> rows_scatter (slab -> destinations, fixed order)
 // plus the candidate mean over the present modalities (one launch each way) and the masked mean BCE over the present
 // (row, sample) pairs (one launch: loss and dlogit).  fp32 throughout.  Deterministic: no float atomics.
-#include "common.hip.h"
+// The pieces this head shares with the BatchNorm head (head.hip) -- the ie_demo row each way, the LN(cls) row forward, the dW1 and
+// dx loops, the slab scatter -- are the blocks of head_common.hip.h; the kernels are this file's.
+#include "head_common.hip.h"
 
 namespace {
 
-constexpr int D = 256, DX = 512, MAXB = 256, FPW = 4;  // d_model, head input width, most samples per call, features per workgroup
-inline int rows_per_lane(int B) { return B <= 64 ? 1 : (B <= 128 ? 2 : 4); }
-
-MTMP_DEV float block_sum(float v, float* red, int tid) {   // 256 threads -> every thread gets the sum
-    v = wave_sum(v);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-struct Shared3 {      // ie_demo.{0.weight[256][2],0.bias,1.weight,1.bias}, layer_norms_after_concat.{weight,bias}
-    const float* demo_w; const float* demo_b; const float* demo_g; const float* demo_be; const float* ln_g; const float* ln_b;
-};
 struct HeadSet {      // Linear(512,256), LayerNorm(256), Linear(256,1) of one row
     const float* w1; const float* b1; const float* g; const float* be; const float* w2; const float* b2;
 };
@@ -50,29 +38,10 @@ __global__ __launch_bounds__(256) void head3_x_kernel(Cls3<TC> cls, const float*
     const int c = 4 * lane;
     if (r < 3 * B) {
         const int m = r / B, b = r - m * B;
-        const f32x4 v = load4<TC>(cls.p[m] + (size_t)b * cls.ld[m] + c);
-        const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / D);
-        float d[4], sq = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { d[i] = v[i] - mean; sq += d[i] * d[i]; }
-        const float rstd = rsqrtf(wave_sum(sq) * (1.0f / D) + eps);
-        f32x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = fmaf(d[i] * rstd, p.ln_g[c + i], p.ln_b[c + i]);
-        *reinterpret_cast<f32x4*>(x + ((size_t)m * B + b) * DX + c) = o;
+        *reinterpret_cast<f32x4*>(x + ((size_t)m * B + b) * DX + c) = cls_row_fwd(cls.p[m] + (size_t)b * cls.ld[m], p, c, eps);
     } else {
         const int b = r - 3 * B;
-        const float a = age[b], g = gen[b];
-        float u[4], d[4], su = 0.f, sq = 0.f;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { u[i] = fmaf(a, p.demo_w[2 * (c + i)], fmaf(g, p.demo_w[2 * (c + i) + 1], p.demo_b[c + i])); su += u[i]; }
-        const float mean = wave_sum(su) * (1.0f / D);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { d[i] = u[i] - mean; sq += d[i] * d[i]; }
-        const float rstd = rsqrtf(wave_sum(sq) * (1.0f / D) + eps);
-        f32x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = fmaxf(fmaf(d[i] * rstd, p.demo_g[c + i], p.demo_be[c + i]), 0.f);
+        const f32x4 o = demo_row_fwd(age[b], gen[b], p, c, eps);
 #pragma unroll
         for (int m = 0; m < 3; ++m) *reinterpret_cast<f32x4*>(x + ((size_t)m * B + b) * DX + D + c) = o;
     }
@@ -88,7 +57,7 @@ __global__ __launch_bounds__(256) void head3_fc_kernel(const float* x, Sets3 ps,
     const HeadSet p = ps.s[m];
     const float* xm = x + (size_t)m * B * DX;
     const float* wrow = p.w1 + (size_t)j * DX;
-    float acc[R];
+    float acc[R];           // the tile product: inline here and in head_fc_kernel, not a block (head_common.hip.h says why)
 #pragma unroll
     for (int rr = 0; rr < R; ++rr) acc[rr] = 0.f;
     for (int k0 = 0; k0 < DX; k0 += 64) {
@@ -129,11 +98,8 @@ __global__ __launch_bounds__(256) void head3_out_kernel(float* h, float* rstd_ou
     const int c = 4 * lane;
     float* row = h + (size_t)r * D + c;
     const f32x4 v = *reinterpret_cast<const f32x4*>(row);
-    const float mean = wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.0f / D);
-    float d[4], sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { d[i] = v[i] - mean; sq += d[i] * d[i]; }
-    const float rstd = rsqrtf(wave_sum(sq) * (1.0f / D) + eps);
+    float d[4];
+    const float rstd = wave_ln4(v, v[0] + v[1] + v[2] + v[3], eps, d);
     f32x4 hh;
     float s = 0.f;
 #pragma unroll
@@ -206,14 +172,8 @@ __global__ __launch_bounds__(256) void head3_fc_bwd_kernel(const float* d_o, con
         }
         a_w2 += wave_sum(t_w2); a_g += wave_sum(t_g); a_b += wave_sum(t_b); a_b1 += wave_sum(t_b1); a_dl += wave_sum(t_dl);
         __syncthreads();
-        // dW1[j][k] = sum_b dh[m,b][j] x[m,b][k]: thread t owns columns t and t + 256 of the workgroup's four rows of W1
-        const float* xm = x + (size_t)m * B * DX;
-        float s0[FPW] = {0.f, 0.f, 0.f, 0.f}, s1[FPW] = {0.f, 0.f, 0.f, 0.f};
-        for (int r = 0; r < B; ++r) {
-            const float x0 = xm[(size_t)r * DX + tid], x1 = xm[(size_t)r * DX + D + tid];
-#pragma unroll
-            for (int f = 0; f < FPW; ++f) { s0[f] = fmaf(dhs[f][r], x0, s0[f]); s1[f] = fmaf(dhs[f][r], x1, s1[f]); }
-        }
+        float s0[FPW], s1[FPW];
+        dw1_rows(dhs, x + (size_t)m * B * DX, B, s0, s1);     // this row's dW1, finished on its own
 #pragma unroll
         for (int f = 0; f < FPW; ++f) { t0[f] += s0[f]; t1[f] += s1[f]; }
     }
@@ -227,7 +187,7 @@ __global__ __launch_bounds__(256) void head3_fc_bwd_kernel(const float* d_o, con
 }
 
 // sample-parallel backward: workgroup = sample b, thread = column k of each half of x; the three rows one after the other.
-// slab row b: [dln_g | dln_b | ddemo_g | ddemo_be | ddemo_w (interleaved [256][2], the parameter's own layout) | ddemo_b] = 7 x 256
+// Slab row b: demo_row_bwd, with ddemo_w interleaved.
 template <typename TC>
 __global__ __launch_bounds__(256) void head3_x_bwd_kernel(const float* dh, Cls3<TC> cls, const float* age, const float* gen,
                                                           Shared3 p, Sets3 ps, DCls3<TC> dcls, float* slab, int B, float eps) {
@@ -240,15 +200,10 @@ __global__ __launch_bounds__(256) void head3_x_bwd_kernel(const float* dh, Cls3<
         __syncthreads();
         dhr[k] = dh[((size_t)m * B + b) * D + k];
         __syncthreads();
-        const float* w1 = ps.s[m].w1;
-        float dxc = 0.f, dd = 0.f;
-        for (int j = 0; j < D; ++j) {
-            const float g = dhr[j];
-            dxc = fmaf(g, w1[(size_t)j * DX + k], dxc);
-            dd = fmaf(g, w1[(size_t)j * DX + D + k], dd);
-        }
+        float dxc, dd;
+        dx_row(dhr, ps.s[m].w1, k, dxc, dd);
         dxd += dd;
-        // LayerNorm(cls_m) backward
+        // LayerNorm(cls_m) backward: inline here and in head_x_bwd_kernel, not a block (head_common.hip.h says why)
         const float v = to_f32(cls.p[m][(size_t)b * cls.ld[m] + k]);
         const float mean = block_sum(v, red, k) * (1.0f / D);
         const float d = v - mean;
@@ -262,45 +217,7 @@ __global__ __launch_bounds__(256) void head3_x_bwd_kernel(const float* dh, Cls3<
     float* row = slab + (size_t)b * 7 * D;
     row[k] = s_g;
     row[D + k] = s_b;
-    // ie_demo backward
-    const float a = age[b], g = gen[b];
-    const float u = fmaf(a, p.demo_w[2 * k], fmaf(g, p.demo_w[2 * k + 1], p.demo_b[k]));
-    const float mean = block_sum(u, red, k) * (1.0f / D);
-    const float d = u - mean;
-    const float rstd = rsqrtf(block_sum(d * d, red, k) * (1.0f / D) + eps);
-    const float xh = d * rstd;
-    const float dyd = fmaf(xh, p.demo_g[k], p.demo_be[k]) > 0.f ? dxd : 0.f;
-    const float gy = dyd * p.demo_g[k];
-    const float m1 = block_sum(gy, red, k) * (1.0f / D), m2 = block_sum(gy * xh, red, k) * (1.0f / D);
-    const float du = rstd * (gy - m1 - xh * m2);
-    row[2 * D + k] = dyd * xh;
-    row[3 * D + k] = dyd;
-    row[4 * D + 2 * k] = du * a;
-    row[4 * D + 2 * k + 1] = du * g;
-    row[6 * D + k] = du;
-}
-
-// column sums of the slab, every 256-column block to a destination of its own (blocks 4 and 5 are the interleaved
-// ie_demo.0.weight gradient: one destination of 512).  A workgroup = 64 columns x 4 row lanes combined in a fixed order.
-struct RowDst { float* d[7]; };
-__global__ __launch_bounds__(256) void head3_rows_scatter_kernel(const float* slab, int rows, RowDst t) {
-    __shared__ float part[4][64];
-    const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6, c = blockIdx.x * 64 + cl;
-    float s0 = 0.f, s1 = 0.f;
-    int r = rl;
-    for (; r + 4 < rows; r += 8) {
-        s0 += slab[(size_t)r * 7 * D + c];
-        s1 += slab[(size_t)(r + 4) * 7 * D + c];
-    }
-    if (r < rows) s0 += slab[(size_t)r * 7 * D + c];
-    part[rl][cl] = s0 + s1;
-    __syncthreads();
-    if (rl == 0) {
-        const float s = (part[0][cl] + part[1][cl]) + (part[2][cl] + part[3][cl]);
-        const int blk = c / D, k = c - blk * D;
-        if (blk == 5) t.d[4][D + k] = s;
-        else t.d[blk][k] = s;
-    }
+    demo_row_bwd<true>(age[b], gen[b], p, dxd, eps, red, k, row);
 }
 
 // modalities present under pattern id c (trainer.py:68-77: 0 = all, 1 = report missing, 2 = image missing, 3 = both missing):
@@ -360,9 +277,6 @@ __global__ __launch_bounds__(256) void bce_masked_kernel(const float* o, const f
     if (threadIdx.x == 0) loss[0] = s / n;
 }
 
-inline Shared3 shared_of(const void* const* q) {
-    return Shared3{(const float*)q[0], (const float*)q[1], (const float*)q[2], (const float*)q[3], (const float*)q[4], (const float*)q[5]};
-}
 inline Sets3 sets_of(const void* const* q, int n_sets) {
     Sets3 s;
     for (int m = 0; m < 3; ++m) {
@@ -444,9 +358,7 @@ extern "C" int mtmp_head3_bwd(int cls_dtype, const float* d_out, const void* con
         hipLaunchKernelGGL(head3_x_bwd_kernel<bf16>, dim3(B), dim3(256), 0, st, (const float*)dh, c, age, gender, p, ps, dc, slab, B, ln_eps);
     }
     MTMP_CHECK_LAUNCH("mtmp_head3_bwd(x)");
-    // slab blocks: dln_g, dln_b, ddemo_g, ddemo_be, ddemo_w (two blocks, interleaved), ddemo_b
-    RowDst t{{dst[4], dst[5], dst[2], dst[3], dst[0], nullptr, dst[1]}};
-    hipLaunchKernelGGL(head3_rows_scatter_kernel, dim3(7 * D / 64), dim3(256), 0, st, (const float*)slab, B, t);
+    launch_rows_scatter(slab, B, dst, st);
     MTMP_CHECK_LAUNCH("mtmp_head3_bwd(scatter)");
     return MTMP_OK;
 }

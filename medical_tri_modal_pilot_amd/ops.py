@@ -1465,7 +1465,37 @@ class WindowAttnPadFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------- classification head (K10)
-HEAD_MAX_B = 256        # rows per rank the head kernels take (csrc/head.hip: one, two or four rows per lane)
+HEAD_MAX_B = 256        # rows per rank the head kernels take (csrc/head_common.hip.h: one, two or four rows per lane)
+
+
+def _head_params(prm):
+    """The parameters of a head as its kernels read them: fp32, contiguous."""
+    return [_c(t.detach().float()) for t in prm]
+
+
+def _head_param_grads(prm, launch):
+    """The parameter part of a head's backward: ``launch(dsts)`` writes every parameter's gradient to its destination -- the slices
+    of the flat gradient buffer when they can be overwritten (_sink_dsts; autograd gets None for them), else scratch that is
+    handed to autograd.  Returns the gradients in the order of ``prm``."""
+    sk = _sink_dsts(prm)
+    dsts = sk[2] if sk is not None else [torch.empty(t.numel(), dtype=torch.float32, device=t.device) for t in prm]
+    launch(dsts)
+    if sk is not None:
+        sk[0].mark_ready(sk[1])
+        return (None,) * len(dsts)
+    return tuple(t.view(q.shape) for t, q in zip(dsts, prm))
+
+
+def _saved_grad_once(ctx, g):
+    """Backward of a loss node that saved its gradient d at unit scale: d * g.  Under unit_grad() it is d itself, no launch.  The
+    saved tensor is then handed out as the gradient, so it is handed out ONCE: a second backward over the same graph
+    (retain_graph) gets a copy -- a consumer that accumulates in place into its incoming gradient must not reach into what is
+    saved here."""
+    (d,) = ctx.saved_tensors
+    if g is _UNIT_GRAD.get((g.device.type, g.device.index, g.dtype)) and not getattr(ctx, "handed_out", False):
+        ctx.handed_out = True
+        return d.view(ctx.shape)
+    return (d * g).view(ctx.shape)
 
 
 class HeadFn(torch.autograd.Function):
@@ -1485,19 +1515,17 @@ class HeadFn(torch.autograd.Function):
             raise ValueError(f"HeadFn handles up to {HEAD_MAX_B} rows per rank (got {B})")
         cls = _c(cls.detach() if cls.dtype in (torch.float32, torch.bfloat16) else cls.detach().float())
         age, gender = _c(age.detach().float()), _c(gender.detach().float())
-        P = [_c(t.detach().float()) for t in prm]
+        P = _head_params(prm)
         # order of include/mtmp.h: demo_w, demo_b, demo_g, demo_be, ln_g, ln_b, w1, b1, bn_g, bn_b, run_mean, run_var, w2, b2
-        ptrs = P[:10] + [run_mean, run_var] + P[10:]
-        table = (ctypes.c_void_p * 14)(*[t.data_ptr() for t in ptrs])
+        table = _ptrs(P[:10] + [run_mean, run_var] + P[10:])
         out = torch.empty(B, 1, dtype=torch.float32, device=cls.device)
         ws = torch.empty(_lib.lib().mtmp_head_ws_floats(B), dtype=torch.float32, device=cls.device)
         if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
             raise TypeError("HeadFn: num_batches_tracked must be an int64 device tensor")
-        call("mtmp_head_fwd_t", _dt(cls), _p(cls), _p(age), _p(gender), ctypes.cast(table, ctypes.c_void_p), _p(out), _p(ws), B, 1e-5,
+        call("mtmp_head_fwd_t", _dt(cls), _p(cls), _p(age), _p(gender), table, _p(out), _p(ws), B, 1e-5,
              float(bn_eps), float(momentum), int(bool(training)), _p(nbt), _stream())
         ctx.save_for_backward(cls, age, gender, ws, run_mean, run_var, *P)
         ctx.training = bool(training)
-        ctx.shapes = [t.shape for t in prm]
         ctx.prm = list(prm)
         return out
 
@@ -1505,21 +1533,13 @@ class HeadFn(torch.autograd.Function):
     def backward(ctx, d_out):
         cls, age, gender, ws, run_mean, run_var, *P = ctx.saved_tensors
         B, dev = cls.shape[0], cls.device
-        ptrs = P[:10] + [run_mean, run_var] + P[10:]
-        table = (ctypes.c_void_p * 14)(*[t.data_ptr() for t in ptrs])
+        table = _ptrs(P[:10] + [run_mean, run_var] + P[10:])
         d_out = _c(d_out.float().view(-1))
         dcls = torch.empty(B, D_MODEL, dtype=cls.dtype, device=dev)
         wsb = torch.empty(B * D_MODEL * 8, dtype=torch.float32, device=dev)
-        sk = _sink_dsts(ctx.prm)
-        dsts = sk[2] if sk is not None else [torch.empty(t.numel(), dtype=torch.float32, device=dev) for t in ctx.prm]
-        dtab = (ctypes.c_void_p * 12)(*[t.data_ptr() for t in dsts])
-        call("mtmp_head_bwd_scatter", _dt(cls), _p(d_out), _p(cls), _p(age), _p(gender), ctypes.cast(table, ctypes.c_void_p), _p(ws),
-             _p(dcls), ctypes.cast(dtab, ctypes.c_void_p), _p(wsb), B, 1e-5, int(ctx.training), _stream())
-        if sk is not None:
-            sk[0].mark_ready(sk[1])
-            grads = (None,) * 12
-        else:
-            grads = tuple(t.view(sh) for t, sh in zip(dsts, ctx.shapes))
+        grads = _head_param_grads(ctx.prm, lambda dsts: call(
+            "mtmp_head_bwd_scatter", _dt(cls), _p(d_out), _p(cls), _p(age), _p(gender), table, _p(ws),
+            _p(dcls), _ptrs(dsts), _p(wsb), B, 1e-5, int(ctx.training), _stream()))
         return (dcls, None, None, None, None, None, None, None, None) + grads
 
 
@@ -1539,14 +1559,7 @@ class BceLogitsMean(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        (d,) = ctx.saved_tensors
-        # loss.backward() through unit_grad(): d itself, no launch.  The saved tensor is handed out as the gradient, so it is
-        # handed out ONCE: a second backward over the same graph (retain_graph) gets a copy -- a consumer that accumulates in
-        # place into its incoming gradient must not reach into what is saved here
-        if g is _UNIT_GRAD.get((g.device.type, g.device.index, g.dtype)) and not getattr(ctx, "handed_out", False):
-            ctx.handed_out = True
-            return d.view(ctx.shape), None
-        return (d * g).view(ctx.shape), None
+        return _saved_grad_once(ctx, g), None
 
 
 _UNIT_GRAD = {}
@@ -1604,14 +1617,13 @@ class TriHeadFn(torch.autograd.Function):
         if cls[1].dtype != cls[0].dtype or cls[2].dtype != cls[0].dtype:
             cls = [t.float().contiguous() for t in cls]
         age, gender = _c(age.detach().float()), _c(gender.detach().float())
-        P = [_c(t.detach().float()) for t in prm]
+        P = _head_params(prm)
         n_sets = (len(prm) - 6) // 6
         out = torch.empty(3, B, dtype=torch.float32, device=cls[0].device)
         ws = torch.empty(_lib.lib().mtmp_head3_ws_floats(B), dtype=torch.float32, device=cls[0].device)
         call("mtmp_head3_fwd", _dt(cls[0]), _ptrs(cls), (ctypes.c_longlong * 3)(*[t.stride(0) for t in cls]), _p(age), _p(gender),
              _ptrs(P), n_sets, _p(out), _p(ws), B, 1e-5, _stream())
         ctx.save_for_backward(age, gender, ws, *cls, *P)
-        ctx.shapes = [t.shape for t in prm]
         ctx.prm = list(prm)
         return out
 
@@ -1623,15 +1635,9 @@ class TriHeadFn(torch.autograd.Function):
         d_out = _c(d_out.float())
         dcls = [torch.empty(B, D_MODEL, dtype=c0.dtype, device=dev) for _ in range(3)]
         wsb = torch.empty(_lib.lib().mtmp_head3_bwd_ws_floats(B), dtype=torch.float32, device=dev)
-        sk = _sink_dsts(ctx.prm)
-        dsts = sk[2] if sk is not None else [torch.empty(t.numel(), dtype=torch.float32, device=dev) for t in ctx.prm]
-        call("mtmp_head3_bwd", _dt(c0), _p(d_out), _ptrs(cls), (ctypes.c_longlong * 3)(*[t.stride(0) for t in cls]), _p(age),
-             _p(gender), _ptrs(P), (len(P) - 6) // 6, _p(ws), _ptrs(dcls), _ptrs(dsts), _p(wsb), B, 1e-5, _stream())
-        if sk is not None:
-            sk[0].mark_ready(sk[1])
-            grads = (None,) * len(dsts)
-        else:
-            grads = tuple(t.view(sh) for t, sh in zip(dsts, ctx.shapes))
+        grads = _head_param_grads(ctx.prm, lambda dsts: call(
+            "mtmp_head3_bwd", _dt(c0), _p(d_out), _ptrs(cls), (ctypes.c_longlong * 3)(*[t.stride(0) for t in cls]), _p(age),
+            _p(gender), _ptrs(P), (len(P) - 6) // 6, _p(ws), _ptrs(dcls), _ptrs(dsts), _p(wsb), B, 1e-5, _stream()))
         return (dcls[0], dcls[1], dcls[2], None, None) + grads
 
 
@@ -1699,12 +1705,7 @@ class BceMaskedMean(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        (d,) = ctx.saved_tensors
-        # (handed out once, like BceLogitsMean's)
-        if g is _UNIT_GRAD.get((g.device.type, g.device.index, g.dtype)) and not getattr(ctx, "handed_out", False):
-            ctx.handed_out = True
-            return d.view(ctx.shape), None, None
-        return (d * g).view(ctx.shape), None, None
+        return _saved_grad_once(ctx, g), None, None
 
 
 def bce_masked_mean(criterion, output, target, missing_num):

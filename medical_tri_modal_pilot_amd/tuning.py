@@ -35,8 +35,8 @@ PREFORK_IMAGE_ENCODER = True
 # "stream_order" = the order of round 4 (vital signs created first, issued last).  Measured in DESIGN section 7a.
 INPUT_NODE_ORDER = "long_last"
 # ops.StreamInputFn / ops.TieTimeEmbed backward: partial slabs + ONE mtmp_reduce_scatter launch that writes the parameters' slices of
-# the flat gradient (the event and time embeddings' backward as one launch, the bottleneck tokens' gradient through ops.BottSink)
-# instead of two reduction levels, a multi-tensor copy and the accumulation launches of the shared parameters per node.
+# the flat gradient (the event and time embeddings' backward as one launch) instead of two reduction levels, a multi-tensor copy
+# and the accumulation launches of the shared parameters per node.
 FUSED_INPUT_TAIL = True
 # tri_mbt_vsltcls (--berttype bert): the nn.Embedding(30000, 256) lookup and its gradient as ops.TokenEmbedFn (csrc/token_embed.hip:
 # touched rows written into the flat gradient) instead of F.embedding + cast and embedding_dense_backward + AccumulateGrad (a dense

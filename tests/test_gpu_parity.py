@@ -768,11 +768,13 @@ def test_time_embed_and_data_linear_vs_torch(ops, dt):
     check(f"data_linear[{str(dt)[6:]}].db", pb.grad, proj.bias.grad, 1e-4 if dt == torch.float32 else 3e-2)
 
 
-@pytest.mark.parametrize("training", [True, False])
-@pytest.mark.parametrize("B", [64, 5, 128, 200])
+# B: 65, 129 = the first sizes with two and four rows per lane, 256 = the most rows; 1 has no batch statistics (eval only)
+@pytest.mark.parametrize("B,training", [(b, t) for t in (True, False) for b in (64, 5, 128, 200, 65, 129, 256)] + [(1, False)])
 def test_head_vs_torch_modules(ops, training, B):
     """K10 (tri_mbt_vsltcls.py:59-76 ie_demo + :248-255 head): six HIP launches against the torch modules
-    (Linear, LayerNorm, BatchNorm1d with its running statistics, ReLU), forward, every gradient, running stats."""
+    (Linear, LayerNorm, BatchNorm1d with its running statistics, ReLU), forward, every gradient, running stats.
+    The fp32 case also runs the float-only entries mtmp_head_fwd / mtmp_head_bwd on the same inputs: the same kernels as HeadFn's
+    (bitwise equal) but for the seven row-summed gradients, whose slab is reduced in another fixed order."""
     torch.manual_seed(3)
     dm = torch.nn.Sequential(torch.nn.Linear(2, 256), torch.nn.LayerNorm(256), torch.nn.ReLU())
     ln = torch.nn.LayerNorm(256)
@@ -810,6 +812,31 @@ def test_head_vs_torch_modules(ops, training, B):
             assert float(a.grad.abs().max()) < 1e-4 * scale and float(b.grad.abs().max()) < 1e-4 * scale, nm
             continue
         check(f"{t}.d{nm}", a.grad, b.grad, 1e-4)
+    # mtmp_head_fwd / mtmp_head_bwd (float rows, no batch counter, gradients as g_rows[7][256] / dw1 / g_feat[4][256] / db2)
+    from medical_tri_modal_pilot_amd import _lib
+    f32 = dict(dtype=torch.float32, device=DEV)
+    P = [p_.detach().clone().to(DEV) for p_ in prm_mods]
+    rm1, rv1 = rm0.clone().to(DEV), rv0.clone().to(DEV)
+    table = ops._ptrs(P[:10] + [rm1, rv1] + P[10:])
+    c1, a1, g1, do1 = cd.detach().clone(), age.to(DEV), gen.to(DEV), w.to(DEV).view(-1).contiguous()
+    out1, ws1 = torch.empty(B, **f32), torch.empty(_lib.lib().mtmp_head_ws_floats(B), **f32)
+    _lib.call("mtmp_head_fwd", c1.data_ptr(), a1.data_ptr(), g1.data_ptr(), table, out1.data_ptr(), ws1.data_ptr(), B, 1e-5, 1e-5,
+              0.1, int(training), ops._stream())
+    dcls1, g_rows, dw1, g_feat, db2 = (torch.empty(*sh, **f32) for sh in ((B, 256), (7, 256), (256, 512), (4, 256), (1,)))
+    wsb1 = torch.empty(B * 256 * 8, **f32)
+    _lib.call("mtmp_head_bwd", do1.data_ptr(), c1.data_ptr(), a1.data_ptr(), g1.data_ptr(), table, ws1.data_ptr(), dcls1.data_ptr(),
+              g_rows.data_ptr(), dw1.data_ptr(), g_feat.data_ptr(), db2.data_ptr(), wsb1.data_ptr(), B, 1e-5, int(training), ops._stream())
+    g = dict(zip(names, (p_.grad for p_ in prm)))
+    for nm, a, b in (("out", out1, out.view(-1)), ("dcls", dcls1, cd.grad), ("dw1", dw1, g["w1"]), ("db1", g_feat[0], g["b1"]),
+                     ("dbn_g", g_feat[1], g["bn_g"]), ("dbn_b", g_feat[2], g["bn_b"]), ("dw2", g_feat[3], g["w2"].view(-1)),
+                     ("db2", db2, g["b2"]), ("running_mean", rm1, rm), ("running_var", rv1, rv)):
+        assert torch.equal(a, b), f"{t}.direct.{nm}"
+    tg = dict(zip(names, (p_.grad for p_ in prm_mods)))
+    for i, nm in enumerate(("ln_g", "ln_b", "demo_g", "demo_be", "demo_w0", "demo_w1", "demo_b")):
+        if training and nm == "ln_b":                          # (mathematically zero: see above)
+            assert float(g_rows[i].abs().max()) < 1e-4 * scale, nm
+            continue
+        check(f"{t}.direct.d{nm}", g_rows[i], tg["demo_w"][:, int(nm[-1])] if nm.startswith("demo_w") else tg[nm], 1e-4)
     if training:
         check(t + ".running_mean", rm, fc[1].running_mean, 1e-6)
         check(t + ".running_var", rv, fc[1].running_var, 1e-6)
