@@ -1419,35 +1419,11 @@ template <typename T> size_t fwd_smem() { return (size_t)2 * fwd_stage_elems<T>(
 template <typename T> size_t dq_smem() { return (size_t)2 * dq_stage_bytes<T>(); }
 template <typename T> size_t dkdv_smem() { return (size_t)2 * dkdv_stage_bytes<T>(); }
 
-template <typename K> int set_smem(K kern, size_t bytes) {
-    if (bytes > 48 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)bytes) != hipSuccess) {
-            mtmp_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu) failed", bytes);
-            return MTMP_ERR_LAUNCH;
-        }
-    }
-    return MTMP_OK;
-}
-
-// segments -> one grid: first[i] = first block of segment i (largest work first is the caller's business)
-template <typename A, typename F> Grouped<A> make_group(int n, const A* segs, F blocks_of, int& total) {
-    Grouped<A> g;
-    total = 0;
-    for (int i = 0; i < GRP_MAX; ++i) {
-        g.seg[i] = segs[i < n ? i : 0];
-        g.first[i] = total;
-        if (i < n) total += blocks_of(segs[i]);
-    }
-    g.first[GRP_MAX] = total;
-    return g;
-}
-
 template <typename T> int launch_fwd(int n, const AttnArgs<T>* segs, hipStream_t st) {
     int nwg;
     const Grouped<AttnArgs<T>> g = make_group(n, segs, [](const AttnArgs<T>& a) { return ((a.N + FWD_QWG - 1) / FWD_QWG) * a.H * a.B; }, nwg);
     const size_t sm = fwd_smem<T>();
-    if (int e = set_smem(attn_fwd_kernel<T>, sm)) return e;
+    if (int e = raise_lds("mtmp_attn_fwd", attn_fwd_kernel<T>, sm)) return e;
     hipLaunchKernelGGL(attn_fwd_kernel<T>, dim3(nwg), dim3(256), sm, st, g);
     MTMP_CHECK_LAUNCH("mtmp_attn_fwd");
     return MTMP_OK;
@@ -1456,7 +1432,7 @@ template <typename T> int launch_fwd(int n, const AttnArgs<T>* segs, hipStream_t
 template <typename T> int launch_bwd(int n, const AttnBwdArgs<T>* segs, hipStream_t st) {
     int nwg;
     const Grouped<AttnBwdArgs<T>> g = make_group(n, segs, [](const AttnBwdArgs<T>& a) { return ((a.N + 127) / 128) * a.H * a.B; }, nwg);
-    if (int e = set_smem(attn_bwd_dq_kernel<T>, dq_smem<T>())) return e;
+    if (int e = raise_lds("mtmp_attn_bwd", attn_bwd_dq_kernel<T>, dq_smem<T>())) return e;
     hipLaunchKernelGGL(attn_bwd_dq_kernel<T>, dim3(nwg), dim3(256), dq_smem<T>(), st, g);      // also writes delta
     MTMP_CHECK_LAUNCH("mtmp_attn_bwd(dq)");
     if constexpr (sizeof(T) == 2) {
@@ -1468,13 +1444,13 @@ template <typename T> int launch_bwd(int n, const AttnBwdArgs<T>* segs, hipStrea
             const Grouped<AttnBwdArgs<T>> g64 =
                 make_group(n, segs, [](const AttnBwdArgs<T>& a) { return ((a.N + DKV64_KEYS - 1) / DKV64_KEYS) * a.H * a.B; }, nwg64);
             const size_t sm64 = (size_t)BWD64_STAGES * dkdv_stage_bytes<T>() + 4 * DKV64_OUT_BYTES;
-            if (int e = set_smem(attn_bwd_dkdv64_kernel, sm64)) return e;
+            if (int e = raise_lds("mtmp_attn_bwd", attn_bwd_dkdv64_kernel, sm64)) return e;
             hipLaunchKernelGGL(attn_bwd_dkdv64_kernel, dim3(nwg64), dim3(256), sm64, st, g64);
             MTMP_CHECK_LAUNCH("mtmp_attn_bwd(dkdv64)");
             return MTMP_OK;
         }
     }
-    if (int e = set_smem(attn_bwd_dkdv_kernel<T>, dkdv_smem<T>())) return e;
+    if (int e = raise_lds("mtmp_attn_bwd", attn_bwd_dkdv_kernel<T>, dkdv_smem<T>())) return e;
     hipLaunchKernelGGL(attn_bwd_dkdv_kernel<T>, dim3(nwg), dim3(256), dkdv_smem<T>(), st, g);
     MTMP_CHECK_LAUNCH("mtmp_attn_bwd(dkdv)");
     return MTMP_OK;
@@ -1485,19 +1461,6 @@ bool attn_shape_ok(int B, int N, int H, int ld_a, int ld_b) {
 }
 
 }  // namespace
-
-template <typename T>
-int fwd_entry(int n, const void* const* q, const void* const* k, const void* const* v, void* const* o, const void* const* res,
-              void* const* o_res, float* const* lse, const int32_t* const* kv_len, const int32_t* const* row_start,
-              const float* const* key_norms, const int* N, const int* ld_qkv, const int* ld_o, int B, int H, float scale,
-              hipStream_t st) {
-    AttnArgs<T> a[GRP_MAX];
-    for (int i = 0; i < n; ++i)
-        a[i] = AttnArgs<T>{(const T*)q[i], (const T*)k[i], (const T*)v[i], (T*)o[i], res ? (const T*)res[i] : nullptr,
-                           o_res ? (T*)o_res[i] : nullptr, lse[i], kv_len ? kv_len[i] : nullptr, key_norms ? key_norms[i] : nullptr,
-                           B, N[i], H, ld_qkv[i], ld_o[i], scale, row_start ? row_start[i] : nullptr};
-    return launch_fwd<T>(n, a, st);
-}
 
 // n <= 3 streams in ONE launch (all arrays are HOST arrays of n entries; res / o_res / kv_len / row_start / key_norms may be NULL
 // as a whole or per entry).  mtmp_attn_fwd is the n = 1 form.  row_start[i] != NULL: stream i is PACKED -- int32[B] device, sample
@@ -1515,11 +1478,15 @@ extern "C" int mtmp_attn_fwd_grouped(int dtype, int n, const void* const* q, con
         MTMP_CHECK_ARG(attn_shape_ok(B, N[i], H, ld_qkv[i], ld_o[i]), "mtmp_attn_fwd: bad shape B=%d N=%d H=%d ld=%d/%d", B, N[i], H,
                        ld_qkv[i], ld_o[i]);
     }
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) return fwd_entry<float>(n, q, k, v, o, res, o_res, lse, kv_len, row_start, key_norms, N, ld_qkv, ld_o, B, H, scale, st);
-    if (dtype == 1) return fwd_entry<bf16>(n, q, k, v, o, res, o_res, lse, kv_len, row_start, key_norms, N, ld_qkv, ld_o, B, H, scale, st);
-    mtmp_set_error("mtmp_attn_fwd: unknown dtype %d", dtype);
-    return MTMP_ERR_ARG;
+    return with_dtype(dtype, "mtmp_attn_fwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        AttnArgs<T> a[GRP_MAX];
+        for (int i = 0; i < n; ++i)
+            a[i] = AttnArgs<T>{(const T*)q[i], (const T*)k[i], (const T*)v[i], (T*)o[i], res ? (const T*)res[i] : nullptr,
+                               o_res ? (T*)o_res[i] : nullptr, lse[i], kv_len ? kv_len[i] : nullptr, key_norms ? key_norms[i] : nullptr,
+                               B, N[i], H, ld_qkv[i], ld_o[i], scale, row_start ? row_start[i] : nullptr};
+        return launch_fwd<T>(n, a, (hipStream_t)stream);
+    });
 }
 
 extern "C" int mtmp_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* o, const void* res,
@@ -1527,19 +1494,6 @@ extern "C" int mtmp_attn_fwd(int dtype, const void* q, const void* k, const void
                              int ld_qkv, int ld_o, float scale, void* stream) {
     return mtmp_attn_fwd_grouped(dtype, 1, &q, &k, &v, &o, &res, &o_res, &lse, &kv_len, nullptr, &key_norms, &N, &ld_qkv, &ld_o, B, H,
                                  scale, stream);
-}
-
-template <typename T>
-int bwd_entry(int n, const void* const* q, const void* const* k, const void* const* v, const void* const* o, const void* const* d_o,
-              const float* const* lse, const int32_t* const* kv_len, const int32_t* const* row_start, void* const* dq,
-              void* const* dk, void* const* dv, float* const* delta_ws, const int* N, const int* ld_qkv, const int* ld_o,
-              const int* ld_do, const int* ld_dqkv, int B, int H, float scale, hipStream_t st) {
-    AttnBwdArgs<T> a[GRP_MAX];
-    for (int i = 0; i < n; ++i)
-        a[i] = AttnBwdArgs<T>{(const T*)q[i], (const T*)k[i], (const T*)v[i], (const T*)d_o[i], lse[i], delta_ws[i],
-                              kv_len ? kv_len[i] : nullptr, (T*)dq[i], (T*)dk[i], (T*)dv[i], B, N[i], H, ld_qkv[i], ld_do[i],
-                              ld_dqkv[i], scale, (const T*)o[i], ld_o[i], row_start ? row_start[i] : nullptr};
-    return launch_bwd<T>(n, a, st);
 }
 
 extern "C" int mtmp_attn_bwd_grouped(int dtype, int n, const void* const* q, const void* const* k, const void* const* v,
@@ -1556,13 +1510,15 @@ extern "C" int mtmp_attn_bwd_grouped(int dtype, int n, const void* const* q, con
         MTMP_CHECK_ARG(attn_shape_ok(B, N[i], H, ld_qkv[i], ld_o[i]) && attn_shape_ok(B, N[i], H, ld_do[i], ld_dqkv[i]),
                        "mtmp_attn_bwd: bad shape B=%d N=%d H=%d", B, N[i], H);
     }
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0)
-        return bwd_entry<float>(n, q, k, v, o, d_o, lse, kv_len, row_start, dq, dk, dv, delta_ws, N, ld_qkv, ld_o, ld_do, ld_dqkv, B, H, scale, st);
-    if (dtype == 1)
-        return bwd_entry<bf16>(n, q, k, v, o, d_o, lse, kv_len, row_start, dq, dk, dv, delta_ws, N, ld_qkv, ld_o, ld_do, ld_dqkv, B, H, scale, st);
-    mtmp_set_error("mtmp_attn_bwd: unknown dtype %d", dtype);
-    return MTMP_ERR_ARG;
+    return with_dtype(dtype, "mtmp_attn_bwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        AttnBwdArgs<T> a[GRP_MAX];
+        for (int i = 0; i < n; ++i)
+            a[i] = AttnBwdArgs<T>{(const T*)q[i], (const T*)k[i], (const T*)v[i], (const T*)d_o[i], lse[i], delta_ws[i],
+                                  kv_len ? kv_len[i] : nullptr, (T*)dq[i], (T*)dk[i], (T*)dv[i], B, N[i], H, ld_qkv[i], ld_do[i],
+                                  ld_dqkv[i], scale, (const T*)o[i], ld_o[i], row_start ? row_start[i] : nullptr};
+        return launch_bwd<T>(n, a, (hipStream_t)stream);
+    });
 }
 
 extern "C" int mtmp_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* d_o,
@@ -1793,20 +1749,15 @@ extern "C" int mtmp_attn_cls_fwd(int dtype, const void* q, const void* k, const 
     MTMP_CHECK_ARG(attn_cls_ok(B, N, H, cls_tok, ld_qkv) && ld_res >= H * DH && (!row_start || kv_len),
                    "mtmp_attn_cls_fwd: bad argument (B=%d N=%d H=%d cls=%d ld=%d)", B, N, H, cls_tok, ld_qkv);
     const size_t sm = ((size_t)N + 4 + 32 * DH) * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) {
-        AttnClsArgs<float> a{(const float*)q, (const float*)k, (const float*)v, ld_qkv, (const float*)res, ld_res, (float*)o_cls,
-                             (float*)r1_cls, lse, nullptr, nullptr, nullptr, nullptr, 0, kv_len, row_start, B, N, H, cls_tok, scale};
-        if (int e = set_smem(attn_cls_fwd_kernel<float>, sm)) return e;
-        hipLaunchKernelGGL(attn_cls_fwd_kernel<float>, dim3(B * H), dim3(256), sm, st, a);
-    } else if (dtype == 1) {
-        AttnClsArgs<bf16> a{(const bf16*)q, (const bf16*)k, (const bf16*)v, ld_qkv, (const bf16*)res, ld_res, (bf16*)o_cls,
-                            (bf16*)r1_cls, lse, nullptr, nullptr, nullptr, nullptr, 0, kv_len, row_start, B, N, H, cls_tok, scale};
-        if (int e = set_smem(attn_cls_fwd_kernel<bf16>, sm)) return e;
-        hipLaunchKernelGGL(attn_cls_fwd_kernel<bf16>, dim3(B * H), dim3(256), sm, st, a);
-    } else { mtmp_set_error("mtmp_attn_cls_fwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_attn_cls_fwd");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_attn_cls_fwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        AttnClsArgs<T> a{(const T*)q, (const T*)k, (const T*)v, ld_qkv, (const T*)res, ld_res, (T*)o_cls, (T*)r1_cls, lse,
+                         nullptr, nullptr, nullptr, nullptr, 0, kv_len, row_start, B, N, H, cls_tok, scale};
+        if (int e = raise_lds("mtmp_attn_cls_fwd", attn_cls_fwd_kernel<T>, sm)) return e;
+        hipLaunchKernelGGL(attn_cls_fwd_kernel<T>, dim3(B * H), dim3(256), sm, (hipStream_t)stream, a);
+        MTMP_CHECK_LAUNCH("mtmp_attn_cls_fwd");
+        return MTMP_OK;
+    });
 }
 
 // Backward of the above: d_o [B, H * 64] (gradient w.r.t. o_cls) -> dq, dk, dv written for EVERY row of every sample (dq is zero
@@ -1819,21 +1770,15 @@ extern "C" int mtmp_attn_cls_bwd(int dtype, const void* q, const void* k, const 
     MTMP_CHECK_ARG(attn_cls_ok(B, N, H, cls_tok, ld_qkv) && ld_dqkv >= H * DH && (!row_start || kv_len),
                    "mtmp_attn_cls_bwd: bad argument (B=%d N=%d H=%d cls=%d ld=%d)", B, N, H, cls_tok, ld_qkv);
     const size_t sm = ((size_t)2 * N + 4 + 32 * DH) * sizeof(float);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) {
-        AttnClsArgs<float> a{(const float*)q, (const float*)k, (const float*)v, ld_qkv, nullptr, 0, (float*)o_cls, nullptr,
-                             (float*)lse, (const float*)d_o, (float*)dq, (float*)dk, (float*)dv, ld_dqkv, kv_len, row_start, B, N, H,
-                             cls_tok, scale};
-        if (int e = set_smem(attn_cls_bwd_kernel<float>, sm)) return e;
-        hipLaunchKernelGGL(attn_cls_bwd_kernel<float>, dim3(B * H), dim3(256), sm, st, a);
-    } else if (dtype == 1) {
-        AttnClsArgs<bf16> a{(const bf16*)q, (const bf16*)k, (const bf16*)v, ld_qkv, nullptr, 0, (bf16*)o_cls, nullptr, (float*)lse,
-                            (const bf16*)d_o, (bf16*)dq, (bf16*)dk, (bf16*)dv, ld_dqkv, kv_len, row_start, B, N, H, cls_tok, scale};
-        if (int e = set_smem(attn_cls_bwd_kernel<bf16>, sm)) return e;
-        hipLaunchKernelGGL(attn_cls_bwd_kernel<bf16>, dim3(B * H), dim3(256), sm, st, a);
-    } else { mtmp_set_error("mtmp_attn_cls_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_attn_cls_bwd");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_attn_cls_bwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        AttnClsArgs<T> a{(const T*)q, (const T*)k, (const T*)v, ld_qkv, nullptr, 0, (T*)o_cls, nullptr, (float*)lse, (const T*)d_o,
+                         (T*)dq, (T*)dk, (T*)dv, ld_dqkv, kv_len, row_start, B, N, H, cls_tok, scale};
+        if (int e = raise_lds("mtmp_attn_cls_bwd", attn_cls_bwd_kernel<T>, sm)) return e;
+        hipLaunchKernelGGL(attn_cls_bwd_kernel<T>, dim3(B * H), dim3(256), sm, (hipStream_t)stream, a);
+        MTMP_CHECK_LAUNCH("mtmp_attn_cls_bwd");
+        return MTMP_OK;
+    });
 }
 
 #ifdef MTMP_LAB_CLOCK
@@ -1847,12 +1792,12 @@ extern "C" int mtmp_key_norms(int dtype, const void* k, float* out, long long ro
     MTMP_CHECK_ARG(k && out, "mtmp_key_norms: null pointer");
     MTMP_CHECK_ARG(rows > 0 && rows < (1ll << 31) && H > 0 && H <= 4 && ld >= H * DH && (ld % 8) == 0,
                    "mtmp_key_norms: bad shape rows=%lld H=%d ld=%d", rows, H, ld);
-    hipStream_t st = (hipStream_t)stream;
     const int nblk = (int)((rows + 31) / 32);
-    if (dtype == 0) hipLaunchKernelGGL(key_norms_kernel<float>, dim3((nblk + 3) / 4), dim3(256), 0, st, (const float*)k, out, (int)rows, H, ld);
-    else if (dtype == 1) hipLaunchKernelGGL(key_norms_kernel<bf16>, dim3((nblk + 3) / 4), dim3(256), 0, st, (const bf16*)k, out, (int)rows, H, ld);
-    else { mtmp_set_error("mtmp_key_norms: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_key_norms");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_key_norms", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(key_norms_kernel<T>, dim3((nblk + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const T*)k, out, (int)rows, H, ld);
+        MTMP_CHECK_LAUNCH("mtmp_key_norms");
+        return MTMP_OK;
+    });
 }
 

@@ -348,3 +348,38 @@ void mtmp_set_error(const char* fmt, ...);
             return MTMP_ERR_LAUNCH;                                              \
         }                                                                        \
     } while (0)
+
+// Host helpers shared by the C entry points ("Where an entry's host code lives").
+// with_dtype(dtype, who, f): f(DtypeTag<float>{}) for dtype 0, f(DtypeTag<bf16>{}) for dtype 1, anything else is refused as
+// "<who>: unknown dtype".  f is a generic lambda that names its element type as `typename decltype(tag)::type` and returns the
+// entry's status, so MTMP_CHECK_ARG / MTMP_CHECK_LAUNCH inside it return from the entry.
+template <typename T> struct DtypeTag { using type = T; };
+template <typename F> int with_dtype(int dtype, const char* who, F&& f) {
+    if (dtype == 0) return f(DtypeTag<float>{});
+    if (dtype == 1) return f(DtypeTag<bf16>{});
+    mtmp_set_error("%s: unknown dtype %d", who, dtype);
+    return MTMP_ERR_ARG;
+}
+
+// a kernel that asks for more than the default 48 KB of dynamic LDS needs its limit raised before the launch
+template <typename K> int raise_lds(const char* who, K kern, size_t bytes) {
+    if (bytes > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)bytes) != hipSuccess) {
+        mtmp_set_error("%s: cannot raise dynamic LDS to %zu bytes", who, bytes);
+        return MTMP_ERR_LAUNCH;
+    }
+    return MTMP_OK;
+}
+
+// segments -> one grid (Grouped): first[i] = first block of segment i; unused entries repeat segment 0 behind the end of the grid
+template <typename A, typename F> Grouped<A> make_group(int n, const A* segs, F blocks_of, int& total) {
+    Grouped<A> g;
+    total = 0;
+    for (int i = 0; i < GRP_MAX; ++i) {
+        g.seg[i] = segs[i < n ? i : 0];
+        g.first[i] = total;
+        if (i < n) total += blocks_of(segs[i]);
+    }
+    g.first[GRP_MAX] = total;
+    return g;
+}

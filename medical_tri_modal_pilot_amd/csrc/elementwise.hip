@@ -609,17 +609,15 @@ extern "C" int mtmp_ln_bwd(int dtype, const void* z, int ldz, const float* stats
     MTMP_CHECK_ARG(M > 0 && ldz >= D && ldz % 4 == 0 && (!d_res || (ldr >= D && ldr % 4 == 0)), "mtmp_ln_bwd: bad shape");
     hipStream_t st = (hipStream_t)stream;
     const int nb = grid_for_rows(M);
-    if (dtype == 0)
-        hipLaunchKernelGGL(ln_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)z, ldz, stats, gamma,
-                           (const float*)dy, (const float*)d_res, ldr, (float*)dz, M, eps, ws);
-    else if (dtype == 1)
-        hipLaunchKernelGGL(ln_bwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, (const bf16*)z, ldz, stats, gamma,
-                           (const bf16*)dy, (const bf16*)d_res, ldr, (bf16*)dz, M, eps, ws);
-    else { mtmp_set_error("mtmp_ln_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_ln_bwd");
-    launch_slab_reduce(ws, nb, 2 * D, ws + (size_t)nb * 2 * D, dgamma_dbeta, st);
-    MTMP_CHECK_LAUNCH("mtmp_ln_bwd(reduce)");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_ln_bwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(ln_bwd_kernel<T>, dim3(nb), dim3(256), 0, st, (const T*)z, ldz, stats, gamma, (const T*)dy,
+                           (const T*)d_res, ldr, (T*)dz, M, eps, ws);
+        MTMP_CHECK_LAUNCH("mtmp_ln_bwd");
+        launch_slab_reduce(ws, nb, 2 * D, ws + (size_t)nb * 2 * D, dgamma_dbeta, st);
+        MTMP_CHECK_LAUNCH("mtmp_ln_bwd(reduce)");
+        return MTMP_OK;
+    });
 }
 
 // out[n,256] = TIE embedding of events[n,3]; params [8][256] fp32, ftab [20][256] fp32.
@@ -627,26 +625,27 @@ namespace {
 int launch_tie_fwd(int dtype, const float* events, const float* params, const float* ftab, void* out, int rows,
                    const int* cu, int t_pad, hipStream_t st, const char* who, bool val = true) {
     const int nb = max(1, min((rows + 3) / 4, 2048));
-    if (dtype == 0 && val) hipLaunchKernelGGL(tie_fwd_kernel<float>, dim3(nb), dim3(256), 0, st, events, params, ftab, (float*)out, rows, cu, t_pad);
-    else if (dtype == 1 && val) hipLaunchKernelGGL(tie_fwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, events, params, ftab, (bf16*)out, rows, cu, t_pad);
-    else if (dtype == 0) hipLaunchKernelGGL((tie_fwd_kernel<float, false>), dim3(nb), dim3(256), 0, st, events, params, ftab, (float*)out, rows, cu, t_pad);
-    else if (dtype == 1) hipLaunchKernelGGL((tie_fwd_kernel<bf16, false>), dim3(nb), dim3(256), 0, st, events, params, ftab, (bf16*)out, rows, cu, t_pad);
-    else { mtmp_set_error("%s: unknown dtype %d", who, dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH(who);
-    return MTMP_OK;
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const auto kern = val ? tie_fwd_kernel<T, true> : tie_fwd_kernel<T, false>;
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, st, events, params, ftab, (T*)out, rows, cu, t_pad);
+        MTMP_CHECK_LAUNCH(who);
+        return MTMP_OK;
+    });
 }
 int tie_bwd_blocks(int rows) { return max(1, min((rows + 3) / 4, 512)); }
 int launch_tie_bwd_partials(int dtype, const float* events, const float* params, const void* d_out, float* ws, int rows, const int* cu,
                             int t_pad, hipStream_t st, const char* who, bool val, const float* ev2 = nullptr, const void* d2a = nullptr,
                             const void* d2b = nullptr, int n2 = 0, int n2a = 0) {
     const int nb = tie_bwd_blocks(rows + n2);
-    if (dtype == 0 && val) hipLaunchKernelGGL(tie_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, events, params, (const float*)d_out, rows, ws, cu, t_pad, ev2, (const float*)d2a, (const float*)d2b, n2, n2a);
-    else if (dtype == 1 && val) hipLaunchKernelGGL(tie_bwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, events, params, (const bf16*)d_out, rows, ws, cu, t_pad, ev2, (const bf16*)d2a, (const bf16*)d2b, n2, n2a);
-    else if (dtype == 0) hipLaunchKernelGGL((tie_bwd_kernel<float, false>), dim3(nb), dim3(256), 0, st, events, params, (const float*)d_out, rows, ws, cu, t_pad, ev2, (const float*)d2a, (const float*)d2b, n2, n2a);
-    else if (dtype == 1) hipLaunchKernelGGL((tie_bwd_kernel<bf16, false>), dim3(nb), dim3(256), 0, st, events, params, (const bf16*)d_out, rows, ws, cu, t_pad, ev2, (const bf16*)d2a, (const bf16*)d2b, n2, n2a);
-    else { mtmp_set_error("%s: unknown dtype %d", who, dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH(who);
-    return MTMP_OK;
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        const auto kern = val ? tie_bwd_kernel<T, true> : tie_bwd_kernel<T, false>;
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, st, events, params, (const T*)d_out, rows, ws, cu, t_pad, ev2, (const T*)d2a,
+                           (const T*)d2b, n2, n2a);
+        MTMP_CHECK_LAUNCH(who);
+        return MTMP_OK;
+    });
 }
 int launch_tie_bwd(int dtype, const float* events, const float* params, const void* d_out, float* grads, float* ws,
                    int rows, const int* cu, int t_pad, hipStream_t st, const char* who, bool val = true) {
@@ -735,12 +734,12 @@ extern "C" int mtmp_hourly_embed_fwd(int dtype, const float* x, const float* w, 
                                      void* stream) {
     MTMP_CHECK_ARG(x && w && params && out && n > 0 && F >= 1 && F <= HOURLY_F, "mtmp_hourly_embed_fwd: bad argument (n=%d F=%d)", n, F);
     const int nb = max(1, min((n + 3) / 4, 2048));
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) hipLaunchKernelGGL(hourly_fwd_kernel<float>, dim3(nb), dim3(256), 0, st, x, w, params, (float*)out, n, F);
-    else if (dtype == 1) hipLaunchKernelGGL(hourly_fwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, x, w, params, (bf16*)out, n, F);
-    else { mtmp_set_error("mtmp_hourly_embed_fwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_hourly_embed_fwd");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_hourly_embed_fwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(hourly_fwd_kernel<T>, dim3(nb), dim3(256), 0, (hipStream_t)stream, x, w, params, (T*)out, n, F);
+        MTMP_CHECK_LAUNCH("mtmp_hourly_embed_fwd");
+        return MTMP_OK;
+    });
 }
 
 extern "C" int mtmp_hourly_embed_bwd_ws_floats(int n, int F) { return hourly_bwd_blocks(n) * (F + 3) * D; }
@@ -753,13 +752,14 @@ extern "C" int mtmp_hourly_embed_bwd(int dtype, const float* x, const float* w, 
                    "mtmp_hourly_embed_bwd: bad argument (n=%d F=%d)", n, F);
     const int nb = hourly_bwd_blocks(n);
     hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) hipLaunchKernelGGL(hourly_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, x, w, params, (const float*)d_out, ws, n, F);
-    else if (dtype == 1) hipLaunchKernelGGL(hourly_bwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, x, w, params, (const bf16*)d_out, ws, n, F);
-    else { mtmp_set_error("mtmp_hourly_embed_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_hourly_embed_bwd");
-    launch_slab_reduce(ws, nb, (F + 3) * D, nullptr, grads, st);     // nb <= 64: one level, the tail is not used
-    MTMP_CHECK_LAUNCH("mtmp_hourly_embed_bwd(reduce)");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_hourly_embed_bwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(hourly_bwd_kernel<T>, dim3(nb), dim3(256), 0, st, x, w, params, (const T*)d_out, ws, n, F);
+        MTMP_CHECK_LAUNCH("mtmp_hourly_embed_bwd");
+        launch_slab_reduce(ws, nb, (F + 3) * D, nullptr, grads, st);     // nb <= 64: one level, the tail is not used
+        MTMP_CHECK_LAUNCH("mtmp_hourly_embed_bwd(reduce)");
+        return MTMP_OK;
+    });
 }
 
 extern "C" int mtmp_stream_input_ws_floats(int rows) { return (max(1, min((rows + 15) / 16, 1024)) + RED_GROUPS) * 7 * D; }
@@ -768,24 +768,32 @@ extern "C" int mtmp_stream_input_ws_floats(int rows) { return (max(1, min((rows 
 // bott [nb][256] fp32; stats float[B*(N+1)][2] (mean, 1/sqrt(var+eps)) kept for the backward.
 // row_start != NULL (with kv_len, both int32 device, mtmp_row_starts): PACKED output -- rows r < kv_len[b] of sample b go to
 // rows row_start[b] + r of `out` (same allocation), the others are not written.
+namespace {
+// who: the entry that was called; add == NULL, add_L == 1 are the kernel's defaults (no added rows)
+int stream_input_fwd(const char* who, int dtype, const void* x, const float* cls, const float* gamma, const float* beta,
+                     const float* pe, const float* bott, void* out, float* stats, int B, int N, int nb, float eps, float p,
+                     unsigned seed, const unsigned* seed_dev, const int32_t* row_start, const int32_t* kv_len, const void* add,
+                     int add_L, void* stream) {
+    MTMP_CHECK_ARG(x && cls && gamma && beta && out && stats && B > 0 && N > 0 && nb >= 0 && nb <= NB_MAX && (nb == 0 || bott) &&
+                       p >= 0.f && p < 1.f && (long long)B * (nb + 1 + N) < (1ll << 25) && (!row_start || kv_len) && add_L > 0 &&
+                       (!add || ((long long)B * N) % add_L == 0),
+                   "%s: bad argument (B=%d N=%d nb=%d p=%f add_L=%d)", who, B, N, nb, p, add_L);
+    const int rows = B * (nb + 1 + N), nbk = max(1, min((rows + 3) / 4, 2048));
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(stream_in_fwd_kernel<T>, dim3(nbk), dim3(256), 0, (hipStream_t)stream, (const T*)x, cls, gamma, beta, pe,
+                           bott, (T*)out, stats, B, N, nb, eps, p, seed, seed_dev, row_start, kv_len, (const T*)add, add_L);
+        MTMP_CHECK_LAUNCH(who);
+        return MTMP_OK;
+    });
+}
+}  // namespace
 extern "C" int mtmp_stream_input_fwd(int dtype, const void* x, const float* cls, const float* gamma, const float* beta,
                                      const float* pe, const float* bott, void* out, float* stats, int B, int N, int nb,
                                      float eps, float p, unsigned seed, const unsigned* seed_dev, const int32_t* row_start,
                                      const int32_t* kv_len, void* stream) {
-    MTMP_CHECK_ARG(x && cls && gamma && beta && out && stats && B > 0 && N > 0 && nb >= 0 && nb <= NB_MAX && (nb == 0 || bott) &&
-                       p >= 0.f && p < 1.f && (long long)B * (nb + 1 + N) < (1ll << 25) && (!row_start || kv_len),
-                   "mtmp_stream_input_fwd: bad argument (B=%d N=%d nb=%d p=%f)", B, N, nb, p);
-    hipStream_t st = (hipStream_t)stream;
-    const int rows = B * (nb + 1 + N), nbk = max(1, min((rows + 3) / 4, 2048));
-    if (dtype == 0)
-        hipLaunchKernelGGL(stream_in_fwd_kernel<float>, dim3(nbk), dim3(256), 0, st, (const float*)x, cls, gamma, beta, pe,
-                           bott, (float*)out, stats, B, N, nb, eps, p, seed, seed_dev, row_start, kv_len);
-    else if (dtype == 1)
-        hipLaunchKernelGGL(stream_in_fwd_kernel<bf16>, dim3(nbk), dim3(256), 0, st, (const bf16*)x, cls, gamma, beta, pe,
-                           bott, (bf16*)out, stats, B, N, nb, eps, p, seed, seed_dev, row_start, kv_len);
-    else { mtmp_set_error("mtmp_stream_input_fwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_stream_input_fwd");
-    return MTMP_OK;
+    return stream_input_fwd("mtmp_stream_input_fwd", dtype, x, cls, gamma, beta, pe, bott, out, stats, B, N, nb, eps, p, seed, seed_dev,
+                            row_start, kv_len, nullptr, 1, stream);
 }
 
 // mtmp_stream_input_fwd with `add` [B N / add_L][256] (dtype, may be NULL): row (b N + t) / add_L is added to input token (b, t) in
@@ -795,21 +803,8 @@ extern "C" int mtmp_stream_input_fwd_add(int dtype, const void* x, const float* 
                                          const float* pe, const float* bott, void* out, float* stats, int B, int N, int nb,
                                          float eps, float p, unsigned seed, const unsigned* seed_dev, const int32_t* row_start,
                                          const int32_t* kv_len, const void* add, int add_L, void* stream) {
-    MTMP_CHECK_ARG(x && cls && gamma && beta && out && stats && B > 0 && N > 0 && nb >= 0 && nb <= NB_MAX && (nb == 0 || bott) &&
-                       p >= 0.f && p < 1.f && (long long)B * (nb + 1 + N) < (1ll << 25) && (!row_start || kv_len) && add_L > 0 &&
-                       (!add || ((long long)B * N) % add_L == 0),
-                   "mtmp_stream_input_fwd_add: bad argument (B=%d N=%d nb=%d p=%f add_L=%d)", B, N, nb, p, add_L);
-    hipStream_t st = (hipStream_t)stream;
-    const int rows = B * (nb + 1 + N), nbk = max(1, min((rows + 3) / 4, 2048));
-    if (dtype == 0)
-        hipLaunchKernelGGL(stream_in_fwd_kernel<float>, dim3(nbk), dim3(256), 0, st, (const float*)x, cls, gamma, beta, pe,
-                           bott, (float*)out, stats, B, N, nb, eps, p, seed, seed_dev, row_start, kv_len, (const float*)add, add_L);
-    else if (dtype == 1)
-        hipLaunchKernelGGL(stream_in_fwd_kernel<bf16>, dim3(nbk), dim3(256), 0, st, (const bf16*)x, cls, gamma, beta, pe,
-                           bott, (bf16*)out, stats, B, N, nb, eps, p, seed, seed_dev, row_start, kv_len, (const bf16*)add, add_L);
-    else { mtmp_set_error("mtmp_stream_input_fwd_add: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_stream_input_fwd_add");
-    return MTMP_OK;
+    return stream_input_fwd("mtmp_stream_input_fwd_add", dtype, x, cls, gamma, beta, pe, bott, out, stats, B, N, nb, eps, p, seed,
+                            seed_dev, row_start, kv_len, add, add_L, stream);
 }
 
 // dx [B, N, 256] (dtype); grads float[7][256] = dgamma, dbeta, dcls, dbott[0..3] (rows past nb are zero),
@@ -821,15 +816,13 @@ int launch_stream_in_bwd(int dtype, const void* dz, const void* x, const float* 
                          float* ws, int B, int N, int nb, float p, unsigned seed, const unsigned* seed_dev, const int32_t* row_start,
                          const int32_t* kv_len, hipStream_t st, const char* who) {
     const int nbk = stream_in_bwd_blocks(B * (nb + 1 + N));
-    if (dtype == 0)
-        hipLaunchKernelGGL(stream_in_bwd_kernel<float>, dim3(nbk), dim3(256), 0, st, (const float*)dz, (const float*)x, cls,
-                           gamma, stats, (float*)dx, ws, B, N, nb, p, seed, seed_dev, row_start, kv_len);
-    else if (dtype == 1)
-        hipLaunchKernelGGL(stream_in_bwd_kernel<bf16>, dim3(nbk), dim3(256), 0, st, (const bf16*)dz, (const bf16*)x, cls,
-                           gamma, stats, (bf16*)dx, ws, B, N, nb, p, seed, seed_dev, row_start, kv_len);
-    else { mtmp_set_error("%s: unknown dtype %d", who, dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH(who);
-    return MTMP_OK;
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(stream_in_bwd_kernel<T>, dim3(nbk), dim3(256), 0, st, (const T*)dz, (const T*)x, cls, gamma, stats,
+                           (T*)dx, ws, B, N, nb, p, seed, seed_dev, row_start, kv_len);
+        MTMP_CHECK_LAUNCH(who);
+        return MTMP_OK;
+    });
 }
 }  // namespace
 extern "C" int mtmp_stream_input_bwd(int dtype, const void* dz, const void* x, const float* cls, const float* gamma,
@@ -885,11 +878,11 @@ extern "C" int mtmp_token_sums(int dtype, int n, const void* const* dx, void* co
         q.dx[i] = dx[k]; q.out[i] = out[k]; q.rows[i] = i < n ? rows[k] : 0; q.L[i] = L[k];
         total += q.rows[i];
     }
-    if (dtype == 0) hipLaunchKernelGGL(token_sums_kernel<float>, dim3(total), dim3(256), 0, (hipStream_t)stream, q);
-    else if (dtype == 1) hipLaunchKernelGGL(token_sums_kernel<bf16>, dim3(total), dim3(256), 0, (hipStream_t)stream, q);
-    else { mtmp_set_error("mtmp_token_sums: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_token_sums");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_token_sums", [&](auto tag) {
+        hipLaunchKernelGGL(token_sums_kernel<typename decltype(tag)::type>, dim3(total), dim3(256), 0, (hipStream_t)stream, q);
+        MTMP_CHECK_LAUNCH("mtmp_token_sums");
+        return MTMP_OK;
+    });
 }
 
 // The stream-input backward of up to three token streams in ONE launch, partial slabs only: ws receives the streams' slabs back to
@@ -928,11 +921,11 @@ extern "C" int mtmp_stream_input_bwd_grouped(int dtype, int n, const void* const
         }
     }
     g.first[SI_MAX] = total;
-    if (dtype == 0) hipLaunchKernelGGL(stream_in_bwd_grouped_kernel<float>, dim3(total), dim3(256), 0, (hipStream_t)stream, g);
-    else if (dtype == 1) hipLaunchKernelGGL(stream_in_bwd_grouped_kernel<bf16>, dim3(total), dim3(256), 0, (hipStream_t)stream, g);
-    else { mtmp_set_error("mtmp_stream_input_bwd_grouped: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_stream_input_bwd_grouped");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_stream_input_bwd_grouped", [&](auto tag) {
+        hipLaunchKernelGGL(stream_in_bwd_grouped_kernel<typename decltype(tag)::type>, dim3(total), dim3(256), 0, (hipStream_t)stream, g);
+        MTMP_CHECK_LAUNCH("mtmp_stream_input_bwd_grouped");
+        return MTMP_OK;
+    });
 }
 // The same launch, PARTIAL slabs only: ws receives [mtmp_stream_input_slab_rows(B * (nb+1+N))][7][256] floats (dgamma, dbeta, dcls,
 // dbott[0..3]) for mtmp_reduce_scatter.
@@ -1042,20 +1035,14 @@ extern "C" int mtmp_bottleneck_exchange_fwd(int dtype, void* z_v, void* z_i, voi
                                             const int32_t* row_start_v, void* stream) {
     MTMP_CHECK_ARG(z_v && z_i && missing && B > 0 && n_v >= 4 && n_i >= 4 && (!z_t || n_t >= 4) && (!resbottle || prev),
                    "mtmp_bottleneck_exchange_fwd: bad argument (B=%d rows %d/%d/%d)", B, n_v, n_i, n_t);
-    if (dtype == 0) {
-        ExchangeArgs<float> a{{(float*)z_v, (float*)z_i, (float*)z_t}, {(long long)n_v * D, (long long)n_i * D, (long long)n_t * D},
-                              missing, prev, keep, nullptr, nullptr, resbottle, row_start_v};
-        hipLaunchKernelGGL(exchange_fwd_kernel<float>, dim3(B * 4), dim3(256), 0, (hipStream_t)stream, a);
-    } else if (dtype == 1) {
-        ExchangeArgs<bf16> a{{(bf16*)z_v, (bf16*)z_i, (bf16*)z_t}, {(long long)n_v * D, (long long)n_i * D, (long long)n_t * D},
-                             missing, prev, keep, nullptr, nullptr, resbottle, row_start_v};
-        hipLaunchKernelGGL(exchange_fwd_kernel<bf16>, dim3(B * 4), dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        mtmp_set_error("mtmp_bottleneck_exchange_fwd: unknown dtype %d", dtype);
-        return MTMP_ERR_ARG;
-    }
-    MTMP_CHECK_LAUNCH("mtmp_bottleneck_exchange_fwd");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_bottleneck_exchange_fwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        ExchangeArgs<T> a{{(T*)z_v, (T*)z_i, (T*)z_t}, {(long long)n_v * D, (long long)n_i * D, (long long)n_t * D},
+                          missing, prev, keep, nullptr, nullptr, resbottle, row_start_v};
+        hipLaunchKernelGGL(exchange_fwd_kernel<T>, dim3(B * 4), dim3(256), 0, (hipStream_t)stream, a);
+        MTMP_CHECK_LAUNCH("mtmp_bottleneck_exchange_fwd");
+        return MTMP_OK;
+    });
 }
 
 // Backward of the exchange, in place on the gradient buffers dz_m [B, n_m, 256] (rows 0..3): see
@@ -1065,20 +1052,14 @@ extern "C" int mtmp_bottleneck_exchange_bwd(int dtype, void* dz_v, void* dz_i, v
                                             float* d_prev_out, const int32_t* row_start_v, void* stream) {
     MTMP_CHECK_ARG(dz_v && dz_i && missing && B > 0 && n_v >= 4 && n_i >= 4 && (!dz_t || n_t >= 4) && (!resbottle || d_prev_out),
                    "mtmp_bottleneck_exchange_bwd: bad argument (B=%d rows %d/%d/%d)", B, n_v, n_i, n_t);
-    if (dtype == 0) {
-        ExchangeArgs<float> a{{(float*)dz_v, (float*)dz_i, (float*)dz_t}, {(long long)n_v * D, (long long)n_i * D, (long long)n_t * D},
-                              missing, nullptr, nullptr, d_prev_in, d_prev_out, resbottle, row_start_v};
-        hipLaunchKernelGGL(exchange_bwd_kernel<float>, dim3(B * 4), dim3(256), 0, (hipStream_t)stream, a);
-    } else if (dtype == 1) {
-        ExchangeArgs<bf16> a{{(bf16*)dz_v, (bf16*)dz_i, (bf16*)dz_t}, {(long long)n_v * D, (long long)n_i * D, (long long)n_t * D},
-                             missing, nullptr, nullptr, d_prev_in, d_prev_out, resbottle, row_start_v};
-        hipLaunchKernelGGL(exchange_bwd_kernel<bf16>, dim3(B * 4), dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        mtmp_set_error("mtmp_bottleneck_exchange_bwd: unknown dtype %d", dtype);
-        return MTMP_ERR_ARG;
-    }
-    MTMP_CHECK_LAUNCH("mtmp_bottleneck_exchange_bwd");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_bottleneck_exchange_bwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        ExchangeArgs<T> a{{(T*)dz_v, (T*)dz_i, (T*)dz_t}, {(long long)n_v * D, (long long)n_i * D, (long long)n_t * D},
+                          missing, nullptr, nullptr, d_prev_in, d_prev_out, resbottle, row_start_v};
+        hipLaunchKernelGGL(exchange_bwd_kernel<T>, dim3(B * 4), dim3(256), 0, (hipStream_t)stream, a);
+        MTMP_CHECK_LAUNCH("mtmp_bottleneck_exchange_bwd");
+        return MTMP_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------

@@ -1502,23 +1502,11 @@ int tn_splits(int M, int N, int K, int target_wgs) {
     return s < 1 ? 1 : s;
 }
 
-// segments -> one grid: first[i] = first block of segment i; unused entries repeat segment 0 behind the end of the grid
-template <typename A, typename F> Grouped<A> make_group(int n, const A* segs, F blocks_of, int& total) {
-    Grouped<A> g;
-    total = 0;
-    for (int i = 0; i < GRP_MAX; ++i) {
-        g.seg[i] = segs[i < n ? i : 0];
-        g.first[i] = total;
-        if (i < n) total += blocks_of(segs[i]);
-    }
-    g.first[GRP_MAX] = total;
-    return g;
-}
-
 // mode: 0 forward (relu / dropout from the arguments; a.signs != nullptr with relu: also write the sign bits), 1 gate by a.signs
 // n segments (token streams) in one launch: same N / activation / dropout switch / sign bits / key-norm table in all of them
 int launch_ln_gemm_dma(int n, const GemmArgs<bf16>* segs, int relu, int gate, hipStream_t st) {
     using P = PanelDma;
+    static_assert(P::lds_bytes > 48 * 1024, "every launch of this kernel raises its dynamic LDS limit");
     const GemmArgs<bf16>& a = segs[0];
     const bool drop = a.drop_p > 0.f, signs = !gate && relu && a.signs;
     for (int i = 1; i < n; ++i)
@@ -1527,17 +1515,15 @@ int launch_ln_gemm_dma(int n, const GemmArgs<bf16>* segs, int relu, int gate, hi
             mtmp_set_error("mtmp_ln_gemm (grouped): the streams of one launch must agree in N, dropout, sign bits and key norms");
             return MTMP_ERR_ARG;
         }
-    const void* fs[7] = {(const void*)ln_gemm_dma_kernel<false, false, false, false>, (const void*)ln_gemm_dma_kernel<false, true, false, false>,
-                         (const void*)ln_gemm_dma_kernel<true, false, false, false>, (const void*)ln_gemm_dma_kernel<true, true, false, false>,
-                         (const void*)ln_gemm_dma_kernel<true, false, false, true>, (const void*)ln_gemm_dma_kernel<true, true, false, true>,
-                         (const void*)ln_gemm_dma_kernel<false, false, true, false>};
-    const bool knorm = a.knorm != nullptr;           // (the Q/K/V projection: no activation, no dropout, N = 768)
-    const int which = gate ? 6 : signs ? 4 + (drop ? 1 : 0) : (relu ? 2 : 0) + (drop ? 1 : 0);
-    const void* fk = (const void*)ln_gemm_dma_kernel<false, false, false, false, true>;
-    if (hipFuncSetAttribute(knorm ? fk : fs[which], hipFuncAttributeMaxDynamicSharedMemorySize, (int)P::lds_bytes) != hipSuccess) {
-        mtmp_set_error("mtmp_ln_gemm: cannot raise dynamic LDS to %zu", P::lds_bytes);
-        return MTMP_ERR_LAUNCH;
-    }
+    // the instantiations in use, <RELU, DROP, GATE, SIGNS, KNORM>: the Q/K/V projection (key norms: no activation, no dropout,
+    // N = 768), the sign-gated dH, FFN1 with sign bits, the plain forward
+    const bool knorm = a.knorm != nullptr;
+    const auto kern = knorm   ? ln_gemm_dma_kernel<false, false, false, false, true>
+                      : gate  ? ln_gemm_dma_kernel<false, false, true, false>
+                      : signs ? (drop ? ln_gemm_dma_kernel<true, true, false, true> : ln_gemm_dma_kernel<true, false, false, true>)
+                      : relu  ? (drop ? ln_gemm_dma_kernel<true, true, false, false> : ln_gemm_dma_kernel<true, false, false, false>)
+                              : (drop ? ln_gemm_dma_kernel<false, true, false, false> : ln_gemm_dma_kernel<false, false, false, false>);
+    if (int e = raise_lds("mtmp_ln_gemm", kern, P::lds_bytes)) return e;
     // as launch_ln_gemm below; a workgroup's bias block in LDS holds at most MAXP panels
     int mtiles;
     const Grouped<GemmArgs<bf16>> g = make_group(n, segs, [](const GemmArgs<bf16>& x) { return (x.M + BM - 1) / BM; }, mtiles);
@@ -1546,78 +1532,44 @@ int launch_ln_gemm_dma(int n, const GemmArgs<bf16>* segs, int relu, int gate, hi
     nsplit = nsplit < 1 ? 1 : (nsplit > npanels ? npanels : nsplit);
     const int need = (npanels + P::MAXP - 1) / P::MAXP;
     if (nsplit < need) nsplit = need;
-    dim3 grid(mtiles, nsplit);
-    if (knorm) {
-        hipLaunchKernelGGL((ln_gemm_dma_kernel<false, false, false, false, true>), grid, dim3(256), P::lds_bytes, st, g);
-        MTMP_CHECK_LAUNCH("mtmp_ln_gemm_qkv");
-        return MTMP_OK;
-    }
-    switch (which) {
-    case 0: hipLaunchKernelGGL((ln_gemm_dma_kernel<false, false, false, false>), grid, dim3(256), P::lds_bytes, st, g); break;
-    case 1: hipLaunchKernelGGL((ln_gemm_dma_kernel<false, true, false, false>), grid, dim3(256), P::lds_bytes, st, g); break;
-    case 2: hipLaunchKernelGGL((ln_gemm_dma_kernel<true, false, false, false>), grid, dim3(256), P::lds_bytes, st, g); break;
-    case 3: hipLaunchKernelGGL((ln_gemm_dma_kernel<true, true, false, false>), grid, dim3(256), P::lds_bytes, st, g); break;
-    case 4: hipLaunchKernelGGL((ln_gemm_dma_kernel<true, false, false, true>), grid, dim3(256), P::lds_bytes, st, g); break;
-    case 5: hipLaunchKernelGGL((ln_gemm_dma_kernel<true, true, false, true>), grid, dim3(256), P::lds_bytes, st, g); break;
-    default: hipLaunchKernelGGL((ln_gemm_dma_kernel<false, false, true, false>), grid, dim3(256), P::lds_bytes, st, g); break;
-    }
-    MTMP_CHECK_LAUNCH("mtmp_ln_gemm");
+    hipLaunchKernelGGL(kern, dim3(mtiles, nsplit), dim3(256), P::lds_bytes, st, g);
+    MTMP_CHECK_LAUNCH(knorm ? "mtmp_ln_gemm_qkv" : "mtmp_ln_gemm");
     return MTMP_OK;
 }
 template <typename T>
-int launch_ln_gemm(GemmArgs<T> a, int relu, hipStream_t st) {
+int launch_ln_gemm(const GemmArgs<T>& a, int relu, hipStream_t st) {
     const size_t sm = Panel<T>::lds_bytes;
     if (a.N % Panel<T>::NP != 0) {
         mtmp_set_error("mtmp_ln_gemm: N=%d must be a multiple of %d for this dtype", a.N, Panel<T>::NP);
         return MTMP_ERR_ARG;
     }
     if constexpr (sizeof(T) == 2) return launch_ln_gemm_dma(1, &a, relu, 0, st);
-    if (sm > 48 * 1024) {
-        const void* fs[4] = {(const void*)ln_gemm_kernel<T, false, false>, (const void*)ln_gemm_kernel<T, false, true>,
-                             (const void*)ln_gemm_kernel<T, true, false>, (const void*)ln_gemm_kernel<T, true, true>};
-        const void* f = fs[(relu ? 2 : 0) + (a.drop_p > 0.f ? 1 : 0)];
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
-            mtmp_set_error("mtmp_ln_gemm: cannot raise dynamic LDS to %zu", sm);
-            return MTMP_ERR_LAUNCH;
-        }
-    }
+    // (RELU, DROP) are template parameters: no per-element selects in the epilogue
+    const bool drop = a.drop_p > 0.f;
+    const auto kern = relu ? (drop ? ln_gemm_kernel<T, true, true> : ln_gemm_kernel<T, true, false>)
+                           : (drop ? ln_gemm_kernel<T, false, true> : ln_gemm_kernel<T, false, false>);
+    if (int e = raise_lds("mtmp_ln_gemm", kern, sm)) return e;
     // one workgroup per 128 rows walks all panels when the row blocks alone fill the chip (2 per CU);
     // otherwise the panels of a row block are split over gridDim.y workgroups
     const int mtiles = (a.M + BM - 1) / BM, npanels = a.N / Panel<T>::NP;
     int nsplit = 512 / mtiles;
     nsplit = nsplit < 1 ? 1 : (nsplit > npanels ? npanels : nsplit);
-    dim3 grid(mtiles, nsplit);
-    const bool drop = a.drop_p > 0.f;         // (RELU, DROP) are template parameters: no per-element selects in the epilogue
-    if (relu && drop)       hipLaunchKernelGGL((ln_gemm_kernel<T, true, true>), grid, dim3(256), sm, st, a);
-    else if (relu)          hipLaunchKernelGGL((ln_gemm_kernel<T, true, false>), grid, dim3(256), sm, st, a);
-    else if (drop)          hipLaunchKernelGGL((ln_gemm_kernel<T, false, true>), grid, dim3(256), sm, st, a);
-    else                    hipLaunchKernelGGL((ln_gemm_kernel<T, false, false>), grid, dim3(256), sm, st, a);
+    hipLaunchKernelGGL(kern, dim3(mtiles, nsplit), dim3(256), sm, st, a);
     MTMP_CHECK_LAUNCH("mtmp_ln_gemm");
     return MTMP_OK;
 }
 template <typename T, int TM>
 int launch_gemm_nt_tm(int n, const GemmArgs<T>* segs, int relu, hipStream_t st) {
-    const GemmArgs<T>& a = segs[0];
     size_t sm = (size_t)(TM + BN) * LDW * sizeof(T);
     const size_t stage = (size_t)TM * LDO * sizeof(T);
     if (sm < stage) sm = stage;
-    if (sm > 48 * 1024) {
-        const void* fs[4] = {(const void*)gemm_nt_kernel<T, false, TM, false>, (const void*)gemm_nt_kernel<T, false, TM, true>,
-                             (const void*)gemm_nt_kernel<T, true, TM, false>, (const void*)gemm_nt_kernel<T, true, TM, true>};
-        const void* f = fs[(relu ? 2 : 0) + (a.drop_p > 0.f ? 1 : 0)];
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
-            mtmp_set_error("mtmp_gemm_nt: cannot raise dynamic LDS to %zu", sm);
-            return MTMP_ERR_LAUNCH;
-        }
-    }
+    const bool drop = segs[0].drop_p > 0.f;
+    const auto kern = relu ? (drop ? gemm_nt_kernel<T, true, TM, true> : gemm_nt_kernel<T, true, TM, false>)
+                           : (drop ? gemm_nt_kernel<T, false, TM, true> : gemm_nt_kernel<T, false, TM, false>);
+    if (int e = raise_lds("mtmp_gemm_nt", kern, sm)) return e;
     int nwg;
     const Grouped<GemmArgs<T>> g = make_group(n, segs, [](const GemmArgs<T>& x) { return ((x.M + TM - 1) / TM) * ((x.N + BN - 1) / BN); }, nwg);
-    dim3 grid(nwg);
-    const bool drop = a.drop_p > 0.f;
-    if (relu && drop)       hipLaunchKernelGGL((gemm_nt_kernel<T, true, TM, true>), grid, dim3(256), sm, st, g);
-    else if (relu)          hipLaunchKernelGGL((gemm_nt_kernel<T, true, TM, false>), grid, dim3(256), sm, st, g);
-    else if (drop)          hipLaunchKernelGGL((gemm_nt_kernel<T, false, TM, true>), grid, dim3(256), sm, st, g);
-    else                    hipLaunchKernelGGL((gemm_nt_kernel<T, false, TM, false>), grid, dim3(256), sm, st, g);
+    hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), sm, st, g);
     MTMP_CHECK_LAUNCH("mtmp_gemm_nt");
     return MTMP_OK;
 }
@@ -1764,23 +1716,17 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void gemm_lnbwd_kern
 }
 
 template <typename T>
-int launch_gemm_lnbwd(int n, LnBwdGemmArgs<T>* segs, float* const* dgamma_dbeta, float* const* ws, hipStream_t st) {
+int launch_gemm_lnbwd(int n, const LnBwdGemmArgs<T>* segs, float* const* dgamma_dbeta, hipStream_t st) {
     size_t sm = (size_t)(128 + 256) * LDW * sizeof(T);
     const size_t stage = (size_t)128 * LDXT * sizeof(T);
     if (sm < stage) sm = stage;
     if (sm < 4 * 2 * 256 * sizeof(float)) sm = 4 * 2 * 256 * sizeof(float);
-    if (sm > 48 * 1024 && hipFuncSetAttribute((const void*)gemm_lnbwd_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                              (int)sm) != hipSuccess) {
-        mtmp_set_error("mtmp_gemm_lnbwd: cannot raise dynamic LDS to %zu", sm);
-        return MTMP_ERR_LAUNCH;
-    }
-    for (int i = 0; i < n; ++i) {
-        segs[i].slab = ws[i];
+    if (int e = raise_lds("mtmp_gemm_lnbwd", gemm_lnbwd_kernel<T>, sm)) return e;
+    for (int i = 0; i < n; ++i)
         if (segs[i].K != segs[0].K) {
             mtmp_set_error("mtmp_gemm_lnbwd (grouped): the streams of one launch must agree in K");
             return MTMP_ERR_ARG;
         }
-    }
     int nb;
     const Grouped<LnBwdGemmArgs<T>> g = make_group(n, segs, [](const LnBwdGemmArgs<T>& x) { return (x.M + 127) / 128; }, nb);
     hipLaunchKernelGGL(gemm_lnbwd_kernel<T>, dim3(nb), dim3(256), sm, st, g);
@@ -1788,7 +1734,7 @@ int launch_gemm_lnbwd(int n, LnBwdGemmArgs<T>* segs, float* const* dgamma_dbeta,
     for (int i = 0; i < n; ++i) {
         if (!dgamma_dbeta || !dgamma_dbeta[i]) continue;      // partials only: the caller reduces them (mtmp_reduce_batch)
         const int nbi = (segs[i].M + 127) / 128;
-        launch_slab_reduce(ws[i], nbi, 512, ws[i] + (size_t)nbi * 512, dgamma_dbeta[i], st);
+        launch_slab_reduce(segs[i].slab, nbi, 512, segs[i].slab + (size_t)nbi * 512, dgamma_dbeta[i], st);
         MTMP_CHECK_LAUNCH("mtmp_gemm_lnbwd(reduce)");
     }
     return MTMP_OK;
@@ -1829,54 +1775,47 @@ int tn_reduce_slabs(const float* ws, float* dw, float* db, int splits, int N, in
     MTMP_CHECK_LAUNCH("mtmp_gemm_tn(reduce)");
     return MTMP_OK;
 }
+// gemm_tn_kernel<bf16> is never launched (bf16 takes the transposing-read kernels below) but has always been part of the library
+template __global__ void gemm_tn_kernel<bf16>(TnArgs<bf16>);
+
+// a: tn_args with the split count and mode of tn_launch_splits; dw != nullptr: also reduce the slabs into dw / db
 template <typename T>
-int launch_gemm_tn(const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N, int K, int ldy, int ldx,
-                   const int* m_live, hipStream_t st) {
+int launch_gemm_tn(const TnArgs<T>& a, int mode, float* dw, float* db, hipStream_t st) {
     constexpr bool TR = sizeof(T) == 2;                    // bf16: transposing-read kernels, eight waves per CU
-    int mode;
-    const int splits = tn_launch_splits(TR, M, N, K, &mode);
-    int rps = (M + splits - 1) / splits;
-    rps = (rps + TK - 1) / TK * TK;
-    TnArgs<T> a{(const T*)dy, (const T*)x, ws, M, N, K, ldy, ldx, splits, rps};
-    a.m_live = m_live;
+    const int M = a.M, N = a.N, K = a.K, splits = a.splits;
+    const char* who = "mtmp_gemm_tn";
     if (mode == 4) {
         const size_t sm = (size_t)256 * LDX * sizeof(T);
-        if (sm > 48 * 1024 && hipFuncSetAttribute((const void*)gemm_tn_edge_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                  (int)sm) != hipSuccess) {
-            mtmp_set_error("mtmp_gemm_tn: cannot raise dynamic LDS to %zu", sm);
-            return MTMP_ERR_LAUNCH;
-        }
+        if (int e = raise_lds(who, gemm_tn_edge_kernel<T>, sm)) return e;
         hipLaunchKernelGGL(gemm_tn_edge_kernel<T>, dim3(splits * ((N + 127) / 128) * ((K + 127) / 128)), dim3(256), sm, st, a);
-        MTMP_CHECK_LAUNCH("mtmp_gemm_tn");
-        return dw ? tn_reduce_slabs(ws, dw, db, splits, N, K, st) : MTMP_OK;
-    }
-    // the DMA kernel needs 16-byte aligned rows and 32-bit byte offsets; operands that are not get the register-staged kernel
-    // at the same split count
-    const bool dma = mode >= 2 && ldy % 8 == 0 && ldx % 8 == 0 && (uintptr_t)dy % 16 == 0 && (uintptr_t)x % 16 == 0 &&
-                     (unsigned long long)M * (unsigned)(ldy > ldx ? ldy : ldx) * 2ull < (1ull << 32);
-    const bool two = mode == 1 || (mode == 3 && !dma);
-    const bool wide = mode == 2;
-    const size_t sm = dma ? (wide ? (size_t)TnDma<2>::DNS * TnDma<2>::DSTAGE : (size_t)TnDma<1>::DNS * TnDma<1>::DSTAGE) : TR ? (size_t)(two ? 8 : 4) * TT * LDG * sizeof(bf16) : (size_t)256 * LDX * sizeof(T);
-    const void* fn = dma ? (wide ? (const void*)gemm_tn_dma_kernel<2> : (const void*)gemm_tn_dma_kernel<1>)
-                         : TR ? (two ? (const void*)gemm_tn_tr_kernel<2> : (const void*)gemm_tn_tr_kernel<1>) : (const void*)gemm_tn_kernel<T>;
-    if (sm > 48 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
-        mtmp_set_error("mtmp_gemm_tn: cannot raise dynamic LDS to %zu", sm);
-        return MTMP_ERR_LAUNCH;
-    }
-    const dim3 grid(splits * (N / 128) * (K / 128)), grid_w(splits * (N / 128) * (K / 256));
-    if constexpr (TR) {
-        int nwg;
-        const Grouped<TnArgs<bf16>> g = make_group(1, &a, [&](const TnArgs<bf16>& x) { return (int)(wide ? grid_w.x : grid.x); }, nwg);
-        if (dma && wide) hipLaunchKernelGGL(gemm_tn_dma_kernel<2>, grid_w, dim3(512), sm, st, g);
-        else if (dma) hipLaunchKernelGGL(gemm_tn_dma_kernel<1>, grid, dim3(512), sm, st, g);
-        else if (two) hipLaunchKernelGGL(gemm_tn_tr_kernel<2>, grid, dim3(512), sm, st, a);
-        else     hipLaunchKernelGGL(gemm_tn_tr_kernel<1>, grid, dim3(256), sm, st, a);
+    } else if constexpr (TR) {
+        // the DMA kernel needs 16-byte aligned rows and 32-bit byte offsets; operands that are not get the register-staged kernel
+        // at the same split count
+        const bool dma = mode >= 2 && a.ldy % 8 == 0 && a.ldx % 8 == 0 && (uintptr_t)a.dy % 16 == 0 && (uintptr_t)a.x % 16 == 0 &&
+                         (unsigned long long)M * (unsigned)(a.ldy > a.ldx ? a.ldy : a.ldx) * 2ull < (1ull << 32);
+        const bool two = mode == 1 || (mode == 3 && !dma), wide = mode == 2;
+        const dim3 grid(splits * (N / 128) * (K / (dma && wide ? 256 : 128)));
+        if (dma) {
+            const auto kern = wide ? gemm_tn_dma_kernel<2> : gemm_tn_dma_kernel<1>;
+            const size_t sm = wide ? (size_t)TnDma<2>::DNS * TnDma<2>::DSTAGE : (size_t)TnDma<1>::DNS * TnDma<1>::DSTAGE;
+            if (int e = raise_lds(who, kern, sm)) return e;
+            int nwg;
+            const Grouped<TnArgs<bf16>> g = make_group(1, &a, [&](const TnArgs<bf16>&) { return (int)grid.x; }, nwg);
+            hipLaunchKernelGGL(kern, grid, dim3(512), sm, st, g);
+        } else {
+            const auto kern = two ? gemm_tn_tr_kernel<2> : gemm_tn_tr_kernel<1>;
+            const size_t sm = (size_t)(two ? 8 : 4) * TT * LDG * sizeof(bf16);
+            if (int e = raise_lds(who, kern, sm)) return e;
+            hipLaunchKernelGGL(kern, grid, dim3(two ? 512 : 256), sm, st, a);
+        }
     } else {
-        hipLaunchKernelGGL(gemm_tn_kernel<T>, grid, dim3(256), sm, st, a);
+        const size_t sm = (size_t)256 * LDX * sizeof(T);
+        if (int e = raise_lds(who, gemm_tn_kernel<T>, sm)) return e;
+        hipLaunchKernelGGL(gemm_tn_kernel<T>, dim3(splits * (N / 128) * (K / 128)), dim3(256), sm, st, a);
     }
-    MTMP_CHECK_LAUNCH("mtmp_gemm_tn");
+    MTMP_CHECK_LAUNCH(who);
     if (!dw) return MTMP_OK;                                  // partials only: the caller reduces them (mtmp_reduce_batch)
-    return tn_reduce_slabs(ws, dw, db, splits, N, K, st);
+    return tn_reduce_slabs(a.slab, dw, db, splits, N, K, st);
 }
 
 // Grouped weight gradients (bf16, LDS-DMA kernel): the same product of up to three token streams in one launch, partial slabs
@@ -1897,12 +1836,10 @@ int tn_group_plan(int n, const int* M, int N, int K, int* splits) {
     }
     return 0;
 }
-int launch_gemm_tn_grouped(int n, TnArgs<bf16>* segs, hipStream_t st) {
+int launch_gemm_tn_grouped(int n, const TnArgs<bf16>* segs, hipStream_t st) {
     const size_t sm = (size_t)TnDma<1>::DNS * TnDma<1>::DSTAGE;
-    if (hipFuncSetAttribute((const void*)gemm_tn_dma_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
-        mtmp_set_error("mtmp_gemm_tn: cannot raise dynamic LDS to %zu", sm);
-        return MTMP_ERR_LAUNCH;
-    }
+    static_assert((size_t)TnDma<1>::DNS * TnDma<1>::DSTAGE > 48 * 1024, "every launch of this kernel raises its dynamic LDS limit");
+    if (int e = raise_lds("mtmp_gemm_tn_grouped", gemm_tn_dma_kernel<1>, sm)) return e;
     int nwg;
     const Grouped<TnArgs<bf16>> g = make_group(n, segs, [](const TnArgs<bf16>& x) { return x.splits * (x.N / 128) * (x.K / 128); }, nwg);
     hipLaunchKernelGGL(gemm_tn_dma_kernel<1>, dim3(nwg), dim3(512), sm, st, g);
@@ -1912,35 +1849,144 @@ int launch_gemm_tn_grouped(int n, TnArgs<bf16>* segs, hipStream_t st) {
 
 }  // namespace
 
+// ---- argument builders: ONE per product.  A builder checks one token stream's arguments and fills the kernel's argument struct
+// by field name; the single entry calls it once, the _grouped entry once per stream, and both hand the result to the launcher they
+// share -- so the single form IS a group of one.  Options that only the single form has (gate, row scale, fp32, the reduction into
+// dw / db / dgamma_dbeta) are builder or launcher parameters for which the grouped entry passes the neutral value.
+// who = the entry that was called, i = the stream (0 in the single form).
+namespace {
+template <typename P> P opt(const P* arr, int i) { return arr ? arr[i] : P{}; }      // entry i of an optional host array
+
+// LayerNorm-fed projection y = drop(act(LN(x) w^T + bias)), K = 256 (FFN1; the activation is the launcher's `relu`).
+// want_signs: also the sign bits of the output (bf16 row-panel kernel, ReLU).
+template <typename T>
+int ln_gemm_args(GemmArgs<T>& g, const char* who, int i, const void* x, const float* gamma, const float* beta, const void* w,
+                 const float* bias, void* y, void* xn, float* stats, int M, int N, int ldx, int ldy, float eps, float drop_p,
+                 unsigned seed, const unsigned* seed_dev, bool want_signs, void* signs, const int* m_live) {
+    MTMP_CHECK_ARG(x && gamma && beta && w && y && (!want_signs || signs), "%s: null pointer (stream %d)", who, i);
+    MTMP_CHECK_ARG(M > 0 && N > 0 && N % 32 == 0 && ldx >= 256 && ldx % 8 == 0 && ldy >= N && ldy % 8 == 0,
+                   "%s: bad shape M=%d N=%d ldx=%d ldy=%d (K is fixed at 256; stream %d)", who, M, N, ldx, ldy, i);
+    MTMP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (double)M * N < 4294967296.0, "%s: bad dropout %f (stream %d)", who, drop_p, i);
+    MTMP_CHECK_ARG(!want_signs || (sizeof(T) == 2 && N % PanelDma::NP == 0), "%s: sign bits: bf16 and N %% 64 == 0 only", who);
+    g = GemmArgs<T>{};
+    g.a = (const T*)x; g.w = (const T*)w; g.bias = bias; g.y = (T*)y;
+    g.gamma = gamma; g.beta = beta; g.xn = (T*)xn; g.stats = stats;
+    g.M = M; g.N = N; g.K = 256; g.lda = ldx; g.ldy = ldy;
+    g.eps = eps; g.drop_p = drop_p; g.seed = seed; g.seed_dev = seed_dev;
+    g.gate_scale = 1.f; g.rows_per_scale = 1;
+    g.signs = want_signs ? (unsigned short*)signs : nullptr;
+    g.m_live = m_live;
+    return MTMP_OK;
+}
+
+// The Q/K/V projection: ln_gemm with N = 768, no activation, no dropout; bf16 also writes the key-norm table from its epilogue
+template <typename T>
+int qkv_args(GemmArgs<T>& g, const char* who, int i, const void* x, const float* gamma, const float* beta, const void* w,
+             const float* bias, void* y, void* xn, float* stats, float* key_norms, int M, int ldx, float eps, const int* m_live) {
+    MTMP_CHECK_ARG(x && gamma && beta && w && y && key_norms, "%s: null pointer (stream %d)", who, i);
+    MTMP_CHECK_ARG(M > 0 && ldx >= 256 && ldx % 8 == 0, "%s: bad shape M=%d ldx=%d (stream %d)", who, M, ldx, i);
+    g = GemmArgs<T>{};
+    g.a = (const T*)x; g.w = (const T*)w; g.bias = bias; g.y = (T*)y;
+    g.gamma = gamma; g.beta = beta; g.xn = (T*)xn; g.stats = stats;
+    g.M = M; g.N = 768; g.K = 256; g.lda = ldx; g.ldy = 768;
+    g.eps = eps; g.gate_scale = 1.f; g.rows_per_scale = 1;
+    g.knorm = sizeof(T) == 2 ? key_norms : nullptr;          // (fp32: mtmp_key_norms behind the projection)
+    g.m_live = m_live;
+    return MTMP_OK;
+}
+
+// The FFN backward's dH: y = signs ? (a' w^T) * gate_scale : 0, K = 256.  fold: a' = a through the backward of a dropout (the mask
+// of mtmp_dropout_bwd for seed, seed_dev, drop_p on the contiguous [M,256] tensor), also written to a_out; else a' = a.
+int gated_args(GemmArgs<bf16>& g, const char* who, int i, const void* a, const void* w, void* y, int M, int N, int lda, int ldy,
+               const void* signs, float gate_scale, bool fold, float drop_p, unsigned seed, const unsigned* seed_dev, void* a_out,
+               const int* m_live) {
+    MTMP_CHECK_ARG(a && w && y && signs, "%s: null pointer (stream %d)", who, i);
+    MTMP_CHECK_ARG(M > 0 && N > 0 && N % PanelDma::NP == 0 && lda >= 256 && lda % 8 == 0 && ldy >= N && ldy % 8 == 0,
+                   "%s: bad shape M=%d N=%d lda=%d ldy=%d (K is fixed at 256; stream %d)", who, M, N, lda, ldy, i);
+    // (the folded mask is indexed by element of the [M,256] operand: 32 bits, M < 2^24)
+    MTMP_CHECK_ARG(!fold || (M < (1 << 24) && drop_p >= 0.f && drop_p < 1.f), "%s: bad M=%d / dropout %f (stream %d)", who, M, drop_p, i);
+    g = GemmArgs<bf16>{};
+    g.a = (const bf16*)a; g.w = (const bf16*)w; g.y = (bf16*)y;
+    g.M = M; g.N = N; g.K = 256; g.lda = lda; g.ldy = ldy;
+    g.gate_scale = gate_scale; g.rows_per_scale = 1;
+    g.signs = (unsigned short*)signs;
+    if (fold) { g.xn = (bf16*)a_out; g.drop_p = drop_p; g.seed = seed; g.seed_dev = seed_dev; }
+    g.m_live = m_live;
+    return MTMP_OK;
+}
+
+// The generic NT projection y = drop(act(a w^T + bias)) (+ res) (FFN2); gate / row_scale: the single form's options
+template <typename T>
+int nt_args(GemmArgs<T>& g, const char* who, int i, const void* a, const void* w, const float* bias, const void* res, void* y,
+            int M, int N, int K, int lda, int ldy, int ldr, int act, float drop_p, unsigned seed, const unsigned* seed_dev,
+            const void* gate, float gate_scale, const float* row_scale, int rows_per_scale, const int* m_live) {
+    MTMP_CHECK_ARG(a && w && y, "%s: null pointer (stream %d)", who, i);
+    MTMP_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 8 == 0 && N % 32 == 0 && lda >= K && lda % 8 == 0 && ldy >= N && ldy % 8 == 0 &&
+                       (!res || (ldr >= N && ldr % 8 == 0)),
+                   "%s: bad shape M=%d N=%d K=%d lda=%d ldy=%d ldr=%d (stream %d)", who, M, N, K, lda, ldy, ldr, i);
+    MTMP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (double)M * N < 4294967296.0, "%s: bad dropout %f (stream %d)", who, drop_p, i);
+    MTMP_CHECK_ARG(act >= 0 && act <= 2 && (!row_scale || rows_per_scale > 0), "%s: bad act %d / row_scale", who, act);
+    g = GemmArgs<T>{};
+    g.a = (const T*)a; g.w = (const T*)w; g.bias = bias; g.res = (const T*)res; g.y = (T*)y;
+    g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldy = ldy; g.ldr = ldr;
+    g.drop_p = drop_p; g.seed = seed; g.seed_dev = seed_dev;
+    g.gate = (const T*)gate; g.gate_scale = gate_scale; g.act = act; g.row_scale = row_scale; g.rows_per_scale = rows_per_scale;
+    g.m_live = m_live;
+    return MTMP_OK;
+}
+
+// dz = LNbackward(dy wt^T; z, stats, gamma) (+ d_res), the gamma / beta partials into ws
+template <typename T>
+int lnbwd_args(LnBwdGemmArgs<T>& g, const char* who, int i, const void* dy, const void* wt, const void* z, int ldz, const float* stats,
+               const float* gamma, const void* d_res, int ldr, void* dz, float* ws, int M, int K, int ldy, float eps, const int* m_live) {
+    MTMP_CHECK_ARG(dy && wt && z && stats && gamma && dz && ws, "%s: null pointer (stream %d)", who, i);
+    MTMP_CHECK_ARG(M > 0 && K > 0 && K % 8 == 0 && ldy >= K && ldy % 8 == 0 && ldz >= 256 && ldz % 4 == 0 &&
+                       (!d_res || (ldr >= 256 && ldr % 4 == 0)),
+                   "%s: bad shape M=%d K=%d ldy=%d ldz=%d ldr=%d (stream %d)", who, M, K, ldy, ldz, ldr, i);
+    g = LnBwdGemmArgs<T>{};
+    g.dy = (const T*)dy; g.wt = (const T*)wt; g.z = (const T*)z; g.stats = stats; g.gamma = gamma; g.d_res = (const T*)d_res;
+    g.dz = (T*)dz; g.slab = ws;
+    g.M = M; g.K = K; g.ldy = ldy; g.ldz = ldz; g.ldr = ldr; g.eps = eps;
+    g.m_live = m_live;
+    return MTMP_OK;
+}
+
+// dW partial slabs = dy^T x over `splits` token ranges
+template <typename T>
+int tn_args(TnArgs<T>& g, const char* who, int i, const void* dy, const void* x, float* ws, int M, int N, int K, int ldy, int ldx,
+            int splits, const int* m_live) {
+    MTMP_CHECK_ARG(dy && x && ws, "%s: null pointer (stream %d)", who, i);
+    MTMP_CHECK_ARG(M > 0 && N > 0 && K > 0 && N % 8 == 0 && K % 8 == 0 && ldy >= N && ldx >= K && ldy % 8 == 0 && ldx % 8 == 0 &&
+                       splits >= 1,
+                   "%s: bad shape M=%d N=%d K=%d ldy=%d ldx=%d splits=%d (stream %d)", who, M, N, K, ldy, ldx, splits, i);
+    g = TnArgs<T>{};
+    g.dy = (const T*)dy; g.x = (const T*)x; g.slab = ws;
+    g.M = M; g.N = N; g.K = K; g.ldy = ldy; g.ldx = ldx; g.splits = splits;
+    g.rows_per_split = ((M + splits - 1) / splits + TK - 1) / TK * TK;
+    g.m_live = m_live;
+    return MTMP_OK;
+}
+}  // namespace
+
 // Y[M,N] = act(LN(X[M,256]; gamma, beta, eps) W[N,256]^T + bias); xn[M,256] and stats[M,2]
 // (mean, 1/(std+eps)) are optional outputs.  Replaces module.py:138-144 + attention.py:68-70
 // (relu=0, N=768) and module.py:138-144 + module.py:74-77 (relu=1, N=1024).
-static int ln_gemm_entry(int dtype, const void* x, const float* gamma, const float* beta, const void* w, const float* bias,
-                         void* y, void* xn, float* stats, int M, int N, int ldx, int ldy, float eps, int relu, float drop_p,
-                         unsigned seed, const unsigned* seed_dev, void* signs, void* stream) {
-    MTMP_CHECK_ARG(x && gamma && beta && w && y, "mtmp_ln_gemm: null pointer");
-    MTMP_CHECK_ARG(M > 0 && N > 0 && N % 32 == 0 && ldx >= 256 && ldx % 8 == 0 && ldy >= N && ldy % 8 == 0,
-                   "mtmp_ln_gemm: bad shape M=%d N=%d ldx=%d ldy=%d (K is fixed at 256)", M, N, ldx, ldy);
-    MTMP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (double)M * N < 4294967296.0, "mtmp_ln_gemm: bad dropout %f", drop_p);
-    MTMP_CHECK_ARG(!signs || (dtype == 1 && relu && N % PanelDma::NP == 0), "mtmp_ln_gemm_signs: bf16, ReLU and N %% 64 == 0 only");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) {
-        GemmArgs<float> a{(const float*)x, (const float*)w, bias, nullptr, (float*)y, gamma, beta, (float*)xn, stats,
-                          M, N, 256, ldx, ldy, 0, eps, drop_p, seed, seed_dev, nullptr, 1.f, 0, nullptr, 1};
-        return launch_ln_gemm<float>(a, relu, st);
-    }
-    if (dtype == 1) {
-        GemmArgs<bf16> a{(const bf16*)x, (const bf16*)w, bias, nullptr, (bf16*)y, gamma, beta, (bf16*)xn, stats,
-                         M, N, 256, ldx, ldy, 0, eps, drop_p, seed, seed_dev, nullptr, 1.f, 0, nullptr, 1, (unsigned short*)signs};
-        return launch_ln_gemm<bf16>(a, relu, st);
-    }
-    mtmp_set_error("mtmp_ln_gemm: unknown dtype %d", dtype);
-    return MTMP_ERR_ARG;
+static int ln_gemm_entry(const char* who, int dtype, const void* x, const float* gamma, const float* beta, const void* w,
+                         const float* bias, void* y, void* xn, float* stats, int M, int N, int ldx, int ldy, float eps, int relu,
+                         float drop_p, unsigned seed, const unsigned* seed_dev, bool want_signs, void* signs, void* stream) {
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        GemmArgs<T> g;
+        if (int e = ln_gemm_args<T>(g, who, 0, x, gamma, beta, w, bias, y, xn, stats, M, N, ldx, ldy, eps, drop_p, seed, seed_dev,
+                                    want_signs, signs, nullptr)) return e;
+        return launch_ln_gemm<T>(g, relu, (hipStream_t)stream);
+    });
 }
 extern "C" int mtmp_ln_gemm(int dtype, const void* x, const float* gamma, const float* beta, const void* w,
                             const float* bias, void* y, void* xn, float* stats, int M, int N, int ldx, int ldy,
                             float eps, int relu, float drop_p, unsigned seed, const unsigned* seed_dev, void* stream) {
-    return ln_gemm_entry(dtype, x, gamma, beta, w, bias, y, xn, stats, M, N, ldx, ldy, eps, relu, drop_p, seed, seed_dev, nullptr, stream);
+    return ln_gemm_entry("mtmp_ln_gemm", dtype, x, gamma, beta, w, bias, y, xn, stats, M, N, ldx, ldy, eps, relu, drop_p, seed,
+                         seed_dev, false, nullptr, stream);
 }
 // The Q/K/V projection of an encoder layer (module.py:138-144 + attention.py:68-70; w = [Wq; Wk; Wv], N = 768) that also
 // writes the key-norm table of the attention forward's bounded body: key_norms[ceil(M / 32)][4] = max ||k_h|| per block of 32
@@ -1949,16 +1995,19 @@ extern "C" int mtmp_ln_gemm(int dtype, const void* x, const float* gamma, const 
 extern "C" int mtmp_key_norms(int dtype, const void* k, float* out, long long rows, int H, int ld, void* stream);
 extern "C" int mtmp_ln_gemm_qkv(int dtype, const void* x, const float* gamma, const float* beta, const void* w, const float* bias,
                                 void* y, void* xn, float* stats, float* key_norms, int M, int ldx, float eps, void* stream) {
-    MTMP_CHECK_ARG(x && gamma && beta && w && y && key_norms, "mtmp_ln_gemm_qkv: null pointer");
-    MTMP_CHECK_ARG(M > 0 && ldx >= 256 && ldx % 8 == 0, "mtmp_ln_gemm_qkv: bad shape M=%d ldx=%d", M, ldx);
-    if (dtype == 1) {
-        GemmArgs<bf16> a{(const bf16*)x, (const bf16*)w, bias, nullptr, (bf16*)y, gamma, beta, (bf16*)xn, stats,
-                         M, 768, 256, ldx, 768, 0, eps, 0.f, 0u, nullptr, nullptr, 1.f, 0, nullptr, 1, nullptr, key_norms};
-        return launch_ln_gemm_dma(1, &a, 0, 0, (hipStream_t)stream);
-    }
-    if (int e = ln_gemm_entry(dtype, x, gamma, beta, w, bias, y, xn, stats, M, 768, ldx, 768, eps, 0, 0.f, 0u, nullptr, nullptr, stream)) return e;
-    const size_t es = dtype == 0 ? 4 : 2;
-    return mtmp_key_norms(dtype, (const char*)y + 256 * es, key_norms, M, 4, 768, stream);
+    const char* who = "mtmp_ln_gemm_qkv";
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        GemmArgs<T> g;
+        if (int e = qkv_args<T>(g, who, 0, x, gamma, beta, w, bias, y, xn, stats, key_norms, M, ldx, eps, nullptr)) return e;
+        if constexpr (sizeof(T) == 2) {
+            return launch_ln_gemm_dma(1, &g, 0, 0, (hipStream_t)stream);
+        } else {
+            MTMP_CHECK_ARG((double)M * 768 < 4294967296.0, "%s: M=%d too large", who, M);
+            if (int e = launch_ln_gemm<T>(g, 0, (hipStream_t)stream)) return e;
+            return mtmp_key_norms(dtype, (const char*)y + 256 * sizeof(T), key_norms, M, 4, 768, stream);
+        }
+    });
 }
 // Sign bits of a ReLU projection (bf16 build of the row-panel kernels only): one bit per output, "y > 0", in the kernels'
 // private order; mtmp_sign_bits_bytes(M, N) bytes.  mtmp_ln_gemm_signs = mtmp_ln_gemm (relu = 1) that also writes them;
@@ -1968,17 +2017,15 @@ extern "C" long long mtmp_sign_bits_bytes(int M, int N) { return (long long)(N /
 extern "C" int mtmp_ln_gemm_signs(int dtype, const void* x, const float* gamma, const float* beta, const void* w,
                                   const float* bias, void* y, void* xn, float* stats, int M, int N, int ldx, int ldy,
                                   float eps, float drop_p, unsigned seed, const unsigned* seed_dev, void* signs, void* stream) {
-    MTMP_CHECK_ARG(signs, "mtmp_ln_gemm_signs: null pointer");
-    return ln_gemm_entry(dtype, x, gamma, beta, w, bias, y, xn, stats, M, N, ldx, ldy, eps, 1, drop_p, seed, seed_dev, signs, stream);
+    return ln_gemm_entry("mtmp_ln_gemm_signs", dtype, x, gamma, beta, w, bias, y, xn, stats, M, N, ldx, ldy, eps, 1, drop_p, seed,
+                         seed_dev, true, signs, stream);
 }
 extern "C" int mtmp_gemm_nt_signs(int dtype, const void* a, const void* w, void* y, int M, int N, int lda, int ldy,
                                   const void* signs, float gate_scale, void* stream) {
-    MTMP_CHECK_ARG(a && w && y && signs, "mtmp_gemm_nt_signs: null pointer");
     MTMP_CHECK_ARG(dtype == 1, "mtmp_gemm_nt_signs: bf16 only (dtype %d)", dtype);
-    MTMP_CHECK_ARG(M > 0 && N > 0 && N % PanelDma::NP == 0 && lda >= 256 && lda % 8 == 0 && ldy >= N && ldy % 8 == 0,
-                   "mtmp_gemm_nt_signs: bad shape M=%d N=%d lda=%d ldy=%d (K is fixed at 256)", M, N, lda, ldy);
-    GemmArgs<bf16> g{(const bf16*)a, (const bf16*)w, nullptr, nullptr, (bf16*)y, nullptr, nullptr, nullptr, nullptr, M, N, 256, lda, ldy,
-                     0, 0.f, 0.f, 0u, nullptr, nullptr, gate_scale, 0, nullptr, 1, (unsigned short*)signs};
+    GemmArgs<bf16> g;
+    if (int e = gated_args(g, "mtmp_gemm_nt_signs", 0, a, w, y, M, N, lda, ldy, signs, gate_scale, false, 0.f, 0u, nullptr, nullptr, nullptr))
+        return e;
     return launch_ln_gemm_dma(1, &g, 0, 1, (hipStream_t)stream);
 }
 
@@ -1988,57 +2035,34 @@ extern "C" int mtmp_gemm_nt_signs(int dtype, const void* a, const void* w, void*
 extern "C" int mtmp_gemm_nt_signs_drop(int dtype, const void* a, const void* w, void* y, int M, int N, int lda, int ldy,
                                        const void* signs, float gate_scale, float drop_p, unsigned seed, const unsigned* seed_dev,
                                        void* a_out, void* stream) {
-    MTMP_CHECK_ARG(a && w && y && signs, "mtmp_gemm_nt_signs_drop: null pointer");
     MTMP_CHECK_ARG(dtype == 1, "mtmp_gemm_nt_signs_drop: bf16 only (dtype %d)", dtype);
-    MTMP_CHECK_ARG(M > 0 && M < (1 << 24) && N > 0 && N % PanelDma::NP == 0 && lda >= 256 && lda % 8 == 0 && ldy >= N && ldy % 8 == 0 &&
-                       drop_p >= 0.f && drop_p < 1.f,
-                   "mtmp_gemm_nt_signs_drop: bad argument M=%d N=%d lda=%d ldy=%d p=%f (K is fixed at 256)", M, N, lda, ldy, drop_p);
-    GemmArgs<bf16> g{(const bf16*)a, (const bf16*)w, nullptr, nullptr, (bf16*)y, nullptr, nullptr, (bf16*)a_out, nullptr, M, N, 256, lda,
-                     ldy, 0, 0.f, drop_p, seed, seed_dev, nullptr, gate_scale, 0, nullptr, 1, (unsigned short*)signs};
+    GemmArgs<bf16> g;
+    if (int e = gated_args(g, "mtmp_gemm_nt_signs_drop", 0, a, w, y, M, N, lda, ldy, signs, gate_scale, true, drop_p, seed, seed_dev,
+                           a_out, nullptr)) return e;
     return launch_ln_gemm_dma(1, &g, 0, 1, (hipStream_t)stream);
 }
 
 // Y[M,N] = drop(act(A[M,K] W[N,K]^T + bias)) (+ R[M,N]).  Replaces module.py:78-80 + encoder.py:32
 // (Conv1d(1024,256,1) + drop2 + residual) and is the generic NT projection of the path.
+// rows_live (may be NULL): a device word with the rows in use (<= M), see the grouped forms
 extern "C" int mtmp_gemm_nt_live(int dtype, const void* a, const void* w, const float* bias, const void* res, void* y,
                                  int M, int N, int K, int lda, int ldy, int ldr, int act, float drop_p, unsigned seed,
                                  const unsigned* seed_dev, const void* gate, float gate_scale, const float* row_scale,
-                                 int rows_per_scale, const int32_t* rows_live, void* stream);
+                                 int rows_per_scale, const int32_t* rows_live, void* stream) {
+    return with_dtype(dtype, "mtmp_gemm_nt", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        GemmArgs<T> g;
+        if (int e = nt_args<T>(g, "mtmp_gemm_nt", 0, a, w, bias, res, y, M, N, K, lda, ldy, ldr, act, drop_p, seed, seed_dev, gate,
+                               gate_scale, row_scale, rows_per_scale, rows_live)) return e;
+        return launch_gemm_nt<T>(1, &g, 0, (hipStream_t)stream);
+    });
+}
 extern "C" int mtmp_gemm_nt(int dtype, const void* a, const void* w, const float* bias, const void* res, void* y,
                             int M, int N, int K, int lda, int ldy, int ldr, int act, float drop_p, unsigned seed,
                             const unsigned* seed_dev, const void* gate, float gate_scale, const float* row_scale,
                             int rows_per_scale, void* stream) {
     return mtmp_gemm_nt_live(dtype, a, w, bias, res, y, M, N, K, lda, ldy, ldr, act, drop_p, seed, seed_dev, gate, gate_scale,
                              row_scale, rows_per_scale, nullptr, stream);
-}
-// rows_live (may be NULL): a device word with the rows in use (<= M), see the grouped forms
-extern "C" int mtmp_gemm_nt_live(int dtype, const void* a, const void* w, const float* bias, const void* res, void* y,
-                                 int M, int N, int K, int lda, int ldy, int ldr, int act, float drop_p, unsigned seed,
-                                 const unsigned* seed_dev, const void* gate, float gate_scale, const float* row_scale,
-                                 int rows_per_scale, const int32_t* rows_live, void* stream) {
-    MTMP_CHECK_ARG(a && w && y, "mtmp_gemm_nt: null pointer");
-    MTMP_CHECK_ARG(M > 0 && N > 0 && K > 0 && K % 8 == 0 && N % 32 == 0 && lda >= K && lda % 8 == 0 && ldy >= N &&
-                       ldy % 8 == 0 && (!res || (ldr >= N && ldr % 8 == 0)),
-                   "mtmp_gemm_nt: bad shape M=%d N=%d K=%d lda=%d ldy=%d ldr=%d", M, N, K, lda, ldy, ldr);
-    MTMP_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f && (double)M * N < 4294967296.0, "mtmp_gemm_nt: bad dropout %f", drop_p);
-    MTMP_CHECK_ARG(act >= 0 && act <= 2 && (!row_scale || rows_per_scale > 0), "mtmp_gemm_nt: bad act %d / row_scale", act);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) {
-        GemmArgs<float> g{(const float*)a, (const float*)w, bias, (const float*)res, (float*)y, nullptr, nullptr,
-                          nullptr, nullptr, M, N, K, lda, ldy, ldr, 0.f, drop_p, seed, seed_dev, (const float*)gate, gate_scale, act, row_scale,
-                          rows_per_scale};
-        g.m_live = rows_live;
-        return launch_gemm_nt<float>(1, &g, 0, st);
-    }
-    if (dtype == 1) {
-        GemmArgs<bf16> g{(const bf16*)a, (const bf16*)w, bias, (const bf16*)res, (bf16*)y, nullptr, nullptr, nullptr,
-                         nullptr, M, N, K, lda, ldy, ldr, 0.f, drop_p, seed, seed_dev, (const bf16*)gate, gate_scale, act, row_scale,
-                         rows_per_scale};
-        g.m_live = rows_live;
-        return launch_gemm_nt<bf16>(1, &g, 0, st);
-    }
-    mtmp_set_error("mtmp_gemm_nt: unknown dtype %d", dtype);
-    return MTMP_ERR_ARG;
 }
 
 extern "C" int mtmp_gemm_lnbwd_ws_floats(int M) { return ((M + 127) / 128 + RED_GROUPS) * 512; }
@@ -2050,22 +2074,13 @@ extern "C" int mtmp_gemm_lnbwd_ws_floats(int M) { return ((M + 127) / 128 + RED_
 extern "C" int mtmp_gemm_lnbwd(int dtype, const void* dy, const void* wt, const void* z, int ldz, const float* stats,
                                const float* gamma, const void* d_res, int ldr, void* dz, float* dgamma_dbeta, float* ws,
                                int M, int K, int ldy, float eps, void* stream) {
-    MTMP_CHECK_ARG(dy && wt && z && stats && gamma && dz && ws, "mtmp_gemm_lnbwd: null pointer");
-    MTMP_CHECK_ARG(M > 0 && K > 0 && K % 8 == 0 && ldy >= K && ldy % 8 == 0 && ldz >= 256 && ldz % 4 == 0 &&
-                       (!d_res || (ldr >= 256 && ldr % 4 == 0)), "mtmp_gemm_lnbwd: bad shape M=%d K=%d ldy=%d ldz=%d", M, K, ldy, ldz);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) {
-        LnBwdGemmArgs<float> a{(const float*)dy, (const float*)wt, (const float*)z, stats, gamma, (const float*)d_res,
-                               (float*)dz, nullptr, M, K, ldy, ldz, ldr, eps};
-        return launch_gemm_lnbwd<float>(1, &a, &dgamma_dbeta, &ws, st);
-    }
-    if (dtype == 1) {
-        LnBwdGemmArgs<bf16> a{(const bf16*)dy, (const bf16*)wt, (const bf16*)z, stats, gamma, (const bf16*)d_res,
-                              (bf16*)dz, nullptr, M, K, ldy, ldz, ldr, eps};
-        return launch_gemm_lnbwd<bf16>(1, &a, &dgamma_dbeta, &ws, st);
-    }
-    mtmp_set_error("mtmp_gemm_lnbwd: unknown dtype %d", dtype);
-    return MTMP_ERR_ARG;
+    return with_dtype(dtype, "mtmp_gemm_lnbwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        LnBwdGemmArgs<T> g;
+        if (int e = lnbwd_args<T>(g, "mtmp_gemm_lnbwd", 0, dy, wt, z, ldz, stats, gamma, d_res, ldr, dz, ws, M, K, ldy, eps, nullptr))
+            return e;
+        return launch_gemm_lnbwd<T>(1, &g, &dgamma_dbeta, (hipStream_t)stream);
+    });
 }
 
 // Deferred reductions.  mtmp_gemm_tn with dw == NULL and mtmp_gemm_lnbwd with dgamma_dbeta == NULL leave their partial slabs in
@@ -2124,34 +2139,31 @@ extern "C" long long mtmp_gemm_tn_ws_floats(int M, int N, int K) {
 // 8 (both multiples of 128: the tuned kernels; the rest: gemm_tn_edge_kernel).  ws: mtmp_gemm_tn_ws_floats(M,N,K) floats.
 // The weight / bias gradients of the Linear and k=1 Conv1d layers of attention.py:60-62 and module.py:74-78, and of the
 // trainable image encoder's Linear layers (swin_transformer.py forward_train).
-extern "C" int mtmp_gemm_tn_live(int dtype, const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N,
-                                 int K, int ldy, int ldx, const int32_t* rows_live, void* stream);
-extern "C" int mtmp_gemm_tn(int dtype, const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N,
-                            int K, int ldy, int ldx, void* stream) {
-    return mtmp_gemm_tn_live(dtype, dy, x, dw, db, ws, M, N, K, ldy, ldx, nullptr, stream);
-}
 // rows_live (may be NULL): a device word with the rows in use (<= M), see mtmp_gemm_tn_grouped -- the split count, the
 // workspace and the grid stay those of M, every split takes its share of the live rows.
 extern "C" int mtmp_gemm_tn_live(int dtype, const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N,
                                  int K, int ldy, int ldx, const int32_t* rows_live, void* stream) {
-    MTMP_CHECK_ARG(dy && x && ws && (dw || !db), "mtmp_gemm_tn: null pointer");
-    MTMP_CHECK_ARG(M > 0 && N > 0 && K > 0 && N % 8 == 0 && K % 8 == 0 && ldy >= N && ldx >= K && ldy % 8 == 0 &&
-                       ldx % 8 == 0, "mtmp_gemm_tn: bad shape M=%d N=%d K=%d ldy=%d ldx=%d", M, N, K, ldy, ldx);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) return launch_gemm_tn<float>(dy, x, dw, db, ws, M, N, K, ldy, ldx, rows_live, st);
-    if (dtype == 1) return launch_gemm_tn<bf16>(dy, x, dw, db, ws, M, N, K, ldy, ldx, rows_live, st);
-    mtmp_set_error("mtmp_gemm_tn: unknown dtype %d", dtype);
-    return MTMP_ERR_ARG;
+    MTMP_CHECK_ARG(dw || !db, "mtmp_gemm_tn: db without dw");
+    return with_dtype(dtype, "mtmp_gemm_tn", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        int mode;
+        const int splits = tn_launch_splits(sizeof(T) == 2, M, N, K, &mode);
+        TnArgs<T> g;
+        if (int e = tn_args<T>(g, "mtmp_gemm_tn", 0, dy, x, ws, M, N, K, ldy, ldx, splits, rows_live)) return e;
+        return launch_gemm_tn<T>(g, mode, dw, db, (hipStream_t)stream);
+    });
+}
+extern "C" int mtmp_gemm_tn(int dtype, const void* dy, const void* x, float* dw, float* db, float* ws, int M, int N,
+                            int K, int ldy, int ldx, void* stream) {
+    return mtmp_gemm_tn_live(dtype, dy, x, dw, db, ws, M, N, K, ldy, ldx, nullptr, stream);
 }
 
-namespace {
-// g_out[i] = keep(seed, i) ? g_in[i] / (1-p) : 0 -- backward of the epilogue dropout (same mask).
 // ------------------------------------------------------------------------------------------------------------------------
 // Grouped forms (bf16): the same operation of up to three token streams of one fusion layer in ONE launch (common.hip.h, Grouped).
 // All pointer / int arrays are HOST arrays of n entries; scalars are common to the streams.  rows_live (may be NULL, entries may be
 // NULL): per stream a DEVICE word with the rows in use this step (<= M[i]) -- the packed vital-sign stream, whose buffers and
-// grids are sized for the padded maximum M[i] (mtmp_row_starts); rows past it are neither read nor written.  Same kernels, same results as n
-// calls of the single forms.  The parity (fp32) build keeps the single forms.
+// grids are sized for the padded maximum M[i] (mtmp_row_starts); rows past it are neither read nor written.  Same builders, same
+// launchers, same kernels as the single forms: same results as n calls of those.  The parity (fp32) build keeps the single forms.
 #define MTMP_CHECK_GROUP(name, n, dtype)                                                                             \
     MTMP_CHECK_ARG((n) >= 1 && (n) <= GRP_MAX && (dtype) == 1, name ": 1..%d streams, bf16 only (n=%d dtype=%d)", GRP_MAX, n, dtype)
 
@@ -2160,16 +2172,11 @@ extern "C" int mtmp_ln_gemm_qkv_grouped(int dtype, int n, const void* const* x, 
                                         float* const* stats, float* const* key_norms, const int* M, const int* ldx, float eps,
                                         const int32_t* const* rows_live, void* stream) {
     MTMP_CHECK_GROUP("mtmp_ln_gemm_qkv_grouped", n, dtype);
-    GemmArgs<bf16> a[GRP_MAX];
-    for (int i = 0; i < n; ++i) {
-        MTMP_CHECK_ARG(x[i] && gamma[i] && beta[i] && w[i] && y[i] && key_norms[i] && M[i] > 0 && ldx[i] >= 256 && ldx[i] % 8 == 0,
-                       "mtmp_ln_gemm_qkv_grouped: bad argument (stream %d)", i);
-        a[i] = GemmArgs<bf16>{(const bf16*)x[i], (const bf16*)w[i], bias ? bias[i] : nullptr, nullptr, (bf16*)y[i], gamma[i], beta[i],
-                              xn ? (bf16*)xn[i] : nullptr, stats ? stats[i] : nullptr, M[i], 768, 256, ldx[i], 768, 0, eps, 0.f, 0u,
-                              nullptr, nullptr, 1.f, 0, nullptr, 1, nullptr, key_norms[i]};
-        a[i].m_live = rows_live ? rows_live[i] : nullptr;
-    }
-    return launch_ln_gemm_dma(n, a, 0, 0, (hipStream_t)stream);
+    GemmArgs<bf16> g[GRP_MAX];
+    for (int i = 0; i < n; ++i)
+        if (int e = qkv_args<bf16>(g[i], "mtmp_ln_gemm_qkv_grouped", i, x[i], gamma[i], beta[i], w[i], opt(bias, i), y[i], opt(xn, i),
+                                   opt(stats, i), key_norms[i], M[i], ldx[i], eps, opt(rows_live, i))) return e;
+    return launch_ln_gemm_dma(n, g, 0, 0, (hipStream_t)stream);
 }
 
 // mtmp_ln_gemm_signs (FFN1: LayerNorm + Conv1d(k=1) + ReLU + drop1 + sign bits), N common, one seed per stream
@@ -2179,17 +2186,12 @@ extern "C" int mtmp_ln_gemm_signs_grouped(int dtype, int n, const void* const* x
                                           float drop_p, const unsigned* seeds, const unsigned* seed_dev,
                                           const int32_t* const* rows_live, void* stream) {
     MTMP_CHECK_GROUP("mtmp_ln_gemm_signs_grouped", n, dtype);
-    MTMP_CHECK_ARG(N > 0 && N % PanelDma::NP == 0 && drop_p >= 0.f && drop_p < 1.f, "mtmp_ln_gemm_signs_grouped: bad N=%d / dropout %f", N, drop_p);
-    GemmArgs<bf16> a[GRP_MAX];
-    for (int i = 0; i < n; ++i) {
-        MTMP_CHECK_ARG(x[i] && gamma[i] && beta[i] && w[i] && y[i] && signs[i] && M[i] > 0 && ldx[i] >= 256 && ldx[i] % 8 == 0 &&
-                           (double)M[i] * N < 4294967296.0, "mtmp_ln_gemm_signs_grouped: bad argument (stream %d)", i);
-        a[i] = GemmArgs<bf16>{(const bf16*)x[i], (const bf16*)w[i], bias ? bias[i] : nullptr, nullptr, (bf16*)y[i], gamma[i], beta[i],
-                              xn ? (bf16*)xn[i] : nullptr, stats ? stats[i] : nullptr, M[i], N, 256, ldx[i], N, 0, eps, drop_p,
-                              seeds ? seeds[i] : 0u, seed_dev, nullptr, 1.f, 0, nullptr, 1, (unsigned short*)signs[i]};
-        a[i].m_live = rows_live ? rows_live[i] : nullptr;
-    }
-    return launch_ln_gemm_dma(n, a, 1, 0, (hipStream_t)stream);
+    GemmArgs<bf16> g[GRP_MAX];
+    for (int i = 0; i < n; ++i)
+        if (int e = ln_gemm_args<bf16>(g[i], "mtmp_ln_gemm_signs_grouped", i, x[i], gamma[i], beta[i], w[i], opt(bias, i), y[i],
+                                       opt(xn, i), opt(stats, i), M[i], N, ldx[i], N, eps, drop_p, opt(seeds, i), seed_dev, true,
+                                       signs[i], opt(rows_live, i))) return e;
+    return launch_ln_gemm_dma(n, g, 1, 0, (hipStream_t)stream);
 }
 
 // mtmp_gemm_nt_signs_drop (dH = dY W2 through ReLU + drop1, drop2's backward on the operand), N common
@@ -2198,16 +2200,10 @@ extern "C" int mtmp_gemm_nt_signs_drop_grouped(int dtype, int n, const void* con
                                                float drop_p, const unsigned* seeds, const unsigned* seed_dev, void* const* a_out,
                                                const int32_t* const* rows_live, void* stream) {
     MTMP_CHECK_GROUP("mtmp_gemm_nt_signs_drop_grouped", n, dtype);
-    MTMP_CHECK_ARG(N > 0 && N % PanelDma::NP == 0 && drop_p >= 0.f && drop_p < 1.f, "mtmp_gemm_nt_signs_drop_grouped: bad N=%d / dropout %f", N, drop_p);
     GemmArgs<bf16> g[GRP_MAX];
-    for (int i = 0; i < n; ++i) {
-        MTMP_CHECK_ARG(a_in[i] && w[i] && y[i] && signs[i] && M[i] > 0 && M[i] < (1 << 24) && lda[i] >= 256 && lda[i] % 8 == 0,
-                       "mtmp_gemm_nt_signs_drop_grouped: bad argument (stream %d)", i);
-        g[i] = GemmArgs<bf16>{(const bf16*)a_in[i], (const bf16*)w[i], nullptr, nullptr, (bf16*)y[i], nullptr, nullptr,
-                              a_out ? (bf16*)a_out[i] : nullptr, nullptr, M[i], N, 256, lda[i], N, 0, 0.f, drop_p, seeds ? seeds[i] : 0u,
-                              seed_dev, nullptr, gate_scale, 0, nullptr, 1, (unsigned short*)signs[i]};
-        g[i].m_live = rows_live ? rows_live[i] : nullptr;
-    }
+    for (int i = 0; i < n; ++i)
+        if (int e = gated_args(g[i], "mtmp_gemm_nt_signs_drop_grouped", i, a_in[i], w[i], y[i], M[i], N, lda[i], N, signs[i],
+                               gate_scale, true, drop_p, opt(seeds, i), seed_dev, opt(a_out, i), opt(rows_live, i))) return e;
     return launch_ln_gemm_dma(n, g, 0, 1, (hipStream_t)stream);
 }
 
@@ -2217,18 +2213,12 @@ extern "C" int mtmp_gemm_nt_grouped(int dtype, int n, const void* const* a_in, c
                                     const int* ldr, int act, float drop_p, const unsigned* seeds, const unsigned* seed_dev,
                                     const int32_t* const* rows_live, void* stream) {
     MTMP_CHECK_GROUP("mtmp_gemm_nt_grouped", n, dtype);
-    MTMP_CHECK_ARG(N > 0 && K > 0 && K % 8 == 0 && N % 32 == 0 && act >= 0 && act <= 2 && drop_p >= 0.f && drop_p < 1.f,
-                   "mtmp_gemm_nt_grouped: bad shape N=%d K=%d act=%d p=%f", N, K, act, drop_p);
     GemmArgs<bf16> g[GRP_MAX];
     for (int i = 0; i < n; ++i) {
-        const bool has_res = res && res[i];
-        MTMP_CHECK_ARG(a_in[i] && w[i] && y[i] && M[i] > 0 && lda[i] >= K && lda[i] % 8 == 0 && ldy[i] >= N && ldy[i] % 8 == 0 &&
-                           (!has_res || (ldr[i] >= N && ldr[i] % 8 == 0)) && (double)M[i] * N < 4294967296.0,
-                       "mtmp_gemm_nt_grouped: bad argument (stream %d)", i);
-        g[i] = GemmArgs<bf16>{(const bf16*)a_in[i], (const bf16*)w[i], bias ? bias[i] : nullptr, has_res ? (const bf16*)res[i] : nullptr,
-                              (bf16*)y[i], nullptr, nullptr, nullptr, nullptr, M[i], N, K, lda[i], ldy[i], has_res ? ldr[i] : 0, 0.f,
-                              drop_p, seeds ? seeds[i] : 0u, seed_dev, nullptr, 1.f, act, nullptr, 1};
-        g[i].m_live = rows_live ? rows_live[i] : nullptr;
+        const void* r = opt(res, i);
+        if (int e = nt_args<bf16>(g[i], "mtmp_gemm_nt_grouped", i, a_in[i], w[i], opt(bias, i), r, y[i], M[i], N, K, lda[i], ldy[i],
+                                  r ? ldr[i] : 0, act, drop_p, opt(seeds, i), seed_dev, nullptr, 1.f, nullptr, 1, opt(rows_live, i)))
+            return e;
     }
     return launch_gemm_nt<bf16>(n, g, 0, (hipStream_t)stream);
 }
@@ -2239,19 +2229,13 @@ extern "C" int mtmp_gemm_lnbwd_grouped(int dtype, int n, const void* const* dy, 
                                        const int* ldr, void* const* dz, float* const* ws, const int* M, int K, const int* ldy, float eps,
                                        const int32_t* const* rows_live, void* stream) {
     MTMP_CHECK_GROUP("mtmp_gemm_lnbwd_grouped", n, dtype);
-    MTMP_CHECK_ARG(K > 0 && K % 8 == 0, "mtmp_gemm_lnbwd_grouped: bad K=%d", K);
-    LnBwdGemmArgs<bf16> a[GRP_MAX];
+    LnBwdGemmArgs<bf16> g[GRP_MAX];
     for (int i = 0; i < n; ++i) {
-        const bool has_res = d_res && d_res[i];
-        MTMP_CHECK_ARG(dy[i] && wt[i] && z[i] && stats[i] && gamma[i] && dz[i] && ws[i] && M[i] > 0 && ldy[i] >= K && ldy[i] % 8 == 0 &&
-                           ldz[i] >= 256 && ldz[i] % 4 == 0 && (!has_res || (ldr[i] >= 256 && ldr[i] % 4 == 0)),
-                       "mtmp_gemm_lnbwd_grouped: bad argument (stream %d)", i);
-        a[i] = LnBwdGemmArgs<bf16>{(const bf16*)dy[i], (const bf16*)wt[i], (const bf16*)z[i], stats[i], gamma[i],
-                                   has_res ? (const bf16*)d_res[i] : nullptr, (bf16*)dz[i], nullptr, M[i], K, ldy[i], ldz[i],
-                                   has_res ? ldr[i] : 0, eps};
-        a[i].m_live = rows_live ? rows_live[i] : nullptr;
+        const void* r = opt(d_res, i);
+        if (int e = lnbwd_args<bf16>(g[i], "mtmp_gemm_lnbwd_grouped", i, dy[i], wt[i], z[i], ldz[i], stats[i], gamma[i], r,
+                                     r ? ldr[i] : 0, dz[i], ws[i], M[i], K, ldy[i], eps, opt(rows_live, i))) return e;
     }
-    return launch_gemm_lnbwd<bf16>(n, a, nullptr, ws, (hipStream_t)stream);
+    return launch_gemm_lnbwd<bf16>(n, g, nullptr, (hipStream_t)stream);
 }
 
 // Weight gradients of up to three streams in one launch (bf16 LDS-DMA kernel), partial slabs only: ws[i] holds
@@ -2267,19 +2251,20 @@ extern "C" int mtmp_gemm_tn_grouped(int dtype, int n, const void* const* dy, con
                                     void* stream) {
     MTMP_CHECK_GROUP("mtmp_gemm_tn_grouped", n, dtype);
     MTMP_CHECK_ARG(N > 0 && K > 0 && N % 128 == 0 && K % 128 == 0, "mtmp_gemm_tn_grouped: N=%d K=%d must be multiples of 128", N, K);
-    TnArgs<bf16> a[GRP_MAX];
+    TnArgs<bf16> g[GRP_MAX];
     for (int i = 0; i < n; ++i) {
-        MTMP_CHECK_ARG(dy[i] && x[i] && ws[i] && M[i] > 0 && splits[i] >= 1 && ldy[i] >= N && ldx[i] >= K && ldy[i] % 8 == 0 &&
-                           ldx[i] % 8 == 0 && (uintptr_t)dy[i] % 16 == 0 && (uintptr_t)x[i] % 16 == 0 &&
+        if (int e = tn_args<bf16>(g[i], "mtmp_gemm_tn_grouped", i, dy[i], x[i], ws[i], M[i], N, K, ldy[i], ldx[i], splits[i],
+                                  opt(rows_live, i))) return e;
+        // what the LDS-DMA kernel asks of its operands (the single form falls back to the register-staged kernel instead)
+        MTMP_CHECK_ARG((uintptr_t)dy[i] % 16 == 0 && (uintptr_t)x[i] % 16 == 0 &&
                            (unsigned long long)M[i] * (unsigned)(ldy[i] > ldx[i] ? ldy[i] : ldx[i]) * 2ull < (1ull << 32),
-                       "mtmp_gemm_tn_grouped: bad argument (stream %d)", i);
-        int rps = (M[i] + splits[i] - 1) / splits[i];
-        rps = (rps + TK - 1) / TK * TK;
-        a[i] = TnArgs<bf16>{(const bf16*)dy[i], (const bf16*)x[i], ws[i], M[i], N, K, ldy[i], ldx[i], splits[i], rps};
-        a[i].m_live = rows_live ? rows_live[i] : nullptr;
+                       "mtmp_gemm_tn_grouped: operands not 16-byte aligned or past 32-bit offsets (stream %d)", i);
     }
-    return launch_gemm_tn_grouped(n, a, (hipStream_t)stream);
+    return launch_gemm_tn_grouped(n, g, (hipStream_t)stream);
 }
+
+namespace {
+// g_out[i] = keep(seed, i) ? g_in[i] / (1-p) : 0 -- backward of the epilogue dropout (same mask).
 
 template <typename T>
 __global__ __launch_bounds__(256) void dropout_bwd_kernel(const T* gi, T* go, size_t n4, unsigned seed0, const unsigned* seed_dev,
@@ -2305,11 +2290,11 @@ extern "C" int mtmp_dropout_bwd(int dtype, const void* g_in, void* g_out, long l
                    "mtmp_dropout_bwd: bad argument n=%lld p=%f", n, p);
     const size_t n4 = (size_t)n / 4;
     const int nb = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) hipLaunchKernelGGL(dropout_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, (const float*)g_in, (float*)g_out, n4, seed, seed_dev, p);
-    else if (dtype == 1) hipLaunchKernelGGL(dropout_bwd_kernel<bf16>, dim3(nb), dim3(256), 0, st, (const bf16*)g_in, (bf16*)g_out, n4, seed, seed_dev, p);
-    else { mtmp_set_error("mtmp_dropout_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_dropout_bwd");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_dropout_bwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(dropout_bwd_kernel<T>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (const T*)g_in, (T*)g_out, n4, seed,
+                           seed_dev, p);
+        MTMP_CHECK_LAUNCH("mtmp_dropout_bwd");
+        return MTMP_OK;
+    });
 }
-

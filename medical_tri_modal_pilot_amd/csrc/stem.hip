@@ -88,13 +88,6 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* img, const float
 
 // out[n_img, H/4, W/4, 96] = LayerNorm(Conv2d_4x4s4(img[n_img,1,H,W]) NHWC); weights/params fp32.
 // Replaces swin_transformer.py:559-567 (features[0]) with the 1-channel stem of :646.
-extern "C" int mtmp_swin_stem_fwd_live(int dtype, const float* img, const float* w, const float* bias, const float* ln_w,
-                                       const float* ln_b, void* out, int n_img, int H, int W, const int32_t* order,
-                                       const int32_t* rows_live, void* stream);
-extern "C" int mtmp_swin_stem_fwd(int dtype, const float* img, const float* w, const float* bias, const float* ln_w,
-                                  const float* ln_b, void* out, int n_img, int H, int W, void* stream) {
-    return mtmp_swin_stem_fwd_live(dtype, img, w, bias, ln_w, ln_b, out, n_img, H, W, nullptr, nullptr, stream);
-}
 // order (int32[n_img] device, may be NULL): output slot i is made from image order[i]; rows_live (may be NULL): a device word
 // with the patch rows in use (live slots x (H/4)(W/4)) -- mtmp_image_slots: present images first, the rest not computed.
 extern "C" int mtmp_swin_stem_fwd_live(int dtype, const float* img, const float* w, const float* bias, const float* ln_w,
@@ -104,10 +97,15 @@ extern "C" int mtmp_swin_stem_fwd_live(int dtype, const float* img, const float*
     MTMP_CHECK_ARG(n_img > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, "mtmp_swin_stem_fwd: bad shape %dx%dx%d", n_img, H, W);
     const long long total = (long long)n_img * (H / 4) * (W / 4);
     const int nb = (int)((total + 127) / 128);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0) hipLaunchKernelGGL(stem_kernel<float>, dim3(nb), dim3(256), 0, st, img, w, bias, ln_w, ln_b, (float*)out, n_img, H, W, order, rows_live);
-    else if (dtype == 1) hipLaunchKernelGGL(stem_kernel<bf16>, dim3(nb), dim3(256), 0, st, img, w, bias, ln_w, ln_b, (bf16*)out, n_img, H, W, order, rows_live);
-    else { mtmp_set_error("mtmp_swin_stem_fwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_swin_stem_fwd");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_swin_stem_fwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL(stem_kernel<T>, dim3(nb), dim3(256), 0, (hipStream_t)stream, img, w, bias, ln_w, ln_b, (T*)out, n_img, H, W,
+                           order, rows_live);
+        MTMP_CHECK_LAUNCH("mtmp_swin_stem_fwd");
+        return MTMP_OK;
+    });
+}
+extern "C" int mtmp_swin_stem_fwd(int dtype, const float* img, const float* w, const float* bias, const float* ln_w,
+                                  const float* ln_b, void* out, int n_img, int H, int W, void* stream) {
+    return mtmp_swin_stem_fwd_live(dtype, img, w, bias, ln_w, ln_b, out, n_img, H, W, nullptr, nullptr, stream);
 }

@@ -492,11 +492,8 @@ int launch_swin_mlp(const void* x, const float* ln_w, const float* ln_b, const v
                     const float* b2, const float* row_scale, int rows_per_scale, void* y, long long M, float eps,
                     const int* rows_live, hipStream_t st) {
     using G = MlpGeom<C, HP>;
-    const void* fn = (const void*)swin_mlp_kernel<C, HP>;
-    if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes) != hipSuccess) {
-        mtmp_set_error("mtmp_swin_mlp: cannot raise dynamic LDS to %zu", G::lds_bytes);
-        return MTMP_ERR_LAUNCH;
-    }
+    static_assert(G::lds_bytes > 48 * 1024, "every launch of this kernel raises its dynamic LDS limit");
+    if (int e = raise_lds("mtmp_swin_mlp", swin_mlp_kernel<C, HP>, G::lds_bytes)) return e;
     hipLaunchKernelGGL((swin_mlp_kernel<C, HP>), dim3((unsigned)((M + 127) / 128)), dim3(256), G::lds_bytes, st, (const bf16*)x,
                        ln_w, ln_b, (const bf16*)w1, b1, (const bf16*)w2, b2, row_scale, rows_per_scale, (bf16*)y, M, eps, rows_live);
     return MTMP_OK;
@@ -842,52 +839,52 @@ __global__ __launch_bounds__(2 * C, 3) void swin_attn_block_kernel(const bf16* x
 // size of the whole batch (a captured hipGraph replays for any number of present images), rows past it are neither read nor
 // written.
 extern "C" int mtmp_layernorm_rows_live(int dtype, const void* x, const float* w, const float* b, void* y, long long rows,
-                                        int C, float eps, int merge, int H, int W, const int32_t* rows_live, void* stream);
-extern "C" int mtmp_layernorm_rows(int dtype, const void* x, const float* w, const float* b, void* y, long long rows,
-                                   int C, float eps, int merge, int H, int W, void* stream) {
-    return mtmp_layernorm_rows_live(dtype, x, w, b, y, rows, C, eps, merge, H, W, nullptr, stream);
-}
-extern "C" int mtmp_layernorm_rows_live(int dtype, const void* x, const float* w, const float* b, void* y, long long rows,
                                         int C, float eps, int merge, int H, int W, const int32_t* rows_live, void* stream) {
     MTMP_CHECK_ARG(x && w && b && y && rows > 0, "mtmp_layernorm_rows: bad pointer / rows");
     MTMP_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 1536 && (!merge || (C % 32 == 0 && H % 2 == 0 && W % 2 == 0)),
                    "mtmp_layernorm_rows: bad shape C=%d merge=%d H=%d W=%d", C, merge, H, W);
-    hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if (dtype == 0) rc = launch_ln_rows<float>(x, w, b, y, rows, C, eps, merge, H, W, rows_live, st);
-    else if (dtype == 1) rc = launch_ln_rows<bf16>(x, w, b, y, rows, C, eps, merge, H, W, rows_live, st);
-    else { mtmp_set_error("mtmp_layernorm_rows: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    if (rc) return rc;
-    MTMP_CHECK_LAUNCH("mtmp_layernorm_rows");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_layernorm_rows", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (int rc = launch_ln_rows<T>(x, w, b, y, rows, C, eps, merge, H, W, rows_live, (hipStream_t)stream)) return rc;
+        MTMP_CHECK_LAUNCH("mtmp_layernorm_rows");
+        return MTMP_OK;
+    });
+}
+extern "C" int mtmp_layernorm_rows(int dtype, const void* x, const float* w, const float* b, void* y, long long rows,
+                                   int C, float eps, int merge, int H, int W, void* stream) {
+    return mtmp_layernorm_rows_live(dtype, x, w, b, y, rows, C, eps, merge, H, W, nullptr, stream);
 }
 
 // out[n,H,W,C] = shifted-window attention of qkv[n,H,W,3C] (q|k|v, head h = 32 columns); window 7,
 // head_dim 32 (C = 32*heads), H % 7 == W % 7 == 0; table [4][heads][64][64] in `dtype` (see header).
-extern "C" int mtmp_swin_window_attn_live(int dtype, const void* qkv, const void* table, void* out, int n_img, int H, int W,
-                                          int C, int heads, int shift, float scale, const int32_t* rows_live, void* stream);
-extern "C" int mtmp_swin_window_attn(int dtype, const void* qkv, const void* table, void* out, int n_img, int H, int W,
-                                     int C, int heads, int shift, float scale, void* stream) {
-    return mtmp_swin_window_attn_live(dtype, qkv, table, out, n_img, H, W, C, heads, shift, scale, nullptr, stream);
+namespace {
+// the launch of both entries; PAD: the kernel that makes the pad tokens (q / k / v = qkv_bias), on the window grid of the padded map
+template <bool PAD>
+int launch_swin_wattn(const char* who, int dtype, const void* qkv, const float* qkv_bias, const void* table, void* out, int n_img,
+                      int H, int W, int C, int heads, int shift, float scale, const int32_t* rows_live, void* stream) {
+    const long long total = (long long)n_img * ((H + WS - 1) / WS) * ((W + WS - 1) / WS) * heads;
+    const int nb = (int)((total + 3) / 4);
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((swin_wattn_kernel<T, PAD>), dim3(nb), dim3(256), 4 * DH * LDV * sizeof(T), (hipStream_t)stream,
+                           (const T*)qkv, (const T*)table, (T*)out, n_img, H, W, C, heads, shift, scale, rows_live, qkv_bias);
+        MTMP_CHECK_LAUNCH(who);
+        return MTMP_OK;
+    });
 }
+}  // namespace
 // (rows_live counts token rows: live images = *rows_live / (H W))
 extern "C" int mtmp_swin_window_attn_live(int dtype, const void* qkv, const void* table, void* out, int n_img, int H, int W,
                                           int C, int heads, int shift, float scale, const int32_t* rows_live, void* stream) {
     MTMP_CHECK_ARG(qkv && table && out, "mtmp_swin_window_attn: null pointer");
     MTMP_CHECK_ARG(n_img > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0 && heads > 0 && C == heads * DH && shift >= 0 &&
                        shift < WS, "mtmp_swin_window_attn: bad shape n=%d H=%d W=%d C=%d heads=%d shift=%d", n_img, H, W, C, heads, shift);
-    const long long total = (long long)n_img * (H / WS) * (W / WS) * heads;
-    const int nb = (int)((total + 3) / 4);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0)
-        hipLaunchKernelGGL((swin_wattn_kernel<float, false>), dim3(nb), dim3(256), 4 * DH * LDV * sizeof(float), st, (const float*)qkv,
-                           (const float*)table, (float*)out, n_img, H, W, C, heads, shift, scale, rows_live, (const float*)nullptr);
-    else if (dtype == 1)
-        hipLaunchKernelGGL((swin_wattn_kernel<bf16, false>), dim3(nb), dim3(256), 4 * DH * LDV * sizeof(bf16), st, (const bf16*)qkv,
-                           (const bf16*)table, (bf16*)out, n_img, H, W, C, heads, shift, scale, rows_live, (const float*)nullptr);
-    else { mtmp_set_error("mtmp_swin_window_attn: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_swin_window_attn");
-    return MTMP_OK;
+    return launch_swin_wattn<false>("mtmp_swin_window_attn", dtype, qkv, nullptr, table, out, n_img, H, W, C, heads, shift, scale,
+                                    rows_live, stream);
+}
+extern "C" int mtmp_swin_window_attn(int dtype, const void* qkv, const void* table, void* out, int n_img, int H, int W,
+                                     int C, int heads, int shift, float scale, void* stream) {
+    return mtmp_swin_window_attn_live(dtype, qkv, table, out, n_img, H, W, C, heads, shift, scale, nullptr, stream);
 }
 
 // The same attention on a map of ANY size: the window grid covers the map padded to whole windows, Hp x Wp = ceil(H / 7) 7 x
@@ -902,35 +899,16 @@ extern "C" int mtmp_swin_window_attn_pad(int dtype, const void* qkv, const float
                    "mtmp_swin_window_attn_pad: bad shape n=%d H=%d W=%d C=%d heads=%d shift=%d", n_img, H, W, C, heads, shift);
     if (H % WS == 0 && W % WS == 0)
         return mtmp_swin_window_attn_live(dtype, qkv, table, out, n_img, H, W, C, heads, shift, scale, rows_live, stream);
-    const int nWh = (H + WS - 1) / WS, nWw = (W + WS - 1) / WS;
-    MTMP_CHECK_ARG(shift == 0 || (nWh > 1 && nWw > 1), "mtmp_swin_window_attn_pad: a padded map of one window is not shifted (H=%d W=%d shift=%d)",
+    MTMP_CHECK_ARG(shift == 0 || (H > WS && W > WS), "mtmp_swin_window_attn_pad: a padded map of one window is not shifted (H=%d W=%d shift=%d)",
                    H, W, shift);
-    const long long total = (long long)n_img * nWh * nWw * heads;
-    const int nb = (int)((total + 3) / 4);
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == 0)
-        hipLaunchKernelGGL((swin_wattn_kernel<float, true>), dim3(nb), dim3(256), 4 * DH * LDV * sizeof(float), st, (const float*)qkv,
-                           (const float*)table, (float*)out, n_img, H, W, C, heads, shift, scale, rows_live, qkv_bias);
-    else if (dtype == 1)
-        hipLaunchKernelGGL((swin_wattn_kernel<bf16, true>), dim3(nb), dim3(256), 4 * DH * LDV * sizeof(bf16), st, (const bf16*)qkv,
-                           (const bf16*)table, (bf16*)out, n_img, H, W, C, heads, shift, scale, rows_live, qkv_bias);
-    else { mtmp_set_error("mtmp_swin_window_attn_pad: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_swin_window_attn_pad");
-    return MTMP_OK;
+    return launch_swin_wattn<true>("mtmp_swin_window_attn_pad", dtype, qkv, qkv_bias, table, out, n_img, H, W, C, heads, shift, scale,
+                                   rows_live, stream);
 }
 
 // y[M,C] = x + row_scale[row / rows_per_scale] * (gelu(LN(x; ln_w, ln_b, eps) W1^T + b1) W2^T + b2): the MLP half of a
 // Swin block (swin_transformer.py:428-449; torchvision MLP keys mlp.0 / mlp.3) in one launch.  bf16 only (dtype 1),
 // C = 96 or 192 (stages 1-2; wider stages use mtmp_layernorm_rows + mtmp_gemm_nt); w1 [4C,C], w2 [C,4C] bf16;
 // ln_w, ln_b, b1, b2 fp32; row_scale (per-image StochasticDepth factor) may be NULL; y must not alias x.
-extern "C" int mtmp_swin_mlp_live(int dtype, const void* x, const float* ln_w, const float* ln_b, const void* w1, const float* b1,
-                                  const void* w2, const float* b2, const float* row_scale, int rows_per_scale, void* y,
-                                  long long M, int C, float eps, const int32_t* rows_live, void* stream);
-extern "C" int mtmp_swin_mlp(int dtype, const void* x, const float* ln_w, const float* ln_b, const void* w1, const float* b1,
-                             const void* w2, const float* b2, const float* row_scale, int rows_per_scale, void* y,
-                             long long M, int C, float eps, void* stream) {
-    return mtmp_swin_mlp_live(dtype, x, ln_w, ln_b, w1, b1, w2, b2, row_scale, rows_per_scale, y, M, C, eps, nullptr, stream);
-}
 extern "C" int mtmp_swin_mlp_live(int dtype, const void* x, const float* ln_w, const float* ln_b, const void* w1, const float* b1,
                                   const void* w2, const float* b2, const float* row_scale, int rows_per_scale, void* y,
                                   long long M, int C, float eps, const int32_t* rows_live, void* stream) {
@@ -944,33 +922,30 @@ extern "C" int mtmp_swin_mlp_live(int dtype, const void* x, const float* ln_w, c
     MTMP_CHECK_LAUNCH("mtmp_swin_mlp");
     return MTMP_OK;
 }
+extern "C" int mtmp_swin_mlp(int dtype, const void* x, const float* ln_w, const float* ln_b, const void* w1, const float* b1,
+                             const void* w2, const float* b2, const float* row_scale, int rows_per_scale, void* y,
+                             long long M, int C, float eps, void* stream) {
+    return mtmp_swin_mlp_live(dtype, x, ln_w, ln_b, w1, b1, w2, b2, row_scale, rows_per_scale, y, M, C, eps, nullptr, stream);
+}
 
 // y[M,N] = LayerNorm(x[M,C]; ln_w, ln_b, eps) W[N,C]^T + bias: norm1 + the qkv projection of a Swin block
 // (swin_transformer.py:428-449, :115-225) in one launch.  bf16 only (dtype 1), C = 96 or 192, N % 32 == 0; W bf16,
 // ln_w / ln_b / bias fp32 (bias may be NULL).
 extern "C" int mtmp_swin_ln_linear_live(int dtype, const void* x, const float* ln_w, const float* ln_b, const void* w,
                                         const float* bias, void* y, long long M, int C, int N, float eps, const int32_t* rows_live,
-                                        void* stream);
-extern "C" int mtmp_swin_ln_linear(int dtype, const void* x, const float* ln_w, const float* ln_b, const void* w,
-                                   const float* bias, void* y, long long M, int C, int N, float eps, void* stream) {
-    return mtmp_swin_ln_linear_live(dtype, x, ln_w, ln_b, w, bias, y, M, C, N, eps, nullptr, stream);
-}
-extern "C" int mtmp_swin_ln_linear_live(int dtype, const void* x, const float* ln_w, const float* ln_b, const void* w,
-                                        const float* bias, void* y, long long M, int C, int N, float eps, const int32_t* rows_live,
                                         void* stream) {
     MTMP_CHECK_ARG(x && ln_w && ln_b && w && y, "mtmp_swin_ln_linear: null pointer");
     MTMP_CHECK_ARG(dtype == 1 && (C == 96 || C == 192) && M > 0 && N > 0 && N % 32 == 0,
                    "mtmp_swin_ln_linear: bf16 with C = 96 or 192 and N %% 32 == 0 only (dtype=%d C=%d N=%d M=%lld)", dtype, C, N, M);
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((M + 127) / 128));
-    if (C == 96)
-        hipLaunchKernelGGL(swin_ln_linear_kernel<96>, grid, dim3(256), 0, st, (const bf16*)x, ln_w, ln_b, (const bf16*)w, bias,
-                           (bf16*)y, M, N, eps, rows_live);
-    else
-        hipLaunchKernelGGL(swin_ln_linear_kernel<192>, grid, dim3(256), 0, st, (const bf16*)x, ln_w, ln_b, (const bf16*)w, bias,
-                           (bf16*)y, M, N, eps, rows_live);
+    const auto kern = C == 96 ? swin_ln_linear_kernel<96> : swin_ln_linear_kernel<192>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((M + 127) / 128)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, ln_w, ln_b,
+                       (const bf16*)w, bias, (bf16*)y, M, N, eps, rows_live);
     MTMP_CHECK_LAUNCH("mtmp_swin_ln_linear");
     return MTMP_OK;
+}
+extern "C" int mtmp_swin_ln_linear(int dtype, const void* x, const float* ln_w, const float* ln_b, const void* w,
+                                   const float* bias, void* y, long long M, int C, int N, float eps, void* stream) {
+    return mtmp_swin_ln_linear_live(dtype, x, ln_w, ln_b, w, bias, y, M, C, N, eps, nullptr, stream);
 }
 
 // out = x + row_scale[image] * (proj(window_attention(qkv(norm1(x)))) + b_proj): the attention half of a Swin block
@@ -979,6 +954,22 @@ extern "C" int mtmp_swin_ln_linear_live(int dtype, const void* x, const float* l
 // table [4][heads][64][64] bf16 as mtmp_swin_window_attn's but with the KEY columns of every 16-key group in accumulator-register
 // order (position 8 h + j of group g holds key 16 g + (j & 3) + 8 (j >> 2) + 4 h); row_scale: fp32[n_img] or NULL;
 // rows_live: NULL or the device word of mtmp_image_slots (rows of the [n_img H W] map in use).
+namespace {
+// the launch of both entries: one workgroup per window of the (PAD: padded) map, nwg of them
+template <bool PAD>
+int launch_swin_attn_block(const char* who, long long nwg, const void* x, const float* ln_w, const float* ln_b, float eps,
+                           const void* wqkv, const float* bqkv, const void* table, const void* wproj, const float* bproj,
+                           const float* row_scale, void* out, int n_img, int H, int W, int C, int shift, float scale,
+                           const int32_t* rows_live, void* stream) {
+    MTMP_CHECK_ARG(nwg < (1ll << 31), "%s: too many windows", who);
+    const auto kern = C == 96 ? swin_attn_block_kernel<96, PAD> : swin_attn_block_kernel<192, PAD>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(2 * C), 0, (hipStream_t)stream, (const bf16*)x, ln_w, ln_b, eps,
+                       (const bf16*)wqkv, bqkv, (const bf16*)table, (const bf16*)wproj, bproj, row_scale, (bf16*)out, n_img, H, W,
+                       shift, scale, rows_live);
+    MTMP_CHECK_LAUNCH(who);
+    return MTMP_OK;
+}
+}  // namespace
 extern "C" int mtmp_swin_attn_block(int dtype, const void* x, const float* ln_w, const float* ln_b, float eps, const void* wqkv,
                                     const float* bqkv, const void* table, const void* wproj, const float* bproj,
                                     const float* row_scale, void* out, int n_img, int H, int W, int C, int heads, int shift,
@@ -989,19 +980,8 @@ extern "C" int mtmp_swin_attn_block(int dtype, const void* x, const float* ln_w,
                        W % WS == 0 && shift >= 0 && shift < WS,
                    "mtmp_swin_attn_block: bf16 with C = 96 or 192, heads = C / 32, maps that are multiples of 7 only "
                    "(dtype=%d C=%d heads=%d n=%d H=%d W=%d shift=%d)", dtype, C, heads, n_img, H, W, shift);
-    const long long nwg = (long long)n_img * (H / WS) * (W / WS);
-    MTMP_CHECK_ARG(nwg < (1ll << 31), "mtmp_swin_attn_block: too many windows");
-    hipStream_t st = (hipStream_t)stream;
-    if (C == 96)
-        hipLaunchKernelGGL((swin_attn_block_kernel<96, false>), dim3((unsigned)nwg), dim3(192), 0, st, (const bf16*)x, ln_w, ln_b, eps,
-                           (const bf16*)wqkv, bqkv, (const bf16*)table, (const bf16*)wproj, bproj, row_scale, (bf16*)out, n_img, H,
-                           W, shift, scale, rows_live);
-    else
-        hipLaunchKernelGGL((swin_attn_block_kernel<192, false>), dim3((unsigned)nwg), dim3(384), 0, st, (const bf16*)x, ln_w, ln_b, eps,
-                           (const bf16*)wqkv, bqkv, (const bf16*)table, (const bf16*)wproj, bproj, row_scale, (bf16*)out, n_img, H,
-                           W, shift, scale, rows_live);
-    MTMP_CHECK_LAUNCH("mtmp_swin_attn_block");
-    return MTMP_OK;
+    return launch_swin_attn_block<false>("mtmp_swin_attn_block", (long long)n_img * (H / WS) * (W / WS), x, ln_w, ln_b, eps, wqkv, bqkv,
+                                         table, wproj, bproj, row_scale, out, n_img, H, W, C, shift, scale, rows_live, stream);
 }
 
 // mtmp_swin_attn_block on a map of ANY size: the window grid covers the map padded to whole windows (Hp x Wp = ceil(H / 7) 7 x
@@ -1026,17 +1006,6 @@ extern "C" int mtmp_swin_attn_block_pad(int dtype, const void* x, const float* l
                    "(H=%d W=%d)", H, W);
     MTMP_CHECK_ARG(shift == 0 || nWh > 1, "mtmp_swin_attn_block_pad: a padded map of one window is not shifted (H=%d W=%d shift=%d)", H, W,
                    shift);
-    const long long nwg = (long long)n_img * nWh * nWw;
-    MTMP_CHECK_ARG(nwg < (1ll << 31), "mtmp_swin_attn_block_pad: too many windows");
-    hipStream_t st = (hipStream_t)stream;
-    if (C == 96)
-        hipLaunchKernelGGL((swin_attn_block_kernel<96, true>), dim3((unsigned)nwg), dim3(192), 0, st, (const bf16*)x, ln_w, ln_b, eps,
-                           (const bf16*)wqkv, bqkv, (const bf16*)table, (const bf16*)wproj, bproj, row_scale, (bf16*)out, n_img, H,
-                           W, shift, scale, rows_live);
-    else
-        hipLaunchKernelGGL((swin_attn_block_kernel<192, true>), dim3((unsigned)nwg), dim3(384), 0, st, (const bf16*)x, ln_w, ln_b, eps,
-                           (const bf16*)wqkv, bqkv, (const bf16*)table, (const bf16*)wproj, bproj, row_scale, (bf16*)out, n_img, H,
-                           W, shift, scale, rows_live);
-    MTMP_CHECK_LAUNCH("mtmp_swin_attn_block_pad");
-    return MTMP_OK;
+    return launch_swin_attn_block<true>("mtmp_swin_attn_block_pad", (long long)n_img * nWh * nWw, x, ln_w, ln_b, eps, wqkv, bqkv, table,
+                                        wproj, bproj, row_scale, out, n_img, H, W, C, shift, scale, rows_live, stream);
 }

@@ -137,11 +137,7 @@ int launch_ln_rows_bwd(const void* x, const float* w, const void* dy, void* dx, 
     const size_t sm = (size_t)4 * (64 / G) * 2 * C * sizeof(float);
 #define MTMP_LNB_CASE(g, n)                                                                                             \
     if (G == g && nch == n) {                                                                                           \
-        if (sm > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(ln_rows_bwd_kernel<T, g, n>),          \
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) { \
-            mtmp_set_error("mtmp_layernorm_rows_bwd: hipFuncSetAttribute(%zu) failed", sm);                             \
-            return MTMP_ERR_LAUNCH;                                                                                     \
-        }                                                                                                               \
+        if (int e = raise_lds("mtmp_layernorm_rows_bwd", ln_rows_bwd_kernel<T, g, n>, sm)) return e;                   \
         hipLaunchKernelGGL((ln_rows_bwd_kernel<T, g, n>), dim3(nb), dim3(256), sm, st, (const T*)x, w, (const T*)dy, (T*)dx, slab, \
                            rows, C, eps);                                                                               \
         return MTMP_OK;                                                                                                 \
@@ -459,76 +455,69 @@ extern "C" int mtmp_layernorm_rows_bwd(int dtype, const void* x, const float* w,
                                        long long rows, int C, float eps, void* stream) {
     MTMP_CHECK_ARG(x && w && dy && dx && slab && rows > 0, "mtmp_layernorm_rows_bwd: bad pointer / rows");
     MTMP_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 1536, "mtmp_layernorm_rows_bwd: bad C=%d", C);
-    hipStream_t st = (hipStream_t)stream;
-    int e;
-    if (dtype == 0) e = launch_ln_rows_bwd<float>(x, w, dy, dx, slab, rows, C, eps, st);
-    else if (dtype == 1) e = launch_ln_rows_bwd<bf16>(x, w, dy, dx, slab, rows, C, eps, st);
-    else { mtmp_set_error("mtmp_layernorm_rows_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    if (e) return e;
-    MTMP_CHECK_LAUNCH("mtmp_layernorm_rows_bwd");
-    return MTMP_OK;
+    return with_dtype(dtype, "mtmp_layernorm_rows_bwd", [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        if (int e = launch_ln_rows_bwd<T>(x, w, dy, dx, slab, rows, C, eps, (hipStream_t)stream)) return e;
+        MTMP_CHECK_LAUNCH("mtmp_layernorm_rows_bwd");
+        return MTMP_OK;
+    });
 }
 
+namespace {
+// BWD: dx = dy * GELU'(x); else y = GELU(x) (dy unused)
+template <bool BWD> int launch_gelu(const char* who, int dtype, const void* x, const void* dy, void* y, long long n, void* stream) {
+    const long long n8 = n / 8;
+    const int nb = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        hipLaunchKernelGGL((gelu_kernel<T, BWD>), dim3(nb), dim3(256), 0, (hipStream_t)stream, (const T*)x, (const T*)dy, (T*)y, n8);
+        MTMP_CHECK_LAUNCH(who);
+        return MTMP_OK;
+    });
+}
+}  // namespace
 // y = GELU(x) over n elements (n % 8 == 0): nn.GELU of the Swin MLP (swin_transformer.py:437-439) as its own pass.
 extern "C" int mtmp_gelu_fwd(int dtype, const void* x, void* y, long long n, void* stream) {
     MTMP_CHECK_ARG(x && y && n > 0 && n % 8 == 0, "mtmp_gelu_fwd: bad argument (n=%lld)", n);
-    hipStream_t st = (hipStream_t)stream;
-    const long long n8 = n / 8;
-    const int nb = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
-    if (dtype == 0) hipLaunchKernelGGL((gelu_kernel<float, false>), dim3(nb), dim3(256), 0, st, (const float*)x, (const float*)nullptr, (float*)y, n8);
-    else if (dtype == 1) hipLaunchKernelGGL((gelu_kernel<bf16, false>), dim3(nb), dim3(256), 0, st, (const bf16*)x, (const bf16*)nullptr, (bf16*)y, n8);
-    else { mtmp_set_error("mtmp_gelu_fwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_gelu_fwd");
-    return MTMP_OK;
+    return launch_gelu<false>("mtmp_gelu_fwd", dtype, x, nullptr, y, n, stream);
 }
 
 // dx = dy * GELU'(x) (the derivative of the form mtmp_gelu_fwd / the projection epilogue applies in this build).
 extern "C" int mtmp_gelu_bwd(int dtype, const void* x, const void* dy, void* dx, long long n, void* stream) {
     MTMP_CHECK_ARG(x && dy && dx && n > 0 && n % 8 == 0, "mtmp_gelu_bwd: bad argument (n=%lld)", n);
-    hipStream_t st = (hipStream_t)stream;
-    const long long n8 = n / 8;
-    const int nb = (int)((n8 + 255) / 256 < 8192 ? (n8 + 255) / 256 : 8192);
-    if (dtype == 0) hipLaunchKernelGGL((gelu_kernel<float, true>), dim3(nb), dim3(256), 0, st, (const float*)x, (const float*)dy, (float*)dx, n8);
-    else if (dtype == 1) hipLaunchKernelGGL((gelu_kernel<bf16, true>), dim3(nb), dim3(256), 0, st, (const bf16*)x, (const bf16*)dy, (bf16*)dx, n8);
-    else { mtmp_set_error("mtmp_gelu_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_gelu_bwd");
-    return MTMP_OK;
+    return launch_gelu<true>("mtmp_gelu_bwd", dtype, x, dy, dx, n, stream);
 }
 
 // Autograd of mtmp_swin_window_attn: qkv [n,H,W,3C], table [4][heads][64][64] (dtype), dout [n,H,W,C] ->
 // dqkv [n,H,W,3C] (every element written once: H, W multiples of 7) and dtab float[4][heads][64][64], which the caller ZEROES
 // first (float atomics: the windows of a type add into one plane).
+namespace {
+// the launch of both entries; PAD: the kernel of the padded map (window grid of the padded map; qkv_bias in, dbias out)
+template <bool PAD>
+int launch_swin_wattn_bwd(const char* who, int dtype, const void* qkv, const float* qkv_bias, const void* table, const void* dout,
+                          void* dqkv, float* dtab, float* dbias, int n_img, int H, int W, int C, int heads, int shift, float scale,
+                          void* stream) {
+    const long long tasks = (long long)n_img * ((H + WS - 1) / WS) * ((W + WS - 1) / WS) * heads;
+    const int nb = (int)((tasks + 3) / 4);
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        constexpr size_t sm = (size_t)4 * 3 * DH * LDV * sizeof(T) + 4 * 2 * LP * sizeof(float);       // bf16: 56 KB
+        static_assert(sm > 48 * 1024, "every launch of this kernel raises its dynamic LDS limit");
+        if (int e = raise_lds(who, swin_wattn_bwd_kernel<T, PAD>, sm)) return e;
+        hipLaunchKernelGGL((swin_wattn_bwd_kernel<T, PAD>), dim3(nb), dim3(256), sm, (hipStream_t)stream, (const T*)qkv, (const T*)table,
+                           (const T*)dout, (T*)dqkv, dtab, n_img, H, W, C, heads, shift, scale, qkv_bias, dbias);
+        MTMP_CHECK_LAUNCH(who);
+        return MTMP_OK;
+    });
+}
+}  // namespace
 extern "C" int mtmp_swin_window_attn_bwd(int dtype, const void* qkv, const void* table, const void* dout, void* dqkv, float* dtab,
                                          int n_img, int H, int W, int C, int heads, int shift, float scale, void* stream) {
     MTMP_CHECK_ARG(qkv && table && dout && dqkv && dtab, "mtmp_swin_window_attn_bwd: null pointer");
     MTMP_CHECK_ARG(n_img > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0 && heads > 0 && C == heads * DH && shift >= 0 && shift < WS,
                    "mtmp_swin_window_attn_bwd: bad shape n=%d H=%d W=%d C=%d heads=%d shift=%d", n_img, H, W, C, heads, shift);
-    hipStream_t st = (hipStream_t)stream;
-    const long long tasks = (long long)n_img * (H / WS) * (W / WS) * heads;
-    const int nb = (int)((tasks + 3) / 4);
-    if (dtype == 0) {
-        const size_t sm = (size_t)4 * 3 * DH * LDV * sizeof(float) + 4 * 2 * LP * sizeof(float);
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<float, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sm) != hipSuccess) {
-            mtmp_set_error("mtmp_swin_window_attn_bwd: hipFuncSetAttribute(%zu) failed", sm);
-            return MTMP_ERR_LAUNCH;
-        }
-        hipLaunchKernelGGL((swin_wattn_bwd_kernel<float, false>), dim3(nb), dim3(256), sm, st, (const float*)qkv, (const float*)table,
-                           (const float*)dout, (float*)dqkv, dtab, n_img, H, W, C, heads, shift, scale, (const float*)nullptr,
-                           (float*)nullptr);
-    } else if (dtype == 1) {
-        const size_t sm = (size_t)4 * 3 * DH * LDV * sizeof(bf16) + 4 * 2 * LP * sizeof(float);       // 56 KB
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<bf16, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)sm) != hipSuccess) {
-            mtmp_set_error("mtmp_swin_window_attn_bwd: hipFuncSetAttribute(%zu) failed", sm);
-            return MTMP_ERR_LAUNCH;
-        }
-        hipLaunchKernelGGL((swin_wattn_bwd_kernel<bf16, false>), dim3(nb), dim3(256), sm, st, (const bf16*)qkv, (const bf16*)table,
-                           (const bf16*)dout, (bf16*)dqkv, dtab, n_img, H, W, C, heads, shift, scale, (const float*)nullptr,
-                           (float*)nullptr);
-    } else { mtmp_set_error("mtmp_swin_window_attn_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_swin_window_attn_bwd");
-    return MTMP_OK;
+    return launch_swin_wattn_bwd<false>("mtmp_swin_window_attn_bwd", dtype, qkv, nullptr, table, dout, dqkv, dtab, nullptr, n_img, H, W,
+                                        C, heads, shift, scale, stream);
 }
 
 // Autograd of mtmp_swin_window_attn_pad: qkv, dqkv [n,H,W,3C] and dout [n,H,W,C] on the UN-padded map of any size; every element
@@ -544,31 +533,8 @@ extern "C" int mtmp_swin_window_attn_pad_bwd(int dtype, const void* qkv, const f
                    "mtmp_swin_window_attn_pad_bwd: bad shape n=%d H=%d W=%d C=%d heads=%d shift=%d", n_img, H, W, C, heads, shift);
     if (H % WS == 0 && W % WS == 0)
         return mtmp_swin_window_attn_bwd(dtype, qkv, table, dout, dqkv, dtab, n_img, H, W, C, heads, shift, scale, stream);
-    const int nWh = (H + WS - 1) / WS, nWw = (W + WS - 1) / WS;
-    MTMP_CHECK_ARG(shift == 0 || (nWh > 1 && nWw > 1),
+    MTMP_CHECK_ARG(shift == 0 || (H > WS && W > WS),
                    "mtmp_swin_window_attn_pad_bwd: a padded map of one window is not shifted (H=%d W=%d shift=%d)", H, W, shift);
-    hipStream_t st = (hipStream_t)stream;
-    const long long tasks = (long long)n_img * nWh * nWw * heads;
-    const int nb = (int)((tasks + 3) / 4);
-    if (dtype == 0) {
-        const size_t sm = (size_t)4 * 3 * DH * LDV * sizeof(float) + 4 * 2 * LP * sizeof(float);
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<float, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
-            mtmp_set_error("mtmp_swin_window_attn_pad_bwd: hipFuncSetAttribute(%zu) failed", sm);
-            return MTMP_ERR_LAUNCH;
-        }
-        hipLaunchKernelGGL((swin_wattn_bwd_kernel<float, true>), dim3(nb), dim3(256), sm, st, (const float*)qkv, (const float*)table,
-                           (const float*)dout, (float*)dqkv, dtab, n_img, H, W, C, heads, shift, scale, qkv_bias, dbias);
-    } else if (dtype == 1) {
-        const size_t sm = (size_t)4 * 3 * DH * LDV * sizeof(bf16) + 4 * 2 * LP * sizeof(float);
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(swin_wattn_bwd_kernel<bf16, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm) != hipSuccess) {
-            mtmp_set_error("mtmp_swin_window_attn_pad_bwd: hipFuncSetAttribute(%zu) failed", sm);
-            return MTMP_ERR_LAUNCH;
-        }
-        hipLaunchKernelGGL((swin_wattn_bwd_kernel<bf16, true>), dim3(nb), dim3(256), sm, st, (const bf16*)qkv, (const bf16*)table,
-                           (const bf16*)dout, (bf16*)dqkv, dtab, n_img, H, W, C, heads, shift, scale, qkv_bias, dbias);
-    } else { mtmp_set_error("mtmp_swin_window_attn_pad_bwd: unknown dtype %d", dtype); return MTMP_ERR_ARG; }
-    MTMP_CHECK_LAUNCH("mtmp_swin_window_attn_pad_bwd");
-    return MTMP_OK;
+    return launch_swin_wattn_bwd<true>("mtmp_swin_window_attn_pad_bwd", dtype, qkv, qkv_bias, table, dout, dqkv, dtab, dbias, n_img, H,
+                                       W, C, heads, shift, scale, stream);
 }

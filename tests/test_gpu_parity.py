@@ -137,6 +137,59 @@ def test_attention_grouped_equals_single_launches(ops, dt):
     assert torch.equal(o2[0], single[1][0]) and torch.equal(o2[1], single[2][0])
 
 
+@pytest.mark.parametrize("M,strided", [(33, False), (300, False), (300, True)])
+def test_gemm_single_equals_group_of_one(ops, M, strided):
+    """Every GEMM product's single entry against its grouped entry called with ONE stream (bf16, same seeds and drop_p): the two
+    share an argument builder and a launcher, so the results are bit-identical.  M = 33: below one 64-row tile; M = 300: the
+    tail of a 128-row block, few enough workgroups that the 64-row tile height is chosen; N = 1024 / K = 256 and N = 256 /
+    K = 1024 are the FFN pair.  strided: every row operand is a [:, :cols] view of a buffer 64 columns wider (lda != K, ldr != N)."""
+    g = torch.Generator().manual_seed(1000 + M)
+    dt, p = torch.bfloat16, 0.1
+
+    def rows(cols):
+        t = torch.randn(M, cols + (64 if strided else 0), generator=g).to(DEV, dt)
+        return t[:, :cols]
+
+    def vec(n, mean=0.0):
+        return (mean + 0.1 * torch.randn(n, generator=g)).to(DEV)
+
+    def same(tag, a, b):
+        for i, (u, v) in enumerate(zip(a, b)):
+            assert torch.equal(u, v), f"{tag}: output {i} of the single form differs from the group of one"
+
+    x, gm, bt = rows(256), vec(256, 1.0), vec(256)
+    wqkv, bqkv = (torch.randn(768, 256, generator=g) / 16).to(DEV, dt), vec(768)
+    w1, b1 = (torch.randn(1024, 256, generator=g) / 16).to(DEV, dt), vec(1024)
+    w2, b2 = (torch.randn(256, 1024, generator=g) / 32).to(DEV, dt), vec(256)
+
+    one = ops.ln_gemm_qkv(x, gm, bt, wqkv, bqkv)
+    grp = ops.ln_gemm_qkv_grouped([x], [gm], [bt], [wqkv], [bqkv])
+    same("ln_gemm_qkv", one, [t[0] for t in grp])
+
+    y, xn, st, sg = ops.ln_gemm(x, gm, bt, w1, b1, 1024, relu=True, drop_p=p, seed=77, want_signs=True)
+    grp = ops.ln_gemm_signs_grouped([x], [gm], [bt], [w1], [b1], 1024, p, [77])
+    same("ln_gemm_signs", (y, xn, st, sg), [t[0] for t in grp])
+
+    h, res = rows(1024), rows(256)
+    one = ops.gemm_nt(h, w2, bias=b2, res2d=res, drop_p=p, seed=78)
+    grp = ops.gemm_nt_grouped([h], [w2], [b2], [res], p, [78])
+    same("gemm_nt", [one], grp)
+
+    dy = rows(256)
+    w2t = w2.t().contiguous()                                     # dH = dY W2: the [1024, 256] operand
+    one = ops.gemm_nt_signs(dy, w2t, sg, gate_scale=1 / (1 - p), drop_p=p, seed=79)
+    gy, gad = ops.gemm_nt_signs_drop_grouped([dy], [w2t], [sg], 1 / (1 - p), p, [79])
+    same("gemm_nt_signs_drop", one, (gy[0], gad[0]))
+
+    dh, dres, wt = rows(1024), rows(256), w1.t().contiguous()      # dX of FFN1 through its LayerNorm: wt = W1^T [256, 1024]
+    d1, dg = [], [[]]
+    one = ops.gemm_lnbwd(dh, wt, x, st, gm, d_res2d=dres, defer=d1)
+    ops.reduce_batch(d1)
+    grp = ops.gemm_lnbwd_grouped([dh], [wt], [x], [st], [gm], [dres], [None], dg)
+    ops.reduce_batch(dg[0])
+    same("gemm_lnbwd", one, grp[0])
+
+
 def test_key_norms_table(ops):
     g = torch.Generator().manual_seed(11)
     for dt in DT:
