@@ -63,6 +63,34 @@ int mtmp_attn_bwd_grouped(int dtype, int n, const void* const* q, const void* co
                           const int32_t* const* row_start, void* const* dq, void* const* dk, void* const* dv,
                           float* const* delta_ws, const int* N, const int* ld_qkv, const int* ld_o, const int* ld_do,
                           const int* ld_dqkv, int B, int H, float scale, void* stream);
+/* Prefix-masked forms of the four entries above, for the multi-token bottleneck encoder (mbt_encoder.py:64-94: a fixed boolean
+ * block over the first rows and keys of the score matrix, OR-ed onto the key-pad mask).  Same arguments plus, per stream,
+ * qk_mask (P HOST words, copied into the kernel arguments by the call) and P (0..16): bit j of word i set = query row i does
+ * not attend key j, for i, j < P; the mask is the same for every sample and head of the stream.  Per (b, h):
+ *     O = softmax(Q K^T scale + keymask(kv_len[b]) + prefixmask) V
+ * i.e. the reference's masked_fill_(mask, -65504) + softmax (attention.py:38-41) on every row that keeps a visible key; a
+ * masked pair has probability exactly 0 and no gradient.  Rows >= P of o / o_res / lse / dq are bit-identical to the plain
+ * entries; qk_mask NULL (as a whole or per entry) or P = 0 gives the plain entries' result everywhere.  Refused: P > 16, N < P,
+ * and a mask row that hides all of keys 0..P-1 (so the kernels never meet an empty key set; callers keep kv_len[b] >= P -- the
+ * prefix rows are never pad rows).  The grouped forms take HOST arrays qk_mask[n] / P[n] like their other arrays. */
+int mtmp_attn_prefix_fwd(int dtype, const void* q, const void* k, const void* v, void* o, const void* res, void* o_res,
+                         float* lse, const int32_t* kv_len, const float* key_norms, const uint16_t* qk_mask, int P, int B, int N,
+                         int H, int ld_qkv, int ld_o, float scale, void* stream);
+int mtmp_attn_prefix_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* d_o,
+                         const float* lse, const int32_t* kv_len, const uint16_t* qk_mask, int P, void* dq, void* dk, void* dv,
+                         float* delta_ws, int B, int N, int H, int ld_qkv, int ld_o, int ld_do, int ld_dqkv, float scale,
+                         void* stream);
+int mtmp_attn_prefix_fwd_grouped(int dtype, int n, const void* const* q, const void* const* k, const void* const* v,
+                                 void* const* o, const void* const* res, void* const* o_res, float* const* lse,
+                                 const int32_t* const* kv_len, const int32_t* const* row_start, const float* const* key_norms,
+                                 const uint16_t* const* qk_mask, const int* P, const int* N, const int* ld_qkv, const int* ld_o,
+                                 int B, int H, float scale, void* stream);
+int mtmp_attn_prefix_bwd_grouped(int dtype, int n, const void* const* q, const void* const* k, const void* const* v,
+                                 const void* const* o, const void* const* d_o, const float* const* lse,
+                                 const int32_t* const* kv_len, const int32_t* const* row_start, const uint16_t* const* qk_mask,
+                                 const int* P, void* const* dq, void* const* dk, void* const* dv, float* const* delta_ws,
+                                 const int* N, const int* ld_qkv, const int* ld_o, const int* ld_do, const int* ld_dqkv, int B,
+                                 int H, float scale, void* stream);
 /* Attention of ONE query row per sample -- the CLS token of the last fusion layer of the vital-sign stream: tri_mbt_vsltcls.py:248
  * reads nothing of the encoder's result but outputs[0][:, 0, :], so in the LAST layer only that row's attention output, FFN and
  * residuals feed the loss (its keys / values still come from all rows).  q / k / v [rows, ld_qkv], res [rows, ld_res] (the layer
@@ -289,6 +317,13 @@ int mtmp_candidate_mean_bwd(const float* d_out, const long long* missing_num, fl
 int mtmp_bce_masked_mean(const float* logits, const float* target, const long long* missing_num, float* loss, float* dlogit, int B,
                          void* stream);
 
+/* The same over R <= 4 logit rows with a table of trained rows (the multi-token models: trainer.py:79-83 and 164-168,
+ * ``criterion(output[missing == 0], target.repeat(4)[missing == 0])`` with missing = missing_multitoken[missing_num]): bit
+ * 4 * pattern + row of `table` set = row `row` is trained on a sample with that pattern id (ids are taken & 3).  logits / dlogit
+ * float[R][B]; n is counted on the device.  One launch, any B > 0, no host synchronisation. */
+int mtmp_bce_rows_masked_mean(const float* logits, const float* target, const long long* missing_num, unsigned table, float* loss,
+                              float* dlogit, int R, int B, void* stream);
+
 /* Stream-ordered time stamp: a one-lane kernel on `stream` stores the 100 MHz wall clock into *slot.  Also works inside a
  * captured hipGraph, where HIP events cannot be timed -- bench.py brackets the roofline kernel of the replayed steps with it. */
 int mtmp_timestamp(unsigned long long* slot, void* stream);
@@ -351,6 +386,17 @@ int mtmp_bottleneck_exchange_fwd(int dtype, void* z_v, void* z_i, void* z_t, int
 int mtmp_bottleneck_exchange_bwd(int dtype, void* dz_v, void* dz_i, void* dz_t, int B, int n_v, int n_i, int n_t,
                                  const long long* missing, int resbottle, const float* d_prev_in, float* d_prev_out,
                                  const int32_t* row_start_v, void* stream);
+
+/* Multi-set bottleneck exchange of TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN (mbt_encoder.py:98-101, 178-191), in place:
+ * every stream buffer z_m [B, n_m, 256] (n_m >= 12) carries three of the four bottleneck sets (vit, vi, vt, it) in rows 4 i ..
+ * 4 i + 3, i indexing bottlenecks_map[m] = {0,1,2} / {0,1,3} / {0,2,3}.  New set s of sample b = sum_m weights[s][missing[b]][m] *
+ * (stream m's rows of set s), written into every holder's rows.  weights: float[4][4][3] on the device (set, pattern, stream;
+ * 0 where a stream does not hold the set or b_out_mean_map does not select it); missing: int64[B] in 0..3 (clamped).
+ * _bwd, on the gradient buffers: every holder's rows of set s <- (sum over the holders' rows) * weights[s][missing[b]][m]. */
+int mtmp_bottleneck_exchange_multi_fwd(int dtype, void* z_v, void* z_i, void* z_t, int B, int n_v, int n_i, int n_t,
+                                       const long long* missing, const float* weights, void* stream);
+int mtmp_bottleneck_exchange_multi_bwd(int dtype, void* dz_v, void* dz_i, void* dz_t, int B, int n_v, int n_i, int n_t,
+                                       const long long* missing, const float* weights, void* stream);
 
 /* Grouped forms of the fusion layer's row-wise kernels (bf16): the same operation of up to three token streams (vital signs /
  * image / text) in ONE launch -- see mtmp_attn_fwd_grouped.  All pointer / int arrays are HOST arrays of n entries (1 <= n <= 3),

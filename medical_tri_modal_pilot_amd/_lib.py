@@ -22,6 +22,10 @@ SIGNATURES = {
     "mtmp_attn_cls_bwd": (c_int, [c_int] + [c_void_p] * 3 + [c_int] + [c_void_p] * 8 + [c_int] * 5 + [c_float, c_void_p]),
     "mtmp_attn_fwd_grouped": (c_int, [c_int, c_int] + [c_void_p] * 13 + [c_int, c_int, c_float, c_void_p]),
     "mtmp_attn_bwd_grouped": (c_int, [c_int, c_int] + [c_void_p] * 17 + [c_int, c_int, c_float, c_void_p]),
+    "mtmp_attn_prefix_fwd": (c_int, [c_int] + [c_void_p] * 10 + [c_int] * 6 + [c_float, c_void_p]),
+    "mtmp_attn_prefix_bwd": (c_int, [c_int] + [c_void_p] * 8 + [c_int] + [c_void_p] * 4 + [c_int] * 7 + [c_float, c_void_p]),
+    "mtmp_attn_prefix_fwd_grouped": (c_int, [c_int, c_int] + [c_void_p] * 15 + [c_int, c_int, c_float, c_void_p]),
+    "mtmp_attn_prefix_bwd_grouped": (c_int, [c_int, c_int] + [c_void_p] * 19 + [c_int, c_int, c_float, c_void_p]),
     "mtmp_key_norms_floats": (c_longlong, [c_longlong, c_int]),
     "mtmp_key_norms": (c_int, [c_int, c_void_p, c_void_p, c_longlong, c_int, c_int, c_void_p]),
     "mtmp_attn_bwd": (c_int, [c_int] + [c_void_p] * 11 + [c_int] * 7 + [c_float, c_void_p]),
@@ -106,6 +110,7 @@ SIGNATURES = {
     "mtmp_candidate_mean_fwd": (c_int, [c_void_p] * 3 + [c_int, c_void_p]),
     "mtmp_candidate_mean_bwd": (c_int, [c_void_p] * 3 + [c_int, c_void_p]),
     "mtmp_bce_masked_mean": (c_int, [c_void_p] * 5 + [c_int, c_void_p]),
+    "mtmp_bce_rows_masked_mean": (c_int, [c_void_p] * 3 + [c_uint] + [c_void_p] * 2 + [c_int, c_int, c_void_p]),
     "mtmp_timestamp": (c_int, [c_void_p, c_void_p]),
     "mtmp_swin_ln_linear": (c_int, [c_int] + [c_void_p] * 6 + [c_longlong, c_int, c_int, c_float, c_void_p]),
     "mtmp_swin_ln_linear_live": (c_int, [c_int] + [c_void_p] * 6 + [c_longlong, c_int, c_int, c_float, c_void_p, c_void_p]),
@@ -118,6 +123,8 @@ SIGNATURES = {
     "mtmp_adamw_step": (c_int, [c_void_p] * 5 + [c_longlong] + [c_float] * 5 + [c_int, c_float, c_void_p]),
     "mtmp_bottleneck_exchange_fwd": (c_int, [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mtmp_bottleneck_exchange_bwd": (c_int, [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mtmp_bottleneck_exchange_multi_fwd": (c_int, [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
+    "mtmp_bottleneck_exchange_multi_bwd": (c_int, [c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p, c_void_p, c_void_p]),
     "mtmp_cxr_hist": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p]),
     "mtmp_cxr_resize": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "mtmp_cxr_affine_crop": (c_int, [c_void_p] * 4 + [c_int, c_int, c_void_p]),

@@ -1,0 +1,80 @@
+"""TRI_MBT_VMULTIVSLT -- MI355X-native drop-in for the reference's multi-token tri-modal MBT model
+(builder/models/8_missing_models/tri_mbt_vmultivslt.py:10-195).
+
+The embeddings, the frozen Swin-T image encoder (under no_grad, present images only) and the forward signature are those of
+TRI_MBT_VSLTCLS; the fusion encoder is TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN (four CLS rows on the vital-sign stream,
+four sets of bottleneck rows, prefix-masked attention), and the head reads the FOUR CLS rows of the vital-sign stream's output:
+LayerNorm, the demographic embedding appended, one ``fc_lists[i]`` = Linear -> LayerNorm -> ReLU -> Linear per row (:140-147,
+181-187).  The forward returns the four logits per sample, [4, B]; the reference's ``missing_trainer`` consumes them in its
+``"multi" in args.model`` branches (trainer.py:164-168: BCE over the heads whose modalities are present; :218-221: the head that
+``missing_num`` names), and so does builder/trainer here (ops.bce_rows_masked_mean).  There is no ``rmse_layer``.
+
+Nothing but stream 0's output is read, so the last layer's image and text blocks are dead, as in the benchmarked model: they are
+not run and are no ``hot_parameters()``.
+"""
+import torch
+import torch.nn as nn
+
+from medical_tri_modal_pilot_amd.builder.models.src.transformer.mbt_encoder import TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN
+
+from .tri_mbt_vsltcls import TRI_MBT_VSLTCLS, flat_layout
+
+
+class TRI_MBT_VMULTIVSLT(TRI_MBT_VSLTCLS):
+    head_fusable = False          # four LayerNorm heads on four rows: torch ops (HIP heads for them are a follow-up)
+    head_min_train_batch = 1
+    takes_packed_tie = False      # the four CLS rows are concatenated in front of the padded [B, T, 256] embedding
+    side_input_chains = False     # the stream input is torch ops on the caller's stream
+    defer_time_adds = False
+    MASKS = [True, False, True]   # (:116-136: the image keys are unmasked with --multiimages 0)
+    FIRST_STREAM_ONLY = True
+
+    def __init__(self, args):
+        name = type(self).__name__
+        if args.input_types != "vslt_img_txt" or getattr(args, "fullmodal_definition", "txt1_img1") != "txt1_img1":
+            raise NotImplementedError(f"{name} needs --input-types vslt_img_txt --fullmodal-definition txt1_img1: its four heads are "
+                                      "trained by the pattern ids of all three modalities (trainer.py:79-83)")
+        if args.vslt_type != "TIE":
+            raise NotImplementedError(f"{name} is built for --vslt-type TIE (got {args.vslt_type})")
+        if args.multiimages != 0:
+            raise NotImplementedError(f"{name} is built for --multiimages 0")
+        if args.residual_bottlenecks == 1:
+            raise NotImplementedError(f"{name}: --residual-bottlenecks 1 is commented out in the reference's encoder class")
+        if "rmse" in args.auxiliary_loss_type:
+            raise NotImplementedError(f"{name}: the rmse auxiliary loss is commented out in the reference's multi-token branches")
+        super().__init__(args)
+        self.fusion_transformer = TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN(
+            batch_size=args.batch_size, n_modality=self.n_modality, bottlenecks_n=self.bottlenecks_n,
+            fusion_startidx=args.mbt_fusion_startIdx, d_input=self.model_dim, n_layers=self.num_layers, n_head=self.num_heads,
+            d_model=self.model_dim, d_ff=self.model_dim * 4, dropout=self.dropout, pe_maxlen=2500, resbottle=False,
+            use_pe=[False, False, True], mask=list(self.MASKS), compute_dtype=self.compute_dtype)
+        self.fusion_transformer.first_stream_output_only = self.FIRST_STREAM_ONLY
+        # the reference's module order behind the encoder: layer_norms_after_concat, [rmse_layer,] fc_lists (:140-147)
+        del self.rmse_layer
+        del self.fc_list
+        self._make_heads()
+
+    def _make_heads(self):
+        self.fc_lists = nn.ModuleList([nn.Sequential(
+            nn.Linear(self.model_dim * 2, self.model_dim, bias=True), nn.LayerNorm(self.model_dim), self.activations["relu"],
+            nn.Linear(self.model_dim, self.output_dim, bias=True)) for _ in range(4)])
+
+    def hot_parameters(self):
+        L = self.num_layers
+        skip = ["img_encoder.", "fusion_transformer.layer_norms_after_concat.", "activations.",
+                f"fusion_transformer.layer_stacks.{L - 1}.1.", f"fusion_transformer.layer_stacks.{L - 1}.2."]
+        named = [(n, p) for n, p in self.named_parameters() if not n.startswith(tuple(skip))]
+        return flat_layout(named, self.fusion_transformer.layer_stacks)
+
+    def backward_stage_params(self, lo: int, hi: int, head: bool):
+        raise NotImplementedError("staged backward graphs are not built for the multi-token encoder (supports_segments = False)")
+
+    def _head_rows(self, outputs):
+        """[4, B, 256]: the rows the four heads read (:181)"""
+        return torch.stack([outputs[0][:, i, :] for i in range(4)])
+
+    def _head(self, outputs, demo_embedding, age, gen, missing, fused_head):
+        rows = self.layer_norms_after_concat(self._head_rows(outputs).float())
+        rows = torch.cat([rows, demo_embedding.unsqueeze(0).expand(4, -1, -1)], dim=2)
+        o = torch.stack([fc(rows[i]) for i, fc in enumerate(self.fc_lists)])                  # [4, B, 1]
+        return o.squeeze(-1), None, None

@@ -345,3 +345,152 @@ class BimodalTransformerEncoder_MBT(nn.Module):
         out0, out1, _, _ = ops.FusionStackFn.apply(streams[0], streams[1], None, self.bottlenecks, *params, cfg)
         nb = self.bottlenecks_n
         return [out0[:, nb:], out1[:, nb:]], 0
+
+
+class TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN(nn.Module):
+    """Multi-token bottleneck fusion (reference: builder/models/src/transformer/mbt_encoder.py:9-193).
+
+    Same constructor, parameter names and forward contract as the reference.  What differs from TrimodalTransformerEncoder_MBT:
+      * four CLS rows on the vital-sign stream (``cls_token`` [1, 4, 256]), none on the image and text streams;
+      * four SETS of four bottleneck rows -- vit, vi, vt, it -- of which every stream carries three as a 12-row prefix
+        (``bottlenecks_map``); in the first layer all of them are the one parameter ``bottlenecks`` [1, 4, 256], so its gradient is
+        the sum over the nine slots (autograd sums it: the prefix is a torch expression);
+      * a fixed boolean mask over the first 16 x 16 (vital signs) / 12 x 12 (image, text) block of the score matrix decides which
+        CLS row and which bottleneck set see which (``prefix_masks``, :64-94), on top of the key-pad mask -- the attention kernels
+        take it as ``qk_mask`` words; an unmasked stream (``mask[m]`` false) gets neither, as in the reference (:164-174);
+      * after a fusion layer every set becomes the mean over the holders that ``b_out_mean_map`` selects for the sample's pattern
+        (ops.bottleneck_exchange_multi).
+    The layers run on the layer engine through ops.MultiTokenStackFn; the stream input (prefix | CLS | tokens, LayerNorm, PE on the
+    text stream, dropout) is torch ops.  Every layer is a fusion layer (``fusion_startidx`` 0); ``resbottle`` is commented out in
+    the reference class and refused here.  ``first_stream_output_only`` (set by a model that reads stream 0's output only): the
+    last layer's image / text blocks are not run and their outputs read as zeros."""
+    supports_segments = False
+    n_cls = 4
+    n_prefix = ops.N_PREFIX
+
+    def __init__(self, batch_size: int, n_modality: int, bottlenecks_n: int, fusion_startidx: int, d_input: int, n_layers: int,
+                 n_head: int, d_model: int, d_ff: int, dropout: float = 0.1, pe_maxlen: int = 5000, txt_idx: int = 2,
+                 resbottle: bool = False, use_pe: list = [False, False, True], mask: list = [True, True, True],
+                 compute_dtype: torch.dtype = torch.bfloat16):
+        super().__init__()
+        if n_modality != 3 or bottlenecks_n != 4:
+            raise ValueError("TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN needs three streams and four bottleneck rows per set")
+        if resbottle:
+            raise NotImplementedError("--residual-bottlenecks 1: the reference has it commented out in this class (mbt_encoder.py:154-190)")
+        if fusion_startidx != 0:
+            raise NotImplementedError("the multi-token encoder is built for --mbt-fusion-startIdx 0 (every layer a fusion layer)")
+        self.use_pe, self.mask = use_pe, mask
+        self.n_modality, self.fusion_idx, self.txt_idx = n_modality, fusion_startidx, txt_idx
+        self.n_layers, self.d_model, self.bottlenecks_n = n_layers, d_model, bottlenecks_n
+        self.resbottle = resbottle
+        self.compute_dtype = compute_dtype
+        self.idx_order = torch.arange(0, batch_size).type(torch.LongTensor)
+        self.layer_norms_after_concat = nn.LayerNorm(self.d_model)       # unused by forward, kept for state_dict parity
+        self.layer_norms_in = nn.ModuleList([nn.LayerNorm(d_model) for _ in range(n_modality)])
+        self.positional_encoding = PositionalEncoding(d_model, max_len=pe_maxlen)
+        self.dropout = nn.Dropout(dropout)
+        self.final_cls_tokens_num = self.n_cls
+        self.cls_token = nn.Parameter(torch.randn(1, self.n_cls, d_model))
+        self.bottlenecks = nn.Parameter(torch.randn(1, bottlenecks_n, d_model))
+        self.bottlenecks_map = [list(r) for r in ops.MULTI_BOTTLENECKS_MAP]
+        self.layer_stacks = nn.ModuleList(nn.ModuleList([
+            TransformerEncoderLayer(d_model=d_model, num_heads=n_head, d_ff=d_ff, dropout_p=dropout)
+            for _ in range(n_modality)]) for _ in range(n_layers))
+
+    def _side_streams(self, dev):
+        """no side streams: the three streams of a layer go out as one grouped launch on the caller's stream"""
+        return None
+
+    # ---- integer artefacts (bit-exact with the reference) ---------------------------------
+    @staticmethod
+    def prefix_masks() -> List[torch.Tensor]:
+        """The three boolean masks of :64-94 (True = the query row does not attend the key): [16,16], [12,12], [12,12].  Rows / keys
+        0..11 are the stream's three bottleneck sets; 12..15 of the first are the CLS rows: CLS i sees set i and itself (CLS 3 only
+        itself), a set sees itself and, on the vital-sign stream, its CLS row.  The image mask has ONE masked row (``[::12, :12]``)."""
+        v = torch.ones(16, 16)
+        v[:4, :4] = 0
+        v[4:8, 4:8] = 0
+        v[8:12, 8:12] = 0
+        for c in range(12, 16):
+            v[c, c] = 0
+        for c, a in ((12, 0), (13, 4), (14, 8)):
+            v[c, a:a + 4] = 0
+            v[a:a + 4, c] = 0
+        i = torch.zeros(12, 12)
+        i[::12, :12] = 1
+        t = torch.ones(12, 12)
+        for m_ in (i, t):
+            m_[:4, :4] = 0
+            m_[4:8, 4:8] = 0
+            m_[8:12, 8:12] = 0
+        return [v.ge(0.5), i.ge(0.5), t.ge(0.5)]
+
+    def mask_words(self) -> List[Optional[List[int]]]:
+        """per stream the prefix mask as the attention kernels take it (bit j of word i), None for an unmasked stream"""
+        return [[sum(int(mk[r, c]) << c for c in range(mk.shape[1])) for r in range(mk.shape[0])] if self.mask[m] else None
+                for m, mk in enumerate(self.prefix_masks())]
+
+    def key_lengths(self, varying_lengths, n_tokens, device) -> List[Optional[torch.Tensor]]:
+        """Valid keys per stream INCLUDING the 12 prefix rows (:120-122, 166): vital signs + 4 CLS rows; text length == 3 (that is
+        txt_lengths == 1) -> 0; None for an unmasked stream.  The caller's tensors are not mutated."""
+        out = []
+        for m in range(self.n_modality):
+            if not self.mask[m]:
+                out.append(None)
+                continue
+            v = varying_lengths[m]
+            v = torch.as_tensor(v, device=device).to(torch.int64)
+            if v.dim() == 0:
+                v = v.repeat(n_tokens[m][0])
+            if m == 0:
+                v = v + self.n_cls
+            if m == self.txt_idx:
+                v = torch.where(v == 3, torch.zeros_like(v), v)
+            out.append((v + self.n_prefix).to(torch.int32).contiguous())
+        return out
+
+    def forward(self, enc_outputs, fixed_lengths=None, varying_lengths=None, return_attns=False, fusion_idx=None, missing=None):
+        if len(enc_outputs) != 3:
+            raise ValueError("TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN takes three streams")
+        if fusion_idx not in (None, 0):
+            raise NotImplementedError("the multi-token encoder is built for fusion_idx 0")
+        dev, dt = enc_outputs[0].device, self.compute_dtype
+        B = enc_outputs[0].size(0)
+        kv = self.key_lengths(varying_lengths, [(B, x.size(1)) for x in enc_outputs], dev)
+        # pattern ids outside 0..3: the reference's gather (:187) raises; checked on the host when the ids live there, as an
+        # asynchronous device-side assert otherwise (never inside a capture); the exchange kernel clamps its table index
+        if not missing.is_cuda and missing.numel() and (int(missing.max()) > 3 or int(missing.min()) < 0):
+            raise IndexError("TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN: missing must be in 0..3")
+        missing = missing.to(dev).long().contiguous()
+        if missing.is_cuda and not torch.cuda.is_current_stream_capturing():
+            torch._assert_async(((missing >= 0) & (missing <= 3)).all())
+        # stream input (:113-142): [4 CLS | events] on the vital-sign stream, LayerNorm (+ PE), dropout; then the 12 prefix rows
+        prefix = self.bottlenecks.repeat(1, 3, 1).expand(B, -1, -1)
+        zs = []
+        for m, x in enumerate(enc_outputs):
+            ln = self.layer_norms_in[m]
+            if m == 0:
+                x = torch.cat([self.cls_token.expand(B, -1, -1).to(x.dtype), x], dim=1)
+            y = F.layer_norm(x.float(), (self.d_model,), ln.weight, ln.bias, ln.eps)
+            if self.use_pe[m]:
+                y = y + self.positional_encoding(x.size(1))
+            zs.append(torch.cat([prefix.to(dt), self.dropout(y).to(dt)], dim=1).contiguous())
+        fl = list(self.layer_stacks)
+        first_only = bool(getattr(self, "first_stream_output_only", False))
+        dead = lambda li, m: first_only and li == len(fl) - 1 and m > 0
+        all_fused = iter(type(fl[0][0]).fused_weights_of(
+            [layer for li, layers in enumerate(fl) for m, layer in enumerate(layers) if not dead(li, m)], dt))
+        params, fused, seeds, p = [], [], [], 0.0
+        for li, layers in enumerate(fl):
+            frow, srow = [], []
+            for m, layer in enumerate(layers):
+                params += layer.param_list()
+                frow.append(None if dead(li, m) else next(all_fused))
+                p, sd = layer.dropout_args()
+                srow.append(sd)
+            fused.append(frow)
+            seeds.append(srow)
+        cfg = dict(n_layers=len(fl), kv=kv, masks=self.mask_words(), missing=missing, drop_p=p, seeds=seeds, fused=fused,
+                   first_only=first_only)
+        outs = ops.MultiTokenStackFn.apply(zs[0], zs[1], zs[2], *params, cfg)
+        return [o[:, self.n_prefix:] for o in outs], 0

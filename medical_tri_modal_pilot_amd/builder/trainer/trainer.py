@@ -340,17 +340,31 @@ def unaveraged_heads(args) -> bool:
     return "mbt_vnoshnoavgtr" in str(getattr(args, "model", ""))
 
 
+def multitoken_heads(args) -> bool:
+    """The model hands out four logits per sample [4, B] (heads vit, vi, vt, v) -- keyed on the model's name like the reference's
+    trainer (``"multi" in args.model``, trainer.py:164,218)."""
+    return "multi" in str(getattr(args, "model", ""))
+
+
 def train_loss(args, criterion, output, t):
     """The training loss on the squeezed logits.  Un-averaged heads (trainer.py:169-174): the target repeated over the three rows and
     the criterion over the logits of the modalities that are present -- ops.bce_masked_mean counts them on the device, so there is
-    neither a data-dependent shape nor a host synchronisation and the step can be captured."""
+    neither a data-dependent shape nor a host synchronisation and the step can be captured.  Multi-token heads (:164-168): the same
+    over four rows with the table ``missing_multitoken == 0`` of :79-83 (ops.bce_rows_masked_mean)."""
+    if multitoken_heads(args):
+        return ops.bce_rows_masked_mean(criterion, output.reshape(4, -1).float(), t["final_target"], t["missing_num"],
+                                        ops.MULTI_LOSS_TABLE)
     if unaveraged_heads(args):
         return ops.bce_masked_mean(criterion, output.reshape(3, -1), t["final_target"], t["missing_num"])
     return ops.bce_with_logits(criterion, output, t["final_target"])
 
 
 def eval_logits(args, output, t):
-    """The logits the test flow scores.  Un-averaged heads (trainer.py:223-229): per sample the mean over the present modalities."""
+    """The logits the test flow scores.  Un-averaged heads (trainer.py:223-229): per sample the mean over the present modalities.
+    Multi-token heads (:218-221): per sample the head that its pattern id names, a plain gather."""
+    if multitoken_heads(args):
+        o = output.reshape(4, -1)
+        return o[t["missing_num"].to(o.device).long(), torch.arange(o.shape[1], device=o.device)]
     if unaveraged_heads(args):
         return ops.candidate_mean(output.reshape(3, -1).float(), t["missing_num"])
     return output

@@ -43,6 +43,34 @@ template <typename T> struct AttnArgs {
     const int* row_start = nullptr;
 };
 
+// ---- prefix mask (mtmp_attn_prefix_*): query row i < P does not attend key j < P where bit j of word i is set -- the fixed
+// boolean block that the multi-token bottleneck encoder ORs onto the key-pad mask (mbt_encoder.py:64-94; P <= 16).  It is a
+// second kernel argument of the PM = true instantiations only, so the plain kernels keep their argument block and their code.
+// The host normalises it: bits >= P and words of rows >= P are zero, so a kernel needs no P -- a row or key outside the prefix
+// simply finds an empty word.  row[s][i >> 1] holds the words of query rows i (low half: even i); col is the transposed
+// mask (bit i of word j = bit j of word i) for the dK / dV kernels, where the KEY is the lane.  Every row keeps one visible key
+// < P (checked on the host) and callers keep kv_len >= P, so no row's key set is empty.
+constexpr int PREFIX_MAX = 16;
+struct PrefixMasks { unsigned row[GRP_MAX][PREFIX_MAX / 2], col[GRP_MAX][PREFIX_MAX / 2]; };
+// word of row / key `i` (global index within the sample; 0 for i >= 16): a select chain over the argument words, no indexed read
+MTMP_DEV unsigned prefix_word(const unsigned (&w)[PREFIX_MAX / 2], int i) {
+    unsigned x = 0;
+#pragma unroll
+    for (int j = 0; j < PREFIX_MAX / 2; ++j) {
+        x = (i == 2 * j) ? (w[j] & 0xFFFFu) : x;
+        x = (i == 2 * j + 1) ? (w[j] >> 16) : x;
+    }
+    return x;
+}
+// C operand of a 32 x 32 score product whose accumulator rows are the keys (queries) 0..31 and whose lane holds query (key) word
+// `word`: -inf where the pair is masked, base elsewhere.  Only registers 0..7 of lane-half 0/1 hold rows < 16.
+MTMP_DEV f32x16 prefix_c(const f32x16& base, unsigned word, int half) {
+    f32x16 c = base;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) c[t] = ((word >> acc_row_swz(t, half)) & 1u) ? -INFINITY : base[t];
+    return c;
+}
+
 // ---- LDS staging of a 64-row x 64-col tile by 256 threads, split into FETCH (global ->
 // registers, issued one tile ahead so the loads fly under the MFMAs of the current tile) and
 // PUT (registers -> LDS, after the barrier).  Full tiles are fetched through running pointers; rows
@@ -152,8 +180,9 @@ constexpr int FWD_QWG = 4 * FWD_QW;             // ... per workgroup
 
 template <typename T> constexpr int fwd_stage_elems() { return KT * LDT + tr_elems<T>(); }     // one K + V^T image pair
 
-template <typename T>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel(Grouped<AttnArgs<T>> grp) {
+// (the kernel body; PM: with the prefix mask `pm` -- attn_fwd_kernel / attn_fwd_prefix_kernel below)
+template <typename T, bool PM>
+MTMP_DEV void attn_fwd_body(const Grouped<AttnArgs<T>>& grp, const PrefixMasks& pm) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     T* sbase = reinterpret_cast<T*>(smem_raw);       // 2 x { K rows [KT][LDT] | V image for the transposed role }
     const int wg = xcd_remap(blockIdx.x, gridDim.x);
@@ -176,6 +205,11 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel
     const size_t base = (size_t)row0 * p.ld_qkv + hd * DH;
     const T* Qb = p.q + base; const T* Kb = p.k + base; const T* Vb = p.v + base;
     const int q0w = qt * FWD_QWG + wave * FWD_QW;          // first query row of this wave
+    // prefix mask: only the first query block of the wave that owns rows 0.. meets it, and only in key block 0 of key tile 0
+    // (P <= 16); that unit's score product starts from C = -inf on the masked pairs (see tail_c), the rest of the loop is as it was
+    unsigned mrow = 0;
+    bool mwave = false;                                    // wave-uniform
+    if constexpr (PM) { mrow = prefix_word(pm.row[seg], q0w + r); mwave = q0w == 0; }
     // Prologue: EVERY load of the workgroup's first phase is issued before anything waits -- this lane's entry of the key-norm
     // table (clamped address, unconditional), the Q fragments, the first key tile -- so the wave pays one memory latency, not
     // three in a row (Q -> ||q|| -> table -> first tile, as the code stood through round 3).
@@ -330,8 +364,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel
         // slot is 8 MFMAs beside one unit of softmax, 4 slots per tile.  The state crossing a barrier is s11 (raw scores of
         // unit (1,1)), p01 and the key block's V fragments; it starts as "-inf scores, zero P" so that the first tile needs no
         // special body (its eight idle P.V MFMAs add zeros: 1.5 % of a 16-tile sample).
-        auto body_rot = [&](int it, auto tail_tag, f32x16& s11, Frag<T> (&p01)[2], Frag<T> (&vtp)[2][2]) {
-            constexpr bool TAIL = decltype(tail_tag)::value;
+        auto body_rot = [&](int it, auto tail_tag, auto mask_tag, f32x16& s11, Frag<T> (&p01)[2], Frag<T> (&vtp)[2][2]) {
+            constexpr bool TAIL = decltype(tail_tag)::value, MASK0 = decltype(mask_tag)::value;   // MASK0: tile 0 of the masked wave
             __syncthreads();                                 // tile `it` visible; the other buffer is free for tile it + 1
             const T* sK = sbase + (it & 1) * fwd_stage_elems<T>();
             const T* sV = sK + KT * LDT;
@@ -344,7 +378,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel
             f32x16 c0, c1;
             if (TAIL) { c0 = tail_c(k0); c1 = tail_c(k0 + 32); }
             pv(0, p01, vtp);                                 // slot A: PV(prev 0,1) + S(0,0) || softmax(prev 1,1)
-            if (TAIL) scores_c(s00, ka0, 0, c0); else scores(s00, ka0, 0);
+            if (MASK0) scores_c(s00, ka0, 0, prefix_c(TAIL ? c0 : f32x16{0}, mrow, half));
+            else if (TAIL) scores_c(s00, ka0, 0, c0); else scores(s00, ka0, 0);
             soft(s11, 1, p11);
             load_v(sV, 0, vt0);
             interleave();
@@ -372,8 +407,19 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel
             Frag<T> p01[2] = {frag_zero<T>(), frag_zero<T>()}, vtp[2][2] = {{frag_zero<T>(), frag_zero<T>()}, {frag_zero<T>(), frag_zero<T>()}};
 #pragma unroll
             for (int t = 0; t < 16; ++t) s11[t] = -INFINITY;
-            for (int it = 0; it < nfull; ++it) body_rot(it, std::false_type{}, s11, p01, vtp);
-            if (ntiles > nfull) body_rot(nfull, std::true_type{}, s11, p01, vtp);
+            if constexpr (PM) {                              // tile 0 of the masked wave apart, then the loop as below
+                int it0 = 0;
+                if (mwave) {
+                    if (nfull > 0) body_rot(0, std::false_type{}, std::true_type{}, s11, p01, vtp);
+                    else body_rot(0, std::true_type{}, std::true_type{}, s11, p01, vtp);
+                    it0 = 1;
+                }
+                for (int it = it0; it < nfull; ++it) body_rot(it, std::false_type{}, std::false_type{}, s11, p01, vtp);
+                if (ntiles > nfull && nfull >= it0) body_rot(nfull, std::true_type{}, std::false_type{}, s11, p01, vtp);
+            } else {
+                for (int it = 0; it < nfull; ++it) body_rot(it, std::false_type{}, std::false_type{}, s11, p01, vtp);
+                if (ntiles > nfull) body_rot(nfull, std::true_type{}, std::false_type{}, s11, p01, vtp);
+            }
             Frag<T> p11[2];                                  // drain: PV(last 0,1) || softmax(last 1,1), then PV(last 1,1)
             pv(0, p01, vtp);
             soft(s11, 1, p11);
@@ -382,8 +428,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel
         }
         m[0] = m[1] = 0.f;
     } else {
-        auto body = [&](int it, auto tail_tag) {
-            constexpr bool TAIL = decltype(tail_tag)::value;
+        auto body = [&](int it, auto tail_tag, auto mask_tag) {
+            constexpr bool TAIL = decltype(tail_tag)::value, MASK0 = decltype(mask_tag)::value;
             tile_begin(it);
             const T* sK = sbase + (it & 1) * fwd_stage_elems<T>();
             const T* sV = sK + KT * LDT;
@@ -397,7 +443,9 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel
 #pragma unroll
                 for (int qb = 0; qb < 2; ++qb) {
                     f32x16 st;
-                    if (TAIL) scores_c(st, ka, qb, ct); else scores(st, ka, qb);
+                    // (a masked score is -inf: it stays out of the row maximum and its p is exp2(-inf) = 0)
+                    if (MASK0 && kb == 0 && qb == 0) scores_c(st, ka, qb, prefix_c(TAIL ? ct : f32x16{0}, mrow, half));
+                    else if (TAIL) scores_c(st, ka, qb, ct); else scores(st, ka, qb);
                     // v_max3 is inline asm, which the compiler's hazard recogniser does not see: an asm instruction
                     // that reads an MFMA result too early gets whatever the register holds.  `seed` is an ordinary
                     // instruction on the LAST accumulator register written, so the required wait states are inserted
@@ -429,8 +477,19 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel
                 }
             }
         };
-        for (int it = 0; it < nfull; ++it) body(it, std::false_type{});
-        if (ntiles > nfull) body(nfull, std::true_type{});
+        if constexpr (PM) {
+            int it0 = 0;
+            if (mwave) {
+                if (nfull > 0) body(0, std::false_type{}, std::true_type{});
+                else body(0, std::true_type{}, std::true_type{});
+                it0 = 1;
+            }
+            for (int it = it0; it < nfull; ++it) body(it, std::false_type{}, std::false_type{});
+            if (ntiles > nfull && nfull >= it0) body(nfull, std::true_type{}, std::false_type{});
+        } else {
+            for (int it = 0; it < nfull; ++it) body(it, std::false_type{}, std::false_type{});
+            if (ntiles > nfull) body(nfull, std::true_type{}, std::false_type{});
+        }
     }
     // Epilogue.  A lane owns one query and 4-element pieces of its O row, so direct stores would be 8-byte pieces
     // at a row stride -- partial-line writes (PMC: 72 MB written per launch for a 33 MB output).  The wave's
@@ -492,6 +551,14 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel
             if (q0w + ps * RPP + rsub < Nq) *reinterpret_cast<u32x4_t*>(rrow + (size_t)ps * RPP * p.ld_o) = sv;
         }
     }
+}
+template <typename T>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_kernel(Grouped<AttnArgs<T>> grp) {
+    attn_fwd_body<T, false>(grp, PrefixMasks{});
+}
+template <typename T>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_fwd_prefix_kernel(Grouped<AttnArgs<T>> grp, PrefixMasks pm) {
+    attn_fwd_body<T, true>(grp, pm);
 }
 
 // Max ||k_h||_2 per 32-token block and head of a [M, ld] key matrix (M = B N rows, head h = columns [64h, 64h + 64)):
@@ -639,8 +706,8 @@ template <typename T> struct AttnBwdArgs {
 
 // dQ: workgroup = 128 query rows, loops over key tiles (S^T and dP^T with the query on the lane).
 template <typename T> constexpr int dq_stage_bytes() { return 2 * DualTile<T>::BYTES; }          // K | V
-template <typename T>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_kernel(Grouped<AttnBwdArgs<T>> grp) {
+template <typename T, bool PM>
+MTMP_DEV void attn_bwd_dq_body(const Grouped<AttnBwdArgs<T>>& grp, const PrefixMasks& pm) {
     using DT = DualTile<T>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int wg = xcd_remap(blockIdx.x, gridDim.x);
@@ -662,6 +729,11 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
     const T* Qb = p.q + base; const T* Kb = p.k + base; const T* Vb = p.v + base;
     const int qrow = qt * 128 + wave * 32 + r;
     const float c2 = p.scale * LOG2E;
+    // prefix mask (PM): lse is the masked one, so p = exp2(s - lse) is right for every visible pair; the masked pairs of key block 0
+    // of key tile 0 get -inf instead of -lse as their C operand (p = 0, dS = 0), in the wave that owns query rows 0..
+    unsigned mrow = 0;
+    bool mwave = false;                                    // wave-uniform
+    if constexpr (PM) { mrow = prefix_word(pm.row[seg], qrow); mwave = qt == 0 && wave == 0; }
     // Prologue: every load of the first phase is issued before anything waits (round 4; it used to be three memory latencies in
     // a row: Q / dO / O, then -- behind the delta store -- LSE, then the first key tile): LSE (clamped row, unconditional), the
     // three row fragments, the first K / V tile.
@@ -721,8 +793,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
     //   phase 1:  S, dP (block 1)  ||  exp / mul / cvt (block 0)    | transposed K fragments of block 0
     //   phase 2:  dQ += (block 0)  ||  exp / mul / cvt (block 1)    | transposed K fragments of block 1
     //   phase 3:  dQ += (block 1)
-    auto body = [&](int it, auto tail_tag) {
-        constexpr bool TAIL = decltype(tail_tag)::value;
+    auto body = [&](int it, auto tail_tag, auto mask_tag) {
+        constexpr bool TAIL = decltype(tail_tag)::value, MASK0 = decltype(mask_tag)::value;      // MASK0: tile 0 of the masked wave
         const int k0 = it * KT;
         __syncthreads();                       // tile `it` visible; the other stage is free for tile it + 1
         const char* sK = smem_raw + (it & 1) * dq_stage_bytes<T>();
@@ -740,12 +812,15 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
             }
         };
         auto scores = [&](int kb, Unit& u, const Frag<T> (&ka)[4], const Frag<T> (&va)[4]) {
-            if (TAIL) {
+            if (TAIL || (MASK0 && kb == 0)) {
                 // ragged last tile: -LSE becomes -inf in the accumulator rows of the keys >= kv_len (keys are rows of S^T), so
-                // their p -- and with it dS = p * dP' -- is exactly 0 with no select per score
-                f32x16 cLt;
+                // their p -- and with it dS = p * dP' -- is exactly 0 with no select per score; the prefix-masked pairs likewise
+                f32x16 cLt = cL;
+                if (TAIL) {
 #pragma unroll
-                for (int t = 0; t < 16; ++t) cLt[t] = (k0 + 32 * kb + acc_row_swz(t, half) < kvl) ? nL : -INFINITY;
+                    for (int t = 0; t < 16; ++t) cLt[t] = (k0 + 32 * kb + acc_row_swz(t, half) < kvl) ? nL : -INFINITY;
+                }
+                if (MASK0 && kb == 0) cLt = prefix_c(cLt, mrow, half);
                 u.st = mma_c<T>(ka[0], qf[0], cLt);
             } else
             u.st = mma_c<T>(ka[0], qf[0], cL);
@@ -813,8 +888,19 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
         __builtin_amdgcn_sched_barrier(0);
         grad(d1, tr1);                         // phase 3
     };
-    for (int it = 0; it < min(nfull, ntiles); ++it) body(it, std::false_type{});
-    if (ntiles > nfull) body(nfull, std::true_type{});
+    if constexpr (PM) {                                        // tile 0 of the masked wave apart, then the loop as below
+        int it0 = 0;
+        if (mwave && ntiles > 0) {
+            if (nfull > 0) body(0, std::false_type{}, std::true_type{});
+            else body(0, std::true_type{}, std::true_type{});
+            it0 = 1;
+        }
+        for (int it = it0; it < min(nfull, ntiles); ++it) body(it, std::false_type{}, std::false_type{});
+        if (ntiles > nfull && nfull >= it0) body(nfull, std::true_type{}, std::false_type{});
+    } else {
+        for (int it = 0; it < min(nfull, ntiles); ++it) body(it, std::false_type{}, std::false_type{});
+        if (ntiles > nfull) body(nfull, std::true_type{}, std::false_type{});
+    }
     if (qrow < Nq) {
         const size_t orow = ((size_t)row0 + qrow) * p.ld_dqkv + hd * DH;
 #pragma unroll
@@ -828,6 +914,14 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
             }
     }
 }
+template <typename T>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_kernel(Grouped<AttnBwdArgs<T>> grp) {
+    attn_bwd_dq_body<T, false>(grp, PrefixMasks{});
+}
+template <typename T>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_prefix_kernel(Grouped<AttnBwdArgs<T>> grp, PrefixMasks pm) {
+    attn_bwd_dq_body<T, true>(grp, pm);
+}
 
 // dK/dV: workgroup = 128 keys (a wave owns 32 and keeps dK, dV in registers), loops over query tiles
 // (S and dP with the key on the lane; P^T and dS^T feed the dV / dK MFMAs from the accumulators).
@@ -835,8 +929,8 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dq_ker
 // rows (the contraction runs over queries), and those rows are written as zeros; query rows past N carry
 // -LSE = -inf, so their p and dS are exactly 0.
 template <typename T> constexpr int dkdv_stage_bytes() { return 2 * DualTile<T>::BYTES + 2 * KT * (int)sizeof(float); }   // Q | dO | -lse | -delta
-template <typename T>
-__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkdv_kernel(Grouped<AttnBwdArgs<T>> grp) {
+template <typename T, bool PM>
+MTMP_DEV void attn_bwd_dkdv_body(const Grouped<AttnBwdArgs<T>>& grp, const PrefixMasks& pm) {
     using DT = DualTile<T>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     const int wg = xcd_remap(blockIdx.x, gridDim.x);
@@ -861,6 +955,10 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkdv_k
     const float* Db = p.delta + ((size_t)b * p.H + hd) * p.N;
     const int kw0 = kt * 128 + wave * 32;      // first key of this wave
     const int key = kw0 + r;                   // this lane's key (column of S)
+    // prefix mask (PM): the key is the lane here, so the lane takes its COLUMN of the mask; the masked queries (rows 0..15 of
+    // query block 0 of query tile 0) get -inf instead of -lse as their C operand: p = 0, dS = 0
+    unsigned mcol = 0;
+    if constexpr (PM) mcol = prefix_word(pm.col[seg], key);
     f32x16 dk0 = {0}, dk1 = {0}, dv0 = {0}, dv1 = {0};
     if (kt * 128 < kvl) {                      // workgroup-uniform: keys past kv_len get zero gradients
         const float c2 = p.scale * LOG2E;
@@ -985,6 +1083,7 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkdv_k
                     f32x16 cL0, cD0;
                     Frag<T> qa0[4], oa0[4];
                     load_rowconst(0, cL0, cD0);
+                    if constexpr (PM) { if (it == 0) cL0 = prefix_c(cL0, mcol, half); }
                     load_rows(0, qa0, oa0);
                     load_rowconst(1, cL1, cD1);
                     load_rows(1, qa1, oa1);
@@ -1051,6 +1150,14 @@ __global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkdv_k
             }
     }
 }
+template <typename T>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkdv_kernel(Grouped<AttnBwdArgs<T>> grp) {
+    attn_bwd_dkdv_body<T, false>(grp, PrefixMasks{});
+}
+template <typename T>
+__global__ __launch_bounds__(256, (sizeof(T) == 2 ? 2 : 1)) void attn_bwd_dkdv_prefix_kernel(Grouped<AttnBwdArgs<T>> grp, PrefixMasks pm) {
+    attn_bwd_dkdv_body<T, true>(grp, pm);
+}
 
 // ---- dK/dV, 64 keys per wave (bf16 build, round 5): ONE wave per SIMD, the accumulators in the AGPR half of the register file.
 // Why (round-4 ablations): in the 32-key kernel a wave's 32 MFMAs per tile stand against ~290 other instructions
@@ -1108,7 +1215,8 @@ MTMP_DEV unsigned cvt_pk_bf16(float lo, float hi) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
 }
 
-__global__ __launch_bounds__(256, 1) void attn_bwd_dkdv64_kernel(Grouped<AttnBwdArgs<bf16>> grp) {
+template <bool PM>
+MTMP_DEV void attn_bwd_dkdv64_body(const Grouped<AttnBwdArgs<bf16>>& grp, const PrefixMasks& pm) {
     using T = bf16;
     using DT = DualTile<T>;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1134,6 +1242,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv64_kernel(Grouped<AttnBwd
     const float* Lb = p.lse + ((size_t)b * p.H + hd) * p.N;
     const float* Db = p.delta + ((size_t)b * p.H + hd) * p.N;
     const int kw0 = kt * DKV64_KEYS + wave * 64;             // first key of this wave
+    // prefix mask (PM): the column of this lane's key in key block 0 (key block 1 starts at key 32 >= P); see slot A of tile 0
+    unsigned mcol = 0;
+    if constexpr (PM) mcol = prefix_word(pm.col[seg], kw0 + r);
     f32x16 dv00 = {0}, dv01 = {0}, dk00 = {0}, dk01 = {0}, dv10 = {0}, dv11 = {0}, dk10 = {0}, dk11 = {0};   // d<k|v><key block><dh half>
     if (kt * DKV64_KEYS < kvl) {              // workgroup-uniform: keys past kv_len get zero gradients
         const float c2 = p.scale * LOG2E;
@@ -1321,6 +1432,13 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv64_kernel(Grouped<AttnBwd
                 // A: scores (0,0) | probabilities of the previous tile's (1,1) | gradients of its (1,0); staging: put tile it + 1, fetch tile it + 2
                 slot(staging, sA, dA, kf[0], vf[0], sB, dB, fY, fX, dv00, dv01, dk00, dk01, cur, 0, cur, 0, it + 1, it + 2);
                 STAMP(4 + 8 * it);
+                // prefix mask: sA holds S' of (query block 0, key block 0); on tile 0 its masked pairs become -inf before slot B
+                // takes the exponentials (p = 0, dS = dP' * 0 = 0).  The row constants cannot carry it here: slot B's product for
+                // key block 1 starts from the same registers.  sA's last MFMA is twelve MFMAs back: no hazard to cover.  (Eight
+                // selects on EVERY tile, with an empty word behind tile 0, not a branch on `it`: a peeled first iteration makes
+                // the compiler move the accumulators between register tuples while the MFMAs that write them -- asm
+                // statements it cannot see into -- are still in flight.)
+                if constexpr (PM) { sA = prefix_c(sA, mcol, half); mcol = 0; }
                 // B: scores (0,1) | probabilities (0,0) | gradients of the previous (1,1); reload: rows of block 1, transposed block 0
                 slot(loads, sB, dB, kf[1], vf[1], sA, dA, fX, fY, dv10, dv11, dk10, dk11, cur, 1, cur, 0, 0, 0);
                 STAMP(5 + 8 * it);
@@ -1414,27 +1532,46 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkdv64_kernel(Grouped<AttnBwd
     }
     STAMP(151);
 }
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkdv64_kernel(Grouped<AttnBwdArgs<bf16>> grp) {
+    attn_bwd_dkdv64_body<false>(grp, PrefixMasks{});
+}
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkdv64_prefix_kernel(Grouped<AttnBwdArgs<bf16>> grp, PrefixMasks pm) {
+    attn_bwd_dkdv64_body<true>(grp, pm);
+}
 
 template <typename T> size_t fwd_smem() { return (size_t)2 * fwd_stage_elems<T>() * sizeof(T); }   // >= 4 x 64 x LDT staging rows
 template <typename T> size_t dq_smem() { return (size_t)2 * dq_stage_bytes<T>(); }
 template <typename T> size_t dkdv_smem() { return (size_t)2 * dkdv_stage_bytes<T>(); }
 
-template <typename T> int launch_fwd(int n, const AttnArgs<T>* segs, hipStream_t st) {
+// pm: NULL = the plain kernels; else the PM instantiations with the launch's prefix masks
+template <typename T> int launch_fwd(int n, const AttnArgs<T>* segs, const PrefixMasks* pm, hipStream_t st) {
     int nwg;
     const Grouped<AttnArgs<T>> g = make_group(n, segs, [](const AttnArgs<T>& a) { return ((a.N + FWD_QWG - 1) / FWD_QWG) * a.H * a.B; }, nwg);
     const size_t sm = fwd_smem<T>();
+    if (pm) {
+        if (int e = raise_lds("mtmp_attn_prefix_fwd", attn_fwd_prefix_kernel<T>, sm)) return e;
+        hipLaunchKernelGGL(attn_fwd_prefix_kernel<T>, dim3(nwg), dim3(256), sm, st, g, *pm);
+        MTMP_CHECK_LAUNCH("mtmp_attn_prefix_fwd");
+        return MTMP_OK;
+    }
     if (int e = raise_lds("mtmp_attn_fwd", attn_fwd_kernel<T>, sm)) return e;
     hipLaunchKernelGGL(attn_fwd_kernel<T>, dim3(nwg), dim3(256), sm, st, g);
     MTMP_CHECK_LAUNCH("mtmp_attn_fwd");
     return MTMP_OK;
 }
 
-template <typename T> int launch_bwd(int n, const AttnBwdArgs<T>* segs, hipStream_t st) {
+template <typename T> int launch_bwd(int n, const AttnBwdArgs<T>* segs, const PrefixMasks* pm, hipStream_t st) {
     int nwg;
     const Grouped<AttnBwdArgs<T>> g = make_group(n, segs, [](const AttnBwdArgs<T>& a) { return ((a.N + 127) / 128) * a.H * a.B; }, nwg);
+    if (pm) {
+        if (int e = raise_lds("mtmp_attn_prefix_bwd", attn_bwd_dq_prefix_kernel<T>, dq_smem<T>())) return e;
+        hipLaunchKernelGGL(attn_bwd_dq_prefix_kernel<T>, dim3(nwg), dim3(256), dq_smem<T>(), st, g, *pm);
+        MTMP_CHECK_LAUNCH("mtmp_attn_prefix_bwd(dq)");
+    } else {
     if (int e = raise_lds("mtmp_attn_bwd", attn_bwd_dq_kernel<T>, dq_smem<T>())) return e;
     hipLaunchKernelGGL(attn_bwd_dq_kernel<T>, dim3(nwg), dim3(256), dq_smem<T>(), st, g);      // also writes delta
     MTMP_CHECK_LAUNCH("mtmp_attn_bwd(dq)");
+    }
     if constexpr (sizeof(T) == 2) {
         // long streams (the vital-sign stream): 64 keys per wave, 256 per workgroup; short ones keep the 32-key kernel
         int nmax = 0;
@@ -1444,11 +1581,23 @@ template <typename T> int launch_bwd(int n, const AttnBwdArgs<T>* segs, hipStrea
             const Grouped<AttnBwdArgs<T>> g64 =
                 make_group(n, segs, [](const AttnBwdArgs<T>& a) { return ((a.N + DKV64_KEYS - 1) / DKV64_KEYS) * a.H * a.B; }, nwg64);
             const size_t sm64 = (size_t)BWD64_STAGES * dkdv_stage_bytes<T>() + 4 * DKV64_OUT_BYTES;
+            if (pm) {
+                if (int e = raise_lds("mtmp_attn_prefix_bwd", attn_bwd_dkdv64_prefix_kernel, sm64)) return e;
+                hipLaunchKernelGGL(attn_bwd_dkdv64_prefix_kernel, dim3(nwg64), dim3(256), sm64, st, g64, *pm);
+                MTMP_CHECK_LAUNCH("mtmp_attn_prefix_bwd(dkdv64)");
+                return MTMP_OK;
+            }
             if (int e = raise_lds("mtmp_attn_bwd", attn_bwd_dkdv64_kernel, sm64)) return e;
             hipLaunchKernelGGL(attn_bwd_dkdv64_kernel, dim3(nwg64), dim3(256), sm64, st, g64);
             MTMP_CHECK_LAUNCH("mtmp_attn_bwd(dkdv64)");
             return MTMP_OK;
         }
+    }
+    if (pm) {
+        if (int e = raise_lds("mtmp_attn_prefix_bwd", attn_bwd_dkdv_prefix_kernel<T>, dkdv_smem<T>())) return e;
+        hipLaunchKernelGGL(attn_bwd_dkdv_prefix_kernel<T>, dim3(nwg), dim3(256), dkdv_smem<T>(), st, g, *pm);
+        MTMP_CHECK_LAUNCH("mtmp_attn_prefix_bwd(dkdv)");
+        return MTMP_OK;
     }
     if (int e = raise_lds("mtmp_attn_bwd", attn_bwd_dkdv_kernel<T>, dkdv_smem<T>())) return e;
     hipLaunchKernelGGL(attn_bwd_dkdv_kernel<T>, dim3(nwg), dim3(256), dkdv_smem<T>(), st, g);
@@ -1458,6 +1607,86 @@ template <typename T> int launch_bwd(int n, const AttnBwdArgs<T>* segs, hipStrea
 
 bool attn_shape_ok(int B, int N, int H, int ld_a, int ld_b) {
     return B > 0 && N > 0 && H > 0 && H <= 4 && ld_a >= H * DH && ld_b >= H * DH && (ld_a % 8) == 0 && (ld_b % 8) == 0;
+}
+
+// The prefix masks of a launch as the kernels take them (PrefixMasks): qk_mask[i] = P[i] HOST words, or NULL / P[i] = 0 for a
+// stream without one.  `any` = some stream has a mask (else the launch takes the plain kernels).  Refused: P outside 0..16, a
+// stream shorter than its prefix, and a row that hides every key of the prefix -- the kernels never meet an empty key set.
+int build_prefix(const char* who, int n, const uint16_t* const* qk_mask, const int* P, const int* N, PrefixMasks& pm, bool& any) {
+    pm = PrefixMasks{};
+    any = false;
+    for (int i = 0; i < n; ++i) {
+        const int np = P ? P[i] : 0;
+        MTMP_CHECK_ARG(np >= 0 && np <= PREFIX_MAX, "%s: prefix of %d rows (stream %d): 0..%d", who, np, i, PREFIX_MAX);
+        if (np == 0 || !qk_mask || !qk_mask[i]) continue;
+        MTMP_CHECK_ARG(N[i] >= np, "%s: stream %d has N=%d rows, fewer than its prefix of %d", who, i, N[i], np);
+        const unsigned full = (1u << np) - 1u;
+        for (int r = 0; r < np; ++r) {
+            const unsigned w = qk_mask[i][r] & full;
+            MTMP_CHECK_ARG(w != full, "%s: mask row %d of stream %d hides every key of the prefix", who, r, i);
+            pm.row[i][r >> 1] |= w << (16 * (r & 1));
+            for (int c = 0; c < np; ++c)
+                if ((w >> c) & 1u) pm.col[i][c >> 1] |= (1u << r) << (16 * (c & 1));
+            any = any || w != 0;
+        }
+    }
+    return MTMP_OK;
+}
+
+// The forward / backward entries proper; who = the family name in messages, qk_mask / P: NULL for the plain entries.
+int attn_fwd_entry(const char* who, int dtype, int n, const void* const* q, const void* const* k, const void* const* v,
+                   void* const* o, const void* const* res, void* const* o_res, float* const* lse,
+                   const int32_t* const* kv_len, const int32_t* const* row_start, const float* const* key_norms,
+                   const uint16_t* const* qk_mask, const int* P, const int* N, const int* ld_qkv, const int* ld_o, int B, int H,
+                   float scale, void* stream) {
+    MTMP_CHECK_ARG(n >= 1 && n <= GRP_MAX && q && k && v && o && lse && N && ld_qkv && ld_o, "%s: bad group (n=%d)", who, n);
+    for (int i = 0; i < n; ++i) {
+        MTMP_CHECK_ARG(q[i] && k[i] && v[i] && o[i] && lse[i], "%s: null pointer (stream %d)", who, i);
+        MTMP_CHECK_ARG((!res || !res[i]) == (!o_res || !o_res[i]), "%s: res and o_res must be given together", who);
+        MTMP_CHECK_ARG(!(row_start && row_start[i]) || (kv_len && kv_len[i]), "%s: a packed stream needs kv_len", who);
+        MTMP_CHECK_ARG(attn_shape_ok(B, N[i], H, ld_qkv[i], ld_o[i]), "%s: bad shape B=%d N=%d H=%d ld=%d/%d", who, B, N[i], H,
+                       ld_qkv[i], ld_o[i]);
+    }
+    PrefixMasks pm;
+    bool masked;
+    if (int e = build_prefix(who, n, qk_mask, P, N, pm, masked)) return e;
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        AttnArgs<T> a[GRP_MAX];
+        for (int i = 0; i < n; ++i)
+            a[i] = AttnArgs<T>{(const T*)q[i], (const T*)k[i], (const T*)v[i], (T*)o[i], res ? (const T*)res[i] : nullptr,
+                               o_res ? (T*)o_res[i] : nullptr, lse[i], kv_len ? kv_len[i] : nullptr, key_norms ? key_norms[i] : nullptr,
+                               B, N[i], H, ld_qkv[i], ld_o[i], scale, row_start ? row_start[i] : nullptr};
+        return launch_fwd<T>(n, a, masked ? &pm : nullptr, (hipStream_t)stream);
+    });
+}
+
+int attn_bwd_entry(const char* who, int dtype, int n, const void* const* q, const void* const* k, const void* const* v,
+                   const void* const* o, const void* const* d_o, const float* const* lse, const int32_t* const* kv_len,
+                   const int32_t* const* row_start, const uint16_t* const* qk_mask, const int* P, void* const* dq, void* const* dk,
+                   void* const* dv, float* const* delta_ws, const int* N, const int* ld_qkv, const int* ld_o, const int* ld_do,
+                   const int* ld_dqkv, int B, int H, float scale, void* stream) {
+    MTMP_CHECK_ARG(n >= 1 && n <= GRP_MAX && q && k && v && o && d_o && lse && dq && dk && dv && delta_ws && N && ld_qkv && ld_o &&
+                       ld_do && ld_dqkv, "%s: bad group (n=%d)", who, n);
+    for (int i = 0; i < n; ++i) {
+        MTMP_CHECK_ARG(q[i] && k[i] && v[i] && o[i] && d_o[i] && lse[i] && dq[i] && dk[i] && dv[i] && delta_ws[i],
+                       "%s: null pointer (stream %d)", who, i);
+        MTMP_CHECK_ARG(!(row_start && row_start[i]) || (kv_len && kv_len[i]), "%s: a packed stream needs kv_len", who);
+        MTMP_CHECK_ARG(attn_shape_ok(B, N[i], H, ld_qkv[i], ld_o[i]) && attn_shape_ok(B, N[i], H, ld_do[i], ld_dqkv[i]),
+                       "%s: bad shape B=%d N=%d H=%d", who, B, N[i], H);
+    }
+    PrefixMasks pm;
+    bool masked;
+    if (int e = build_prefix(who, n, qk_mask, P, N, pm, masked)) return e;
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        AttnBwdArgs<T> a[GRP_MAX];
+        for (int i = 0; i < n; ++i)
+            a[i] = AttnBwdArgs<T>{(const T*)q[i], (const T*)k[i], (const T*)v[i], (const T*)d_o[i], lse[i], delta_ws[i],
+                                  kv_len ? kv_len[i] : nullptr, (T*)dq[i], (T*)dk[i], (T*)dv[i], B, N[i], H, ld_qkv[i], ld_do[i],
+                                  ld_dqkv[i], scale, (const T*)o[i], ld_o[i], row_start ? row_start[i] : nullptr};
+        return launch_bwd<T>(n, a, masked ? &pm : nullptr, (hipStream_t)stream);
+    });
 }
 
 }  // namespace
@@ -1470,23 +1699,8 @@ extern "C" int mtmp_attn_fwd_grouped(int dtype, int n, const void* const* q, con
                                      void* const* o, const void* const* res, void* const* o_res, float* const* lse,
                                      const int32_t* const* kv_len, const int32_t* const* row_start, const float* const* key_norms,
                                      const int* N, const int* ld_qkv, const int* ld_o, int B, int H, float scale, void* stream) {
-    MTMP_CHECK_ARG(n >= 1 && n <= GRP_MAX && q && k && v && o && lse && N && ld_qkv && ld_o, "mtmp_attn_fwd: bad group (n=%d)", n);
-    for (int i = 0; i < n; ++i) {
-        MTMP_CHECK_ARG(q[i] && k[i] && v[i] && o[i] && lse[i], "mtmp_attn_fwd: null pointer (stream %d)", i);
-        MTMP_CHECK_ARG((!res || !res[i]) == (!o_res || !o_res[i]), "mtmp_attn_fwd: res and o_res must be given together");
-        MTMP_CHECK_ARG(!(row_start && row_start[i]) || (kv_len && kv_len[i]), "mtmp_attn_fwd: a packed stream needs kv_len");
-        MTMP_CHECK_ARG(attn_shape_ok(B, N[i], H, ld_qkv[i], ld_o[i]), "mtmp_attn_fwd: bad shape B=%d N=%d H=%d ld=%d/%d", B, N[i], H,
-                       ld_qkv[i], ld_o[i]);
-    }
-    return with_dtype(dtype, "mtmp_attn_fwd", [&](auto tag) {
-        using T = typename decltype(tag)::type;
-        AttnArgs<T> a[GRP_MAX];
-        for (int i = 0; i < n; ++i)
-            a[i] = AttnArgs<T>{(const T*)q[i], (const T*)k[i], (const T*)v[i], (T*)o[i], res ? (const T*)res[i] : nullptr,
-                               o_res ? (T*)o_res[i] : nullptr, lse[i], kv_len ? kv_len[i] : nullptr, key_norms ? key_norms[i] : nullptr,
-                               B, N[i], H, ld_qkv[i], ld_o[i], scale, row_start ? row_start[i] : nullptr};
-        return launch_fwd<T>(n, a, (hipStream_t)stream);
-    });
+    return attn_fwd_entry("mtmp_attn_fwd", dtype, n, q, k, v, o, res, o_res, lse, kv_len, row_start, key_norms, nullptr, nullptr, N,
+                          ld_qkv, ld_o, B, H, scale, stream);
 }
 
 extern "C" int mtmp_attn_fwd(int dtype, const void* q, const void* k, const void* v, void* o, const void* res,
@@ -1501,24 +1715,8 @@ extern "C" int mtmp_attn_bwd_grouped(int dtype, int n, const void* const* q, con
                                      const int32_t* const* kv_len, const int32_t* const* row_start, void* const* dq,
                                      void* const* dk, void* const* dv, float* const* delta_ws, const int* N, const int* ld_qkv,
                                      const int* ld_o, const int* ld_do, const int* ld_dqkv, int B, int H, float scale, void* stream) {
-    MTMP_CHECK_ARG(n >= 1 && n <= GRP_MAX && q && k && v && o && d_o && lse && dq && dk && dv && delta_ws && N && ld_qkv && ld_o &&
-                       ld_do && ld_dqkv, "mtmp_attn_bwd: bad group (n=%d)", n);
-    for (int i = 0; i < n; ++i) {
-        MTMP_CHECK_ARG(q[i] && k[i] && v[i] && o[i] && d_o[i] && lse[i] && dq[i] && dk[i] && dv[i] && delta_ws[i],
-                       "mtmp_attn_bwd: null pointer (stream %d)", i);
-        MTMP_CHECK_ARG(!(row_start && row_start[i]) || (kv_len && kv_len[i]), "mtmp_attn_bwd: a packed stream needs kv_len");
-        MTMP_CHECK_ARG(attn_shape_ok(B, N[i], H, ld_qkv[i], ld_o[i]) && attn_shape_ok(B, N[i], H, ld_do[i], ld_dqkv[i]),
-                       "mtmp_attn_bwd: bad shape B=%d N=%d H=%d", B, N[i], H);
-    }
-    return with_dtype(dtype, "mtmp_attn_bwd", [&](auto tag) {
-        using T = typename decltype(tag)::type;
-        AttnBwdArgs<T> a[GRP_MAX];
-        for (int i = 0; i < n; ++i)
-            a[i] = AttnBwdArgs<T>{(const T*)q[i], (const T*)k[i], (const T*)v[i], (const T*)d_o[i], lse[i], delta_ws[i],
-                                  kv_len ? kv_len[i] : nullptr, (T*)dq[i], (T*)dk[i], (T*)dv[i], B, N[i], H, ld_qkv[i], ld_do[i],
-                                  ld_dqkv[i], scale, (const T*)o[i], ld_o[i], row_start ? row_start[i] : nullptr};
-        return launch_bwd<T>(n, a, (hipStream_t)stream);
-    });
+    return attn_bwd_entry("mtmp_attn_bwd", dtype, n, q, k, v, o, d_o, lse, kv_len, row_start, nullptr, nullptr, dq, dk, dv, delta_ws,
+                          N, ld_qkv, ld_o, ld_do, ld_dqkv, B, H, scale, stream);
 }
 
 extern "C" int mtmp_attn_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* d_o,
@@ -1527,6 +1725,45 @@ extern "C" int mtmp_attn_bwd(int dtype, const void* q, const void* k, const void
                              void* stream) {
     return mtmp_attn_bwd_grouped(dtype, 1, &q, &k, &v, &o, &d_o, &lse, &kv_len, nullptr, &dq, &dk, &dv, &delta_ws, &N, &ld_qkv, &ld_o,
                                  &ld_do, &ld_dqkv, B, H, scale, stream);
+}
+
+// Prefix-masked forms: the same launches with, per stream, a fixed boolean mask over the first P[i] x P[i] block of the score
+// matrix (PrefixMasks above).  qk_mask[i]: P[i] HOST words, bit j of word r set = query row r does not attend key j (r, j < P[i]);
+// the words are copied into the kernel arguments, so the array may be freed or changed after the call.  qk_mask / P NULL as a
+// whole, a NULL entry or P[i] = 0: stream i is unmasked; a launch without any set bit takes the plain kernels.  Callers keep
+// kv_len[b] >= P[i] (the prefix rows are never pad rows).
+extern "C" int mtmp_attn_prefix_fwd_grouped(int dtype, int n, const void* const* q, const void* const* k, const void* const* v,
+                                            void* const* o, const void* const* res, void* const* o_res, float* const* lse,
+                                            const int32_t* const* kv_len, const int32_t* const* row_start,
+                                            const float* const* key_norms, const uint16_t* const* qk_mask, const int* P, const int* N,
+                                            const int* ld_qkv, const int* ld_o, int B, int H, float scale, void* stream) {
+    return attn_fwd_entry("mtmp_attn_prefix_fwd", dtype, n, q, k, v, o, res, o_res, lse, kv_len, row_start, key_norms, qk_mask, P, N,
+                          ld_qkv, ld_o, B, H, scale, stream);
+}
+
+extern "C" int mtmp_attn_prefix_fwd(int dtype, const void* q, const void* k, const void* v, void* o, const void* res, void* o_res,
+                                    float* lse, const int32_t* kv_len, const float* key_norms, const uint16_t* qk_mask, int P, int B,
+                                    int N, int H, int ld_qkv, int ld_o, float scale, void* stream) {
+    return mtmp_attn_prefix_fwd_grouped(dtype, 1, &q, &k, &v, &o, &res, &o_res, &lse, &kv_len, nullptr, &key_norms, &qk_mask, &P, &N,
+                                        &ld_qkv, &ld_o, B, H, scale, stream);
+}
+
+extern "C" int mtmp_attn_prefix_bwd_grouped(int dtype, int n, const void* const* q, const void* const* k, const void* const* v,
+                                            const void* const* o, const void* const* d_o, const float* const* lse,
+                                            const int32_t* const* kv_len, const int32_t* const* row_start,
+                                            const uint16_t* const* qk_mask, const int* P, void* const* dq, void* const* dk,
+                                            void* const* dv, float* const* delta_ws, const int* N, const int* ld_qkv, const int* ld_o,
+                                            const int* ld_do, const int* ld_dqkv, int B, int H, float scale, void* stream) {
+    return attn_bwd_entry("mtmp_attn_prefix_bwd", dtype, n, q, k, v, o, d_o, lse, kv_len, row_start, qk_mask, P, dq, dk, dv, delta_ws,
+                          N, ld_qkv, ld_o, ld_do, ld_dqkv, B, H, scale, stream);
+}
+
+extern "C" int mtmp_attn_prefix_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const void* d_o,
+                                    const float* lse, const int32_t* kv_len, const uint16_t* qk_mask, int P, void* dq, void* dk,
+                                    void* dv, float* delta_ws, int B, int N, int H, int ld_qkv, int ld_o, int ld_do, int ld_dqkv,
+                                    float scale, void* stream) {
+    return mtmp_attn_prefix_bwd_grouped(dtype, 1, &q, &k, &v, &o, &d_o, &lse, &kv_len, nullptr, &qk_mask, &P, &dq, &dk, &dv, &delta_ws,
+                                        &N, &ld_qkv, &ld_o, &ld_do, &ld_dqkv, B, H, scale, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------

@@ -1062,6 +1062,71 @@ extern "C" int mtmp_bottleneck_exchange_bwd(int dtype, void* dz_v, void* dz_i, v
     });
 }
 
+// ------------------------------------------------------------------------------------------
+// Multi-set bottleneck exchange (TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN, mbt_encoder.py:98-101, 178-191).  There are
+// four sets of four bottleneck rows -- vit, vi, vt, it -- and every stream carries three of them as its 12 prefix rows: stream m
+// holds set bottlenecks_map[m][i] in rows 4 i .. 4 i + 3 (kSlot below is that map inverted).  After a fusion layer the new value
+// of set s for sample b is  sum_m w[s][pattern(b)][m] * (stream m's rows of set s)  -- the mean over the holders that
+// b_out_mean_map selects, as a weight table float[4 sets][4 patterns][3 streams] on the device (0 for a stream that does not hold
+// the set or is not selected) -- written back into every holder's rows, in place.  One thread per (sample, set, row, feature);
+// the backward sums the holders' gradient rows and hands each stream its share by the same weights.
+namespace {
+
+__device__ const int kSlot[3][4] = {{0, 1, 2, -1}, {0, 1, -1, 2}, {0, -1, 1, 2}};     // [stream][set] -> slot, -1: not held
+
+template <typename T> struct ExchangeMultiArgs {
+    T* z[3];
+    long long bstride[3];     // elements between consecutive samples of stream m
+    const long long* missing; // [B] pattern ids
+    const float* w;           // [4][4][3]
+};
+
+template <typename T, bool BWD> __global__ __launch_bounds__(256) void exchange_multi_kernel(ExchangeMultiArgs<T> p) {
+    const int b = blockIdx.x >> 4, s = (blockIdx.x >> 2) & 3, r = blockIdx.x & 3, f = threadIdx.x;
+    const long long pat = min(max(p.missing[b], 0LL), 3LL);      // checked on the host (IndexError); clamped so that the table holds
+    const float* w = p.w + (s * 4 + pat) * 3;
+    size_t at[3];
+    float acc = 0.f;
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const int slot = kSlot[m][s];
+        if (slot < 0) continue;
+        at[m] = (size_t)b * (size_t)p.bstride[m] + (size_t)(4 * slot + r) * 256 + f;
+        const float x = to_f32(p.z[m][at[m]]);
+        acc = __fadd_rn(acc, BWD ? x : __fmul_rn(x, w[m]));
+    }
+#pragma unroll
+    for (int m = 0; m < 3; ++m)
+        if (kSlot[m][s] >= 0) p.z[m][at[m]] = from_f32<T>(BWD ? __fmul_rn(acc, w[m]) : acc);
+}
+
+template <bool BWD>
+int exchange_multi(const char* who, int dtype, void* z_v, void* z_i, void* z_t, int B, int n_v, int n_i, int n_t,
+                   const long long* missing, const float* weights, void* stream) {
+    MTMP_CHECK_ARG(z_v && z_i && z_t && missing && weights && B > 0 && B <= (1 << 24) && n_v >= 12 && n_i >= 12 && n_t >= 12,
+                   "%s: bad argument (B=%d rows %d/%d/%d)", who, B, n_v, n_i, n_t);
+    return with_dtype(dtype, who, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        ExchangeMultiArgs<T> a{{(T*)z_v, (T*)z_i, (T*)z_t}, {(long long)n_v * D, (long long)n_i * D, (long long)n_t * D}, missing, weights};
+        hipLaunchKernelGGL((exchange_multi_kernel<T, BWD>), dim3(B * 16), dim3(256), 0, (hipStream_t)stream, a);
+        MTMP_CHECK_LAUNCH(who);
+        return MTMP_OK;
+    });
+}
+
+}  // namespace
+
+// In place on the three stream buffers z_m [B, n_m, 256] (n_m >= 12: rows 0..11 = the stream's three bottleneck sets).  missing:
+// int64[B] in 0..3; weights: float[4][4][3] on the device (set, pattern, stream).  _bwd: the same on the gradient buffers.
+extern "C" int mtmp_bottleneck_exchange_multi_fwd(int dtype, void* z_v, void* z_i, void* z_t, int B, int n_v, int n_i, int n_t,
+                                                  const long long* missing, const float* weights, void* stream) {
+    return exchange_multi<false>("mtmp_bottleneck_exchange_multi_fwd", dtype, z_v, z_i, z_t, B, n_v, n_i, n_t, missing, weights, stream);
+}
+extern "C" int mtmp_bottleneck_exchange_multi_bwd(int dtype, void* dz_v, void* dz_i, void* dz_t, int B, int n_v, int n_i, int n_t,
+                                                  const long long* missing, const float* weights, void* stream) {
+    return exchange_multi<true>("mtmp_bottleneck_exchange_multi_bwd", dtype, dz_v, dz_i, dz_t, B, n_v, n_i, n_t, missing, weights, stream);
+}
+
 // ---------------------------------------------------------------------------
 // Batched 2-D transposes in ONE launch: dst_i[cols_i][rows_i] = src_i[rows_i][cols_i]^T for up to TB_MAX matrices of 16- or
 // 32-bit elements.  The encoder layers' K-contiguous backward operands (W2^T, Wqkv^T, W1^T of every block, rebuilt after

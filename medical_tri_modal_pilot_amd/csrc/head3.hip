@@ -277,6 +277,32 @@ __global__ __launch_bounds__(256) void bce_masked_kernel(const float* o, const f
     if (threadIdx.x == 0) loss[0] = s / n;
 }
 
+// The same over R <= 4 logit rows with a trained-rows table: bit 4 * pattern + row of `table` set = row `row` is trained on a
+// sample whose pattern id is `pattern` (the multi-token models: trainer.py:79-83, missing_multitoken == 0).  loss = the mean over
+// the selected (row, sample) pairs, counted here; dlogit = (sigmoid(o) - y) / n on them, 0 elsewhere.  One workgroup.
+__global__ __launch_bounds__(256) void bce_rows_masked_kernel(const float* o, const float* y, const long long* mnum, unsigned table,
+                                                              float* loss, float* dlogit, int R, int B) {
+    __shared__ float red[4];
+    const unsigned rows_all = (1u << R) - 1u;
+    float cnt = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) cnt += (float)__popc((table >> (4 * (int)(mnum[b] & 3))) & rows_all);
+    const float n = block_sum(cnt, red, threadIdx.x);          // (small integers: exact in any order)
+    float s = 0.f;
+    for (int b = threadIdx.x; b < B; b += 256) {
+        const unsigned on = (table >> (4 * (int)(mnum[b] & 3))) & rows_all;
+        const float t = y[b];
+        for (int m = 0; m < R; ++m) {
+            const size_t i = (size_t)m * B + b;
+            const float v = o[i];
+            const bool sel = (on >> m) & 1u;
+            s += sel ? fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v))) : 0.f;
+            dlogit[i] = sel ? (1.0f / (1.0f + expf(-v)) - t) / n : 0.f;
+        }
+    }
+    s = block_sum(s, red, threadIdx.x);
+    if (threadIdx.x == 0) loss[0] = s / n;
+}
+
 inline Sets3 sets_of(const void* const* q, int n_sets) {
     Sets3 s;
     for (int m = 0; m < 3; ++m) {
@@ -382,5 +408,19 @@ extern "C" int mtmp_bce_masked_mean(const float* logits, const float* target, co
     MTMP_CHECK_ARG(logits && target && missing_num && loss && dlogit && B > 0, "mtmp_bce_masked_mean: bad argument (B=%d)", B);
     hipLaunchKernelGGL(bce_masked_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, missing_num, loss, dlogit, B);
     MTMP_CHECK_LAUNCH("mtmp_bce_masked_mean");
+    return MTMP_OK;
+}
+
+// loss[0] = mean over the trained (row, sample) pairs of BCE-with-logits(logits[row][b], target[b]), dlogit [R, B] = its gradient
+// (0 on the other pairs).  logits / dlogit fp32 [R, B], R <= 4; missing_num int64[B]; table: bit 4 * pattern + row = row trained
+// under that pattern id (ids are taken & 3).
+extern "C" int mtmp_bce_rows_masked_mean(const float* logits, const float* target, const long long* missing_num, unsigned table,
+                                         float* loss, float* dlogit, int R, int B, void* stream) {
+    MTMP_CHECK_ARG(logits && target && missing_num && loss && dlogit && B > 0 && R >= 1 && R <= 4,
+                   "mtmp_bce_rows_masked_mean: bad argument (R=%d B=%d)", R, B);
+    MTMP_CHECK_ARG(table <= 0xFFFFu, "mtmp_bce_rows_masked_mean: table has bits outside 4 patterns x 4 rows (%#x)", table);
+    hipLaunchKernelGGL(bce_rows_masked_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, missing_num, table, loss,
+                       dlogit, R, B);
+    MTMP_CHECK_LAUNCH("mtmp_bce_rows_masked_mean");
     return MTMP_OK;
 }

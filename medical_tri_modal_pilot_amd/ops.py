@@ -359,27 +359,47 @@ def key_norms(qkv):
     return out.view(-1, N_HEAD)
 
 
-def attn_fwd(qkv, kv_len, res=None, knorm=None):
+def _mask_words(qk_mask):
+    """A prefix mask (sequence of P ints <= 0xFFFF: bit j of word i = query row i does not attend key j; mtmp_attn_prefix_fwd) as
+    the (host uint16 array, P) pair the library takes; None -> (None, 0)."""
+    if qk_mask is None or len(qk_mask) == 0:
+        return None, 0
+    return (ctypes.c_uint16 * len(qk_mask))(*[int(w) for w in qk_mask]), len(qk_mask)
+
+
+def attn_fwd(qkv, kv_len, res=None, knorm=None, qk_mask=None):
     """qkv [B,N,768] (q|k|v), kv_len int32[B] or None -> (o[B,N,256], o+res | None, lse[B,4,N]).
-    knorm: the key-norm table of key_norms() / ln_gemm(want_knorm=True); None = the online-maximum body everywhere."""
+    knorm: the key-norm table of key_norms() / ln_gemm(want_knorm=True); None = the online-maximum body everywhere.
+    qk_mask: None, or the P <= 16 words of a prefix mask (_mask_words) over the first P query rows and keys."""
     _gpu(qkv)
     B, N, _ = qkv.shape
     es = qkv.element_size()
     o = torch.empty(B, N, D_MODEL, dtype=qkv.dtype, device=qkv.device)
     o_res = torch.empty_like(o) if res is not None else None
     lse = torch.empty(B, N_HEAD, N, dtype=torch.float32, device=qkv.device)
+    if qk_mask is not None:
+        words, P = _mask_words(qk_mask)
+        call("mtmp_attn_prefix_fwd", _dt(qkv), _p(qkv), _p(qkv, D_MODEL * es), _p(qkv, 2 * D_MODEL * es), _p(o), _p(res),
+             _p(o_res), _p(lse), _p(kv_len), _p(knorm), words, P, B, N, N_HEAD, qkv.stride(1), D_MODEL, D_HEAD ** -0.5, _stream())
+        return o, o_res, lse
     call("mtmp_attn_fwd", _dt(qkv), _p(qkv), _p(qkv, D_MODEL * es), _p(qkv, 2 * D_MODEL * es), _p(o), _p(res),
          _p(o_res), _p(lse), _p(kv_len), _p(knorm), B, N, N_HEAD, qkv.stride(1), D_MODEL, D_HEAD ** -0.5, _stream())
     return o, o_res, lse
 
 
-def attn_bwd(qkv, o, d_o, lse, kv_len):
-    """-> dqkv [B,N,768]."""
+def attn_bwd(qkv, o, d_o, lse, kv_len, qk_mask=None):
+    """-> dqkv [B,N,768].  qk_mask: the forward's."""
     _gpu(qkv, o, d_o)
     B, N, _ = qkv.shape
     es = qkv.element_size()
     dqkv = torch.empty_like(qkv)
     delta = torch.empty(B * N_HEAD * N, dtype=torch.float32, device=qkv.device)
+    if qk_mask is not None:
+        words, P = _mask_words(qk_mask)
+        call("mtmp_attn_prefix_bwd", _dt(qkv), _p(qkv), _p(qkv, D_MODEL * es), _p(qkv, 2 * D_MODEL * es), _p(o), _p(d_o),
+             _p(lse), _p(kv_len), words, P, _p(dqkv), _p(dqkv, D_MODEL * es), _p(dqkv, 2 * D_MODEL * es), _p(delta),
+             B, N, N_HEAD, qkv.stride(1), o.stride(1), d_o.stride(1), dqkv.stride(1), D_HEAD ** -0.5, _stream())
+        return dqkv
     call("mtmp_attn_bwd", _dt(qkv), _p(qkv), _p(qkv, D_MODEL * es), _p(qkv, 2 * D_MODEL * es), _p(o), _p(d_o),
          _p(lse), _p(kv_len), _p(dqkv), _p(dqkv, D_MODEL * es), _p(dqkv, 2 * D_MODEL * es), _p(delta),
          B, N, N_HEAD, qkv.stride(1), o.stride(1), d_o.stride(1), dqkv.stride(1), D_HEAD ** -0.5, _stream())
@@ -816,9 +836,17 @@ def _lives(packs):
     return (ctypes.c_void_p * len(packs))(*[None if pk is None else pk.data_ptr() + 4 * (pk.numel() // 2) for pk in packs])
 
 
-def attn_fwd_grouped(qkvs, kv_lens, ress, knorms, packs=None):
+def _masks(qk_masks):
+    """host arrays (pointers to the streams' mask words, their P) of a grouped launch + the word arrays they point into"""
+    pairs = [_mask_words(m) for m in qk_masks]
+    ptrs = (ctypes.c_void_p * len(pairs))(*[None if w is None else ctypes.addressof(w) for w, _ in pairs])
+    return ptrs, _ints([P for _, P in pairs]), pairs
+
+
+def attn_fwd_grouped(qkvs, kv_lens, ress, knorms, packs=None, qk_masks=None):
     """attn_fwd for up to three streams in ONE launch: lists of qkv [B,N_i,768], kv_len, res, knorm (entries may be None)
-    -> lists (o, o_res, lse).  packs: per stream the row_starts() tensor of a packed stream, or None."""
+    -> lists (o, o_res, lse).  packs: per stream the row_starts() tensor of a packed stream, or None.
+    qk_masks: None, or per stream None / the words of its prefix mask (attn_fwd)."""
     _gpu(*qkvs)
     n, B = len(qkvs), qkvs[0].shape[0]
     es, dt, dev = qkvs[0].element_size(), qkvs[0].dtype, qkvs[0].device
@@ -826,6 +854,14 @@ def attn_fwd_grouped(qkvs, kv_lens, ress, knorms, packs=None):
     o = [torch.empty(B, N, D_MODEL, dtype=dt, device=dev) for N in Ns]
     o_res = [None if r is None else torch.empty(B, N, D_MODEL, dtype=dt, device=dev) for N, r in zip(Ns, ress)]
     lse = [torch.empty(B, N_HEAD, N, dtype=torch.float32, device=dev) for N in Ns]
+    if qk_masks is not None and any(m is not None for m in qk_masks):
+        mptr, mP, keep = _masks(qk_masks)
+        with kernel_marks("attn_fwd", Ns[0]):
+            call("mtmp_attn_prefix_fwd_grouped", _dt(qkvs[0]), n, _ptrs(qkvs), _ptrs(qkvs, D_MODEL * es), _ptrs(qkvs, 2 * D_MODEL * es),
+                 _ptrs(o), _ptrs(ress), _ptrs(o_res), _ptrs(lse), _ptrs(kv_lens), _starts(packs), _ptrs(knorms), mptr, mP, _ints(Ns),
+                 _ints([q.stride(1) for q in qkvs]), _ints([D_MODEL] * n), B, N_HEAD, D_HEAD ** -0.5, _stream())
+        del keep
+        return o, o_res, lse
     with kernel_marks("attn_fwd", Ns[0]):
         call("mtmp_attn_fwd_grouped", _dt(qkvs[0]), n, _ptrs(qkvs), _ptrs(qkvs, D_MODEL * es), _ptrs(qkvs, 2 * D_MODEL * es), _ptrs(o),
              _ptrs(ress), _ptrs(o_res), _ptrs(lse), _ptrs(kv_lens), _starts(packs), _ptrs(knorms), _ints(Ns),
@@ -834,14 +870,24 @@ def attn_fwd_grouped(qkvs, kv_lens, ress, knorms, packs=None):
     return o, o_res, lse
 
 
-def attn_bwd_grouped(qkvs, os_, d_os, lses, kv_lens, packs=None):
-    """attn_bwd for up to three streams in two launches (dQ, dK/dV) -> list of dqkv [B,N_i,768]."""
+def attn_bwd_grouped(qkvs, os_, d_os, lses, kv_lens, packs=None, qk_masks=None):
+    """attn_bwd for up to three streams in two launches (dQ, dK/dV) -> list of dqkv [B,N_i,768].  qk_masks: the forward's."""
     _gpu(*qkvs)
     n, B = len(qkvs), qkvs[0].shape[0]
     es = qkvs[0].element_size()
     Ns = [q.shape[1] for q in qkvs]
     dqkv = [torch.empty_like(q) for q in qkvs]
     delta = [torch.empty(B * N_HEAD * N, dtype=torch.float32, device=qkvs[0].device) for N in Ns]
+    if qk_masks is not None and any(m is not None for m in qk_masks):
+        mptr, mP, keep = _masks(qk_masks)
+        with kernel_marks("attn_bwd", Ns[0]):
+            call("mtmp_attn_prefix_bwd_grouped", _dt(qkvs[0]), n, _ptrs(qkvs), _ptrs(qkvs, D_MODEL * es), _ptrs(qkvs, 2 * D_MODEL * es),
+                 _ptrs(os_), _ptrs(d_os), _ptrs(lses), _ptrs(kv_lens), _starts(packs), mptr, mP, _ptrs(dqkv), _ptrs(dqkv, D_MODEL * es),
+                 _ptrs(dqkv, 2 * D_MODEL * es), _ptrs(delta), _ints(Ns), _ints([q.stride(1) for q in qkvs]),
+                 _ints([o.stride(1) for o in os_]), _ints([d.stride(1) for d in d_os]), _ints([d.stride(1) for d in dqkv]), B, N_HEAD,
+                 D_HEAD ** -0.5, _stream())
+        del keep
+        return dqkv
     with kernel_marks("attn_bwd", Ns[0]):
         call("mtmp_attn_bwd_grouped", _dt(qkvs[0]), n, _ptrs(qkvs), _ptrs(qkvs, D_MODEL * es), _ptrs(qkvs, 2 * D_MODEL * es), _ptrs(os_),
              _ptrs(d_os), _ptrs(lses), _ptrs(kv_lens), _starts(packs), _ptrs(dqkv), _ptrs(dqkv, D_MODEL * es),
@@ -1723,6 +1769,58 @@ def bce_masked_mean(criterion, output, target, missing_num):
     return criterion(output[mask], y3[mask])
 
 
+# table[pattern][row] of the multi-token models (trainer.py:79-83, ``missing_multitoken == 0``): head 3 (vital signs alone) is
+# trained on every sample, head 1 (+ image) / head 2 (+ report) where that modality is present, head 0 on complete samples
+MULTI_LOSS_TABLE = ((True, True, True, True), (False, True, False, True), (False, False, True, True), (False, False, False, True))
+
+
+def _table_bits(table, R):
+    if len(table) != 4 or any(len(row) < R for row in table):
+        raise ValueError(f"bce_rows_masked_mean: table[4 patterns][>= {R} rows], got {table!r}")
+    return sum(1 << (4 * p + r) for p in range(4) for r in range(R) if table[p][r])
+
+
+class BceRowsMaskedMean(torch.autograd.Function):
+    """BceMaskedMean over R <= 4 logit rows with a table of trained rows: apply(logits [R, B] fp32, target [B], missing_num [B],
+    table bits (_table_bits)) -> scalar mean over the selected (row, sample) pairs, counted on the device.  One launch forward,
+    one scale backward."""
+
+    @staticmethod
+    def forward(ctx, logits, target, missing_num, bits):
+        _gpu(logits)
+        o, t = _c(logits.detach().float()), _c(target.detach().float().reshape(-1))
+        ids = _ids64(missing_num, o.device)
+        loss = torch.empty(1, dtype=torch.float32, device=o.device)
+        d = torch.empty_like(o)
+        call("mtmp_bce_rows_masked_mean", _p(o), _p(t), _p(ids), int(bits), _p(loss), _p(d), o.shape[0], o.shape[1], _stream())
+        ctx.save_for_backward(d)
+        ctx.shape = logits.shape
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        return _saved_grad_once(ctx, g), None, None, None
+
+
+def bce_rows_masked_mean(criterion, logits, target, missing_num, table=MULTI_LOSS_TABLE):
+    """The training loss of the multi-token models (trainer.py:164-168): criterion over the logits [R, B] (R <= 4) of the rows
+    that ``table[pattern][row]`` marks as trained, the target repeated over the rows.  Through BceRowsMaskedMean when it is the
+    plain mean-reduced BCEWithLogitsLoss on the GPU, else the reference's boolean-index form."""
+    if (logits.dim() != 2 or not 1 <= logits.shape[0] <= 4 or target.numel() != logits.shape[1]
+            or missing_num.numel() != logits.shape[1]):
+        raise ValueError(f"bce_rows_masked_mean: logits [R <= 4, B], target [B], missing_num [B]; got {tuple(logits.shape)}, "
+                         f"{tuple(target.shape)}, {tuple(missing_num.shape)}")
+    R = logits.shape[0]
+    bits = _table_bits(table, R)
+    if (isinstance(criterion, torch.nn.BCEWithLogitsLoss) and criterion.reduction == "mean" and criterion.weight is None
+            and criterion.pos_weight is None and logits.is_cuda and logits.dtype == torch.float32):
+        return BceRowsMaskedMean.apply(logits, target, missing_num, bits)
+    tab = torch.tensor([[bool(table[p][r]) for r in range(R)] for p in range(4)], device=logits.device)
+    mask = tab[missing_num.to(logits.device).long() & 3].t()
+    yr = target.reshape(1, -1).expand(R, -1)
+    return criterion(logits[mask], yr[mask])
+
+
 # ----------------------------------------------------------------------------- stream input (K4)
 class StreamInputFn(torch.autograd.Function):
     """mbt_encoder.py:697-729 + the [bottleneck | CLS | tokens] concatenation of :745 as one launch each way.
@@ -1917,8 +2015,9 @@ FusedWeights = namedtuple("FusedWeights", "wqkv bqkv w1 w2 w2t wqkvt w1t")
 #   o, r1     cls_layer_forward: of the CLS rows only ([B,256]); r1 with ffn_rows: the gathered B * R rows the FFN ran on
 #   pack      row_starts() of a PACKED stream;  ffn_rows: layer_forward_grouped(ffn_rows=R)
 #   cls_rows  cls_layer_forward: where the backward adds the CLS rows' residual gradient;  cls_tok: their row within a sample
+#   qk_mask   the words of the stream's prefix mask (attn_fwd), or None
 LayerSaved = namedtuple("LayerSaved", "z kv_len g1 g2 wqkvt w1t w2t xn1 st1 qkv o lse r1 xn2 st2 h drop_p seeds hsign "
-                                      "pack ffn_rows cls_rows cls_tok", defaults=(None,) * 4)
+                                      "pack ffn_rows cls_rows cls_tok qk_mask", defaults=(None,) * 5)
 
 
 def _packed_full(rows2d, B, N):
@@ -1928,13 +2027,14 @@ def _packed_full(rows2d, B, N):
     return full
 
 
-def layer_forward(z, kv_len, P, fused, drop_p, seeds, pack=None):
+def layer_forward(z, kv_len, P, fused, drop_p, seeds, pack=None, qk_mask=None):
     """z [B,N,256] contiguous.  P: the 14 parameters; fused: FusedWeights (or its seven tensors in that order).
     Returns (out [B,N,256], LayerSaved).
     pack (row_starts(kv_len, N)): z is a PACKED stream buffer (the samples' kv_len rows back to back) and so is `out`.  This
     single-stream form (the fp32 parity build's) reads the row count on the HOST -- one sync, no hipGraph -- and runs the row
     kernels on the live rows as dense [live, C] matrices; the attention kernels address the samples through pack exactly as the
-    bf16 grouped launches do (layer_forward_grouped takes the count from the device instead)."""
+    bf16 grouped launches do (layer_forward_grouped takes the count from the device instead).
+    qk_mask: None or the words of a prefix mask over the stream's first rows and keys (attn_fwd)."""
     B, N, D = z.shape
     M = B * N
     f = FusedWeights._make(fused)
@@ -1943,14 +2043,15 @@ def layer_forward(z, kv_len, P, fused, drop_p, seeds, pack=None):
     qkv, xn1, st1, knorm = ln_gemm_qkv(z2, P[P_G1], P[P_B1], f.wqkv, f.bqkv)
     if pack is None:
         qkv = qkv.view(B, N, 3 * D)
-        o, r1, lse = attn_fwd(qkv, kv_len, res=z, knorm=knorm)
+        o, r1, lse = attn_fwd(qkv, kv_len, res=z, knorm=knorm, qk_mask=qk_mask)
     else:
         qkv = _packed_full(qkv, B, N)
-        (o,), (r1,), (lse,) = attn_fwd_grouped([qkv], [kv_len], [z], [knorm], [pack])
+        (o,), (r1,), (lse,) = attn_fwd_grouped([qkv], [kv_len], [z], [knorm], [pack], [qk_mask])
     r1_2 = r1.view(M, D)[:live]
     h, xn2, st2, hsign = ln_gemm(r1_2, P[P_G2], P[P_B2], f.w1, P[P_C1], 4 * D, relu=True, drop_p=drop_p, seed=seeds[0], want_signs=True)
     out = gemm_nt(h, f.w2, P[P_C2], res2d=r1_2, drop_p=drop_p, seed=seeds[1])
-    saved = LayerSaved(z, kv_len, P[P_G1], P[P_G2], f.wqkvt, f.w1t, f.w2t, xn1, st1, qkv, o, lse, r1, xn2, st2, h, drop_p, seeds, hsign, pack)
+    saved = LayerSaved(z, kv_len, P[P_G1], P[P_G2], f.wqkvt, f.w1t, f.w2t, xn1, st1, qkv, o, lse, r1, xn2, st2, h, drop_p, seeds, hsign, pack,
+                       qk_mask=qk_mask)
     return (out.view(B, N, D) if pack is None else _packed_full(out, B, N)), saved
 
 
@@ -2055,9 +2156,10 @@ def layer_backward(saved, d_out, sink=None, late=None):
     dr1, dg2, db2 = gemm_lnbwd(dh, sv.w1t, sv.r1.view(M, D)[:live], sv.st2, sv.g2, d_res2d=d_out, gb_out=dst.gb2, defer=red)
     # ---- attention: r1 = z + o  ->  d_o = dr1
     if pack is None:
-        dqkv = attn_bwd(sv.qkv, sv.o, dr1.view(B, N, D), sv.lse, sv.kv_len).view(M, 3 * D)
+        dqkv = attn_bwd(sv.qkv, sv.o, dr1.view(B, N, D), sv.lse, sv.kv_len, sv.qk_mask).view(M, 3 * D)
     else:
-        dqkv = attn_bwd_grouped([sv.qkv], [sv.o], [_packed_full(dr1, B, N)], [sv.lse], [sv.kv_len], [pack])[0].view(M, 3 * D)[:live]
+        dqkv = attn_bwd_grouped([sv.qkv], [sv.o], [_packed_full(dr1, B, N)], [sv.lse], [sv.kv_len], [pack],
+                                [sv.qk_mask])[0].view(M, 3 * D)[:live]
     dwqkv, dbqkv = gemm_tn(dqkv, sv.xn1, out=dst.wqkv, defer=red)   # [768,256], [768]
     dz, dg1, db1 = gemm_lnbwd(dqkv, sv.wqkvt, sv.z.view(M, D)[:live], sv.st1, sv.g1, d_res2d=dr1, gb_out=dst.gb1, defer=red)
     _finish_reductions(red, [] if sink is None else [sink], late)
@@ -2167,14 +2269,16 @@ def grouped_ok(z) -> bool:
     return tuning.GROUPED_LAUNCHES and z.dtype == torch.bfloat16
 
 
-def layer_forward_grouped(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ffn_rows=None):
+def layer_forward_grouped(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ffn_rows=None, qk_masks=None):
     """layer_forward for the active streams of one fusion layer with ONE launch per step (lists, one entry per stream).
     packs: per stream None or the row_starts() tensor of a PACKED stream (its [B, N, 256] buffers then hold the samples' valid
     rows back to back: every kernel below works on pack[B] rows instead of B * N).
     ffn_rows = R: only rows 0..R-1 of every sample of the OUTPUT are read by anyone (the image / text streams in the last layer
     they run in: the bottleneck exchange takes rows 0..3 and nothing else follows) -- the FFN half runs on those B * R rows, the
-    other output rows are left unwritten; the attention half stays dense (the R rows attend to all keys).  Padded streams only."""
+    other output rows are left unwritten; the attention half stays dense (the R rows attend to all keys).  Padded streams only.
+    qk_masks: None, or per stream None / the words of its prefix mask (attn_fwd)."""
     n = len(zs)
+    qk_masks = [None] * n if qk_masks is None else list(qk_masks)
     B, D = zs[0].shape[0], D_MODEL
     Ns = [z.shape[1] for z in zs]
     packs = [None] * n if packs is None else list(packs)
@@ -2183,7 +2287,7 @@ def layer_forward_grouped(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ff
     z2 = [z.view(B * N, D) for z, N in zip(zs, Ns)]
     qkv, xn1, st1, knorm = ln_gemm_qkv_grouped(z2, par(P_G1), par(P_B1), f.wqkv, f.bqkv, packs)
     qkv = [q.view(B, N, 3 * D) for q, N in zip(qkv, Ns)]
-    o, r1, lse = attn_fwd_grouped(qkv, kv_lens, list(zs), knorm, packs)
+    o, r1, lse = attn_fwd_grouped(qkv, kv_lens, list(zs), knorm, packs, qk_masks)
     R = ffn_rows
     if R is not None:
         if any(pk is not None for pk in packs) or any(N < R for N in Ns):
@@ -2201,7 +2305,8 @@ def layer_forward_grouped(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ff
             f_[:, :R] = o_.view(B, R, D)
         out = full
     saved = [LayerSaved(zs[i], kv_lens[i], Ps[i][P_G1], Ps[i][P_G2], f.wqkvt[i], f.w1t[i], f.w2t[i], xn1[i], st1[i], qkv[i], o[i], lse[i],
-                        r1_2[i] if R is not None else r1[i], xn2[i], st2[i], h[i], drop_p, seeds[i], hsign[i], packs[i], R) for i in range(n)]
+                        r1_2[i] if R is not None else r1[i], xn2[i], st2[i], h[i], drop_p, seeds[i], hsign[i], packs[i], R,
+                        qk_mask=qk_masks[i]) for i in range(n)]
     return [out[i].view(B, Ns[i], D) for i in range(n)], saved
 
 
@@ -2230,7 +2335,7 @@ def layer_backward_grouped(saveds, d_outs, sinks, late):
         for f_, d in zip(dense, dr1):
             f_[:, :R] = d.view(B, R, D)
         dr1 = [f_.view(-1, D) for f_ in dense]
-    dqkv = attn_bwd_grouped(sv.qkv, sv.o, [d.view(B, N, D) for d, N in zip(dr1, Ns)], sv.lse, sv.kv_len, packs)
+    dqkv = attn_bwd_grouped(sv.qkv, sv.o, [d.view(B, N, D) for d, N in zip(dr1, Ns)], sv.lse, sv.kv_len, packs, list(sv.qk_mask))
     dqkv = [d.view(M, 3 * D) for d, M in zip(dqkv, Ms)]
     gwq = gemm_tn_grouped(dqkv, sv.xn1, [d.wqkv for d in dst], reds, packs)
     l1 = gemm_lnbwd_grouped(dqkv, sv.wqkvt, [t.view(M, D) for t, M in zip(sv.z, Ms)], sv.st1, sv.g1, dr1, [d.gb1 for d in dst], reds, packs)
@@ -2240,14 +2345,16 @@ def layer_backward_grouped(saveds, d_outs, sinks, late):
 
 
 class EncoderLayerFn(torch.autograd.Function):
-    """layer_forward / layer_backward as one autograd node (layer-level API and tests)."""
+    """layer_forward / layer_backward as one autograd node (layer-level API and tests):
+    apply(z, kv_len, *the 14 parameters, fused, drop_p, seeds[, qk_mask])."""
 
     @staticmethod
     def forward(ctx, z, kv_len, *rest):
         _gpu(z)
-        P, (fused, drop_p, seeds) = rest[:PARAMS_PER_LAYER], rest[PARAMS_PER_LAYER:]
-        out, saved = layer_forward(_c(z), kv_len, P, fused, drop_p, seeds)
+        P, (fused, drop_p, seeds, *opt) = rest[:PARAMS_PER_LAYER], rest[PARAMS_PER_LAYER:]
+        out, saved = layer_forward(_c(z), kv_len, P, fused, drop_p, seeds, qk_mask=opt[0] if opt else None)
         ctx.saved = saved
+        ctx.n_opt = len(opt)
         ctx.wshapes = (P[P_W1].shape, P[P_W2].shape)
         return out
 
@@ -2260,7 +2367,7 @@ class EncoderLayerFn(torch.autograd.Function):
         dz, g = layer_backward(ctx.saved, d_out)
         g = list(g)
         g[P_W1], g[P_W2] = g[P_W1].view(ctx.wshapes[0]), g[P_W2].view(ctx.wshapes[1])
-        return (dz, None, *g, None, None, None)
+        return (dz, None, *g, None, None, None) + (None,) * ctx.n_opt
 
 
 # ----------------------------------------------------------------------------- fusion stack engine
@@ -2569,3 +2676,134 @@ class FusionStackFn(torch.autograd.Function):
         d_bott = d_bott.sum(0, keepdim=True)
         dx = [None if dz[m] is None else dz[m][:, NB:] for m in range(3)]
         return (dx[0], dx[1], dx[2], d_bott, *pgrads, None)
+
+
+# ----------------------------------------------------------------------------- multi-token fusion stack
+# TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN (reference mbt_encoder.py:9-193).  Four sets of four bottleneck rows -- vit,
+# vi, vt, it -- and every stream carries three of them as a 12-row prefix (MULTI_BOTTLENECKS_MAP); a fixed boolean mask over the
+# prefix (and the four CLS rows of the vital-sign stream) decides who sees which set (attn_fwd qk_mask); after a fusion layer
+# every set becomes the mean over the holders that MULTI_B_OUT_MEAN_MAP selects for the sample's pattern.
+MULTI_BOTTLENECKS_MAP = ((0, 1, 2), (0, 1, 3), (0, 2, 3))         # stream -> the sets in its prefix rows 4 i .. 4 i + 3
+# set -> pattern -> positions IN THE SET'S HOLDER LIST (streams in order) that are averaged (mbt_encoder.py:98-101; the fourth
+# set's pattern 3 reads the image stream's rows although both holders are missing -- kept as it is)
+MULTI_B_OUT_MEAN_MAP = (((0, 1, 2), (0, 1), (0, 2), (0,)), ((0, 1), (0, 1), (0,), (0,)), ((0, 1), (0,), (0, 1), (0,)),
+                        ((0, 1), (0,), (1,), (0,)))
+N_PREFIX = 12
+
+
+def multi_exchange_weights() -> torch.Tensor:
+    """float[4 sets][4 patterns][3 streams]: the weight of stream m's rows in the new value of a set (mtmp_bottleneck_exchange_multi_fwd)"""
+    w = torch.zeros(4, 4, 3)
+    for s in range(4):
+        holders = [m for m in range(3) if s in MULTI_BOTTLENECKS_MAP[m]]
+        for pat, sel in enumerate(MULTI_B_OUT_MEAN_MAP[s]):
+            for i in sel:
+                w[s, pat, holders[i]] = 1.0 / len(sel)
+    return w
+
+
+_multi_w_dev = {}
+
+
+def _multi_w(dev):
+    """Device copy of the table, made once (a pageable H2D copy cannot be captured in a hipGraph)."""
+    k = (dev.type, dev.index)
+    if k not in _multi_w_dev:
+        _multi_w_dev[k] = multi_exchange_weights().to(dev).contiguous()
+    return _multi_w_dev[k]
+
+
+def bottleneck_exchange_multi(z, missing, backward=False):
+    """In place on z = [z_v, z_i, z_t] ([B, n_m >= 12, 256] contiguous): the prefix rows <- the exchanged sets (backward: on the
+    gradient buffers, the transposed table)."""
+    _gpu(*z)
+    if any(not t.is_contiguous() or t.dtype != z[0].dtype for t in z):
+        raise ValueError("bottleneck_exchange_multi: three contiguous buffers of one dtype")
+    call("mtmp_bottleneck_exchange_multi_bwd" if backward else "mtmp_bottleneck_exchange_multi_fwd", _dt(z[0]), _p(z[0]), _p(z[1]),
+         _p(z[2]), z[0].shape[0], z[0].shape[1], z[1].shape[1], z[2].shape[1], _p(missing), _p(_multi_w(z[0].device)), _stream())
+
+
+class BottleneckExchangeMultiFn(torch.autograd.Function):
+    """The exchange as an autograd node on copies: apply(z_v, z_i, z_t, missing int64[B]) -> the three buffers with their prefix
+    rows exchanged (layer-level API and tests; MultiTokenStackFn works in place on its own buffers)."""
+
+    @staticmethod
+    def forward(ctx, zv, zi, zt, missing):
+        z = [_c(t).clone() for t in (zv, zi, zt)]
+        missing = _c(missing.to(device=zv.device, dtype=torch.int64))
+        bottleneck_exchange_multi(z, missing)
+        ctx.missing = missing
+        return tuple(z)
+
+    @staticmethod
+    def backward(ctx, dv, di, dt_):
+        dz = [_c(t).clone() for t in (dv, di, dt_)]
+        bottleneck_exchange_multi(dz, ctx.missing, backward=True)
+        return dz[0], dz[1], dz[2], None
+
+
+class MultiTokenStackFn(torch.autograd.Function):
+    """All fusion layers of the multi-token encoder as one autograd node on the layer engine (layer_forward[_grouped] /
+    layer_backward[_grouped]): apply(z_v, z_i, z_t, *layer_params, cfg) -> (out_v, out_i, out_t), every buffer [B, 12 + N_m, 256]
+    = [prefix | tokens] in the compute dtype.  A layer writes new buffers, the exchange overwrites their prefix rows in place and
+    they are the next layer's inputs.  cfg: n_layers, kv (int32[B] | None per stream, prefix included), masks (words | None per
+    stream), missing (int64[B]), drop_p, seeds[l][m], fused[l][m] (None for a block that is not run), first_only (the caller reads
+    stream 0's output only: the last layer runs that stream alone; the other outputs are zeros without a gradient)."""
+
+    @staticmethod
+    def forward(ctx, zv, zi, zt, *rest):
+        cfg, params = rest[-1], rest[:-1]
+        _gpu(zv)
+        L = cfg["n_layers"]
+        z = [_c(t) for t in (zv, zi, zt)]
+        saved, active = [], []
+        for li in range(L):
+            ms = [0] if (cfg.get("first_only") and li == L - 1) else [0, 1, 2]
+            Ps = [params[(li * 3 + m) * PARAMS_PER_LAYER:(li * 3 + m + 1) * PARAMS_PER_LAYER] for m in ms]
+            if grouped_ok(z[0]):
+                outs, sv = layer_forward_grouped([z[m] for m in ms], [cfg["kv"][m] for m in ms], Ps, [cfg["fused"][li][m] for m in ms],
+                                                 cfg["drop_p"], [cfg["seeds"][li][m] for m in ms], qk_masks=[cfg["masks"][m] for m in ms])
+            else:
+                outs, sv = zip(*[layer_forward(z[m], cfg["kv"][m], P, cfg["fused"][li][m], cfg["drop_p"], cfg["seeds"][li][m],
+                                               qk_mask=cfg["masks"][m]) for m, P in zip(ms, Ps)])
+            saved.append(list(sv))
+            active.append(ms)
+            z = [outs[ms.index(m)] if m in ms else None for m in range(3)]
+            if li < L - 1:                 # (the reference exchanges after the last layer too; nothing reads that result)
+                bottleneck_exchange_multi(z, cfg["missing"])
+        ctx.saved, ctx.active, ctx.cfg = saved, active, cfg
+        ctx.shapes = ([t.shape for t in (zv, zi, zt)], [p.shape for p in params], zv.dtype, zv.device)
+        ctx.set_materialize_grads(False)
+        outs = [t if t is not None else torch.zeros(shp, dtype=zv.dtype, device=zv.device) for t, shp in zip(z, ctx.shapes[0])]
+        ctx.mark_non_differentiable(*[o for o, t in zip(outs, z) if t is None])
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, d_v, d_i, d_t):
+        cfg, saved, active = ctx.cfg, ctx.saved, ctx.active
+        zshapes, pshapes, dt, dev = ctx.shapes
+        pgrads = [None] * len(pshapes)
+        dz = [None, None, None]
+        for m, g in enumerate((d_v, d_i, d_t)):
+            if m in active[-1]:
+                dz[m] = torch.zeros(zshapes[m], dtype=dt, device=dev) if g is None else _c(g).to(dt).clone()
+        for li in range(len(active) - 1, -1, -1):
+            ms = active[li]
+            if li < len(active) - 1:       # this layer's outputs went through an exchange
+                bottleneck_exchange_multi(dz, cfg["missing"], backward=True)
+            sv, dzs = [saved[li][ms.index(m)] for m in ms], [dz[m] for m in ms]
+            if grouped_ok(sv[0].z):
+                gdz, gg = layer_backward_grouped(sv, dzs, [None] * len(ms), None)
+            else:
+                gdz, gg = zip(*[layer_backward(s_, d) for s_, d in zip(sv, dzs)])
+            saved[li] = None
+            dz = [None, None, None]
+            for i, m in enumerate(ms):
+                dz[m] = gdz[i]
+                base = (li * 3 + m) * PARAMS_PER_LAYER
+                for k in range(PARAMS_PER_LAYER):
+                    pgrads[base + k] = gg[i][k].view(pshapes[base + k])
+            if len(ms) == 1 and li > 0:    # the streams the last layer skipped re-enter with zero gradient
+                for m in (1, 2):
+                    dz[m] = torch.zeros(zshapes[m], dtype=dt, device=dev)
+        return (dz[0], dz[1], dz[2], *pgrads, None)
