@@ -120,7 +120,7 @@ class TrimodalTransformerEncoder_MBT(nn.Module):
         first_only_ = bool(getattr(self, "first_stream_output_only", False)) or self.vsltonly == 1
         pack_v = None
         if (getattr(self, "pack_rows", False) and fused_in and n_pre == 0 and first_only_ and kv_fused[0] is not None
-                and dt == torch.bfloat16 and tuning.GROUPED_LAUNCHES and not return_attns):
+                and dt == torch.bfloat16 and not return_attns):
             pack_v = ops.row_starts(kv_fused[0], self.bottlenecks_n + 1 + enc_outputs[0].size(1))
         self.last_pack = pack_v
         # the model may have produced the image / text embeddings on the two side streams (inputs_on_side_streams):
@@ -192,7 +192,7 @@ class TrimodalTransformerEncoder_MBT(nn.Module):
                       and self.vsltonly != 1)
         skip_last = first_only or (self.vsltonly == 1 and fused_in and not self.resbottle)     # (vsltonly: ops.FusionStackFn skips them too)
         # ... and when the reader takes nothing but stream 0's CLS row (first_stream_output_only) and the last layer runs that
-        # stream alone, the last layer computes that one query row only (ops.cls_layer_forward: K / V of all rows, attention, FFN
+        # stream alone, the last layer computes that one query row only (ops.layer_forward cls_tok: K / V of all rows, attention, FFN
         # and residuals of the CLS row -- the other rows of the last layer's output feed nothing)
         cls_only = (bool(getattr(self, "first_stream_output_only", False)) and fused_in and (first_only or self.vsltonly == 1)
                     and bool(getattr(self, "cls_only_last_layer", True)) and not return_attns)
@@ -210,7 +210,7 @@ class TrimodalTransformerEncoder_MBT(nn.Module):
         zs = (streams[0], streams[1], streams[2])
         cls_v = None
         # the layer in front of a CLS-only last layer: its image / text outputs feed the bottleneck exchange and nothing else
-        # (ops.layer_forward_grouped ffn_rows) -- by GLOBAL layer index, whatever segment it falls into
+        # (ops.layer_forward ffn_rows) -- by GLOBAL layer index, whatever segment it falls into
         g_ex = len(fl) - 2 if (cls_only and not self.resbottle) else -1
         for si in range(len(bounds) - 1):
             seg = fl[bounds[si]:bounds[si + 1]]

@@ -307,7 +307,7 @@ def swin_attn_block_pad(x, ln_w, ln_b, eps, wqkv, bqkv, table, heads, shift, wpr
 
 
 REDUCE_BATCH_MAX = 8
-# (scheduling switches -- LATE_REDUCTIONS, FOLD_DROPOUT_BWD, DEFER_REDUCTIONS, GROUP_MODE ... -- live in tuning.py)
+# (scheduling switches -- GROUP_MODE, FFN_ROWS_BEFORE_LAST ... -- live in tuning.py)
 
 
 def gemm_tn(dy2d, x2d, want_bias=True, out=None, defer=None, pack=None):
@@ -843,12 +843,52 @@ def _masks(qk_masks):
     return ptrs, _ints([P for _, P in pairs]), pairs
 
 
+# ---- the ops of the layer engine: lists with one entry per stream in, lists out.  The dtype decides how they launch, so the engine
+# does not: bf16 = ONE launch over the streams through the `_grouped` entry (csrc/common.hip.h, Grouped; a group of one is the
+# single entry: same argument builder, same launcher -- tests/test_layer_engine_gpu.py); fp32 (the parity build) = one launch per
+# stream.  The three streams of a fusion layer are 1005 / 54 / 133 tokens long; as three launches on three HIP streams the short
+# ones held whole-CU workgroup slots beside the long one's kernels (round 2: every vital-sign-stream kernel 15-40 % slower in the
+# step than alone, ~1.2 ms per step, ~200 launches).  Which streams share a launch is the caller's cut (launch_groups,
+# tuning.GROUP_MODE).  `packs`: per stream None or the row_starts() tensor of
+# a PACKED stream -- for the row kernels of a packed fp32 stream the count of its rows in use instead, read on the HOST by the
+# engine (_row_limits): they run on those rows as dense matrices and their results are padded back to the buffer's rows, so
+# callers see the shapes of the bf16 launches.
+def _opt(vs, n):
+    return [None] * n if vs is None else list(vs)
+
+
+def _row_limits(zs, packs):
+    """packs as the row kernels take them: a packed fp32 stream's tensor -> its live row count (one sync per stream: no hipGraph)"""
+    return [int(pk[z.shape[0]]) if pk is not None and z.dtype != torch.bfloat16 else pk for z, pk in zip(zs, packs)]
+
+
+def _live_rows(t, pack):
+    return t[:pack] if isinstance(pack, int) and t is not None else t
+
+
+def _padded(t, M, pack):
+    """rows [live, C] of a packed fp32 stream -> an [M, C] buffer that begins with them (the rest is never read)"""
+    if not isinstance(pack, int):
+        return t
+    full = torch.empty(M, t.shape[1], dtype=t.dtype, device=t.device)
+    full[:pack] = t
+    return full
+
+
+def _per_stream(op, n, *lists):
+    """op on lists of one, stream by stream (the fp32 form of the attention ops) -> its lists over all streams"""
+    res = [op(*[None if l is None else [l[i]] for l in lists]) for i in range(n)]
+    return tuple([r[k][0] for r in res] for k in range(len(res[0])))
+
+
 def attn_fwd_grouped(qkvs, kv_lens, ress, knorms, packs=None, qk_masks=None):
-    """attn_fwd for up to three streams in ONE launch: lists of qkv [B,N_i,768], kv_len, res, knorm (entries may be None)
-    -> lists (o, o_res, lse).  packs: per stream the row_starts() tensor of a packed stream, or None.
+    """attn_fwd of a list of streams: lists of qkv [B,N_i,768], kv_len, res, knorm (entries may be None) -> lists (o, o_res, lse).
+    packs: per stream the row_starts() tensor of a packed stream, or None.
     qk_masks: None, or per stream None / the words of its prefix mask (attn_fwd)."""
     _gpu(*qkvs)
     n, B = len(qkvs), qkvs[0].shape[0]
+    if n > 1 and qkvs[0].dtype != torch.bfloat16:
+        return _per_stream(attn_fwd_grouped, n, qkvs, kv_lens, ress, knorms, packs, qk_masks)
     es, dt, dev = qkvs[0].element_size(), qkvs[0].dtype, qkvs[0].device
     Ns = [q.shape[1] for q in qkvs]
     o = [torch.empty(B, N, D_MODEL, dtype=dt, device=dev) for N in Ns]
@@ -871,9 +911,11 @@ def attn_fwd_grouped(qkvs, kv_lens, ress, knorms, packs=None, qk_masks=None):
 
 
 def attn_bwd_grouped(qkvs, os_, d_os, lses, kv_lens, packs=None, qk_masks=None):
-    """attn_bwd for up to three streams in two launches (dQ, dK/dV) -> list of dqkv [B,N_i,768].  qk_masks: the forward's."""
+    """attn_bwd of a list of streams (bf16: two launches, dQ and dK/dV) -> list of dqkv [B,N_i,768].  qk_masks: the forward's."""
     _gpu(*qkvs)
     n, B = len(qkvs), qkvs[0].shape[0]
+    if n > 1 and qkvs[0].dtype != torch.bfloat16:
+        return _per_stream(lambda *a: (attn_bwd_grouped(*a),), n, qkvs, os_, d_os, lses, kv_lens, packs, qk_masks)[0]
     es = qkvs[0].element_size()
     Ns = [q.shape[1] for q in qkvs]
     dqkv = [torch.empty_like(q) for q in qkvs]
@@ -902,10 +944,13 @@ def _uints(vs):
 
 
 def ln_gemm_qkv_grouped(xs, gammas, betas, ws, biases, packs=None):
-    """ln_gemm_qkv of up to three streams in one launch (bf16): lists -> lists (qkv, xn, stats, knorm)."""
+    """ln_gemm_qkv of a list of streams: lists -> lists (qkv, xn, stats, knorm)."""
     _gpu(*xs)
     n, dt, dev = len(xs), xs[0].dtype, xs[0].device
-    Ms = [x.shape[0] for x in xs]
+    Ms, packs = [x.shape[0] for x in xs], _opt(packs, n)
+    if dt != torch.bfloat16:
+        y, xn, st, kn = zip(*[ln_gemm_qkv(_live_rows(xs[i], packs[i]), gammas[i], betas[i], ws[i], biases[i]) for i in range(n)])
+        return [[_padded(t, M, pk) for t, M, pk in zip(ts, Ms, packs)] for ts in (y, xn, st)] + [list(kn)]
     y = [torch.empty(M, 3 * D_MODEL, dtype=dt, device=dev) for M in Ms]
     xn = [torch.empty(M, D_MODEL, dtype=dt, device=dev) for M in Ms]
     st = [torch.empty(M, 2, dtype=torch.float32, device=dev) for M in Ms]
@@ -916,10 +961,14 @@ def ln_gemm_qkv_grouped(xs, gammas, betas, ws, biases, packs=None):
 
 
 def ln_gemm_signs_grouped(xs, gammas, betas, ws, biases, n_out, drop_p, seeds, packs=None):
-    """ln_gemm(relu, dropout, sign bits) of up to three streams in one launch (bf16): lists -> lists (y, xn, stats, signs)."""
+    """ln_gemm(relu, dropout, sign bits) of a list of streams: lists -> lists (y, xn, stats, signs); fp32 has no sign bits (None)."""
     _gpu(*xs)
     n, dt, dev = len(xs), xs[0].dtype, xs[0].device
-    Ms = [x.shape[0] for x in xs]
+    Ms, packs = [x.shape[0] for x in xs], _opt(packs, n)
+    if dt != torch.bfloat16:
+        y, xn, st, sg = zip(*[ln_gemm(_live_rows(xs[i], packs[i]), gammas[i], betas[i], ws[i], biases[i], n_out, relu=True,
+                                      drop_p=drop_p, seed=seeds[i], want_signs=True) for i in range(n)])
+        return [[_padded(t, M, pk) for t, M, pk in zip(ts, Ms, packs)] for ts in (y, xn, st)] + [list(sg)]
     y = [torch.empty(M, n_out, dtype=dt, device=dev) for M in Ms]
     xn = [torch.empty(M, D_MODEL, dtype=dt, device=dev) for M in Ms]
     st = [torch.empty(M, 2, dtype=torch.float32, device=dev) for M in Ms]
@@ -931,10 +980,13 @@ def ln_gemm_signs_grouped(xs, gammas, betas, ws, biases, n_out, drop_p, seeds, p
 
 
 def gemm_nt_grouped(as_, ws, biases, ress, drop_p, seeds, packs=None):
-    """gemm_nt (bias, dropout, residual) of up to three streams in one launch (bf16): lists -> list of y."""
+    """gemm_nt (bias, dropout, residual) of a list of streams: lists -> list of y."""
     _gpu(*as_)
     n, dt, dev = len(as_), as_[0].dtype, as_[0].device
-    Ms, K, N = [a.shape[0] for a in as_], as_[0].shape[1], ws[0].shape[0]
+    Ms, K, N, packs = [a.shape[0] for a in as_], as_[0].shape[1], ws[0].shape[0], _opt(packs, n)
+    if dt != torch.bfloat16:
+        return [_padded(gemm_nt(_live_rows(as_[i], packs[i]), ws[i], biases[i], res2d=_live_rows(ress[i], packs[i]), drop_p=drop_p,
+                                seed=seeds[i]), Ms[i], packs[i]) for i in range(n)]
     y = [torch.empty(M, N, dtype=dt, device=dev) for M in Ms]
     call("mtmp_gemm_nt_grouped", _dt(as_[0]), n, _ptrs(as_), _ptrs(ws), _ptrs(biases), _ptrs(ress), _ptrs(y), _ints(Ms), N, K,
          _ints([a.stride(0) for a in as_]), _ints([N] * n), _ints([0 if r is None else r.stride(0) for r in ress]), 0, float(drop_p),
@@ -942,12 +994,20 @@ def gemm_nt_grouped(as_, ws, biases, ress, drop_p, seeds, packs=None):
     return y
 
 
-def gemm_nt_signs_drop_grouped(as_, ws, signs, gate_scale, drop_p, seeds, packs=None):
-    """gemm_nt_signs (with the dropout backward of the operand folded in when drop_p > 0) of up to three streams in one
-    launch: lists -> (list of y, list of dropped operands | the operands themselves when drop_p == 0)."""
+def gemm_nt_signs_drop_grouped(as_, ws, signs, gate_scale, drop_p, seeds, packs=None, gates=None):
+    """The FFN backward's (dH, dY2) of a list of streams for as_ = the gradients of out = drop2(h w2^T + c2) + r1 on the rows the FFN
+    ran on: dY2 = dropout_bwd(a) (a itself when drop_p == 0), dH = dY2 W2 gated by h > 0 (which encodes ReLU and drop1's mask) in
+    the GEMM epilogue.  bf16: from the forward's sign bits (M N / 8 bytes of gate instead of re-reading h), and drop2's backward
+    rides on the operand load of the same launch; fp32: gates = h itself, behind a dropout_bwd launch."""
     _gpu(*as_)
     n, dt, dev = len(as_), as_[0].dtype, as_[0].device
-    Ms, N = [a.shape[0] for a in as_], ws[0].shape[0]
+    Ms, N, packs = [a.shape[0] for a in as_], ws[0].shape[0], _opt(packs, n)
+    if dt != torch.bfloat16:
+        ad = [_live_rows(a, pk) for a, pk in zip(as_, packs)]
+        if drop_p > 0:
+            ad = [dropout_bwd(a, sd, drop_p) for a, sd in zip(ad, seeds)]
+        y = [gemm_nt(ad[i], ws[i], gate=_live_rows(gates[i], packs[i]), gate_scale=gate_scale) for i in range(n)]
+        return [[_padded(t, M, pk) for t, M, pk in zip(ts, Ms, packs)] for ts in (y, ad)]
     y = [torch.empty(M, N, dtype=dt, device=dev) for M in Ms]
     ad = [torch.empty(M, a.shape[1], dtype=dt, device=dev) for M, a in zip(Ms, as_)] if drop_p > 0 else None
     call("mtmp_gemm_nt_signs_drop_grouped", _dt(as_[0]), n, _ptrs(as_), _ptrs(ws), _ptrs(y), _ints(Ms), N,
@@ -957,11 +1017,15 @@ def gemm_nt_signs_drop_grouped(as_, ws, signs, gate_scale, drop_p, seeds, packs=
 
 
 def gemm_lnbwd_grouped(dys, wts, zs, statss, gammas, d_ress, gb_outs, defers, packs=None):
-    """gemm_lnbwd of up to three streams in one launch, reductions deferred: lists -> list of (dz, dgamma, dbeta);
+    """gemm_lnbwd of a list of streams, reductions deferred: lists -> list of (dz, dgamma, dbeta);
     defers[i] receives stream i's reduction entry (reduce_batch)."""
     _gpu(*dys)
     n, dev = len(dys), dys[0].device
-    Ms, K = [d.shape[0] for d in dys], dys[0].shape[1]
+    Ms, K, packs = [d.shape[0] for d in dys], dys[0].shape[1], _opt(packs, n)
+    if zs[0].dtype != torch.bfloat16:
+        res = [gemm_lnbwd(_live_rows(dys[i], packs[i]), wts[i], _live_rows(zs[i], packs[i]), statss[i], gammas[i],
+                          d_res2d=_live_rows(d_ress[i], packs[i]), gb_out=gb_outs[i], defer=defers[i]) for i in range(n)]
+        return [(_padded(dz, M, pk), dg, db) for (dz, dg, db), M, pk in zip(res, Ms, packs)]
     dz = [torch.empty(M, D_MODEL, dtype=z.dtype, device=dev) for M, z in zip(Ms, zs)]
     gb = [g if g is not None else torch.empty(2 * D_MODEL, dtype=torch.float32, device=dev) for g in gb_outs]
     ws = [torch.empty(_lib.lib().mtmp_gemm_lnbwd_ws_floats(M), dtype=torch.float32, device=dev) for M in Ms]
@@ -974,14 +1038,15 @@ def gemm_lnbwd_grouped(dys, wts, zs, statss, gammas, d_ress, gb_outs, defers, pa
 
 
 def gemm_tn_grouped(dys, xs, outs, defers, packs=None):
-    """gemm_tn of up to three streams in one launch (LDS-DMA kernel), reductions deferred: lists -> list of (dw, db).
-    Falls back to one gemm_tn per stream when the shapes have no grouped form (short streams)."""
+    """gemm_tn of a list of streams, reductions deferred: lists -> list of (dw, db).  bf16: one launch of the LDS-DMA kernel, or
+    one gemm_tn per stream when the shapes have no grouped form (short streams); fp32: one gemm_tn per stream."""
     _gpu(*dys)
     n, dev = len(dys), dys[0].device
-    Ms, N, K = [d.shape[0] for d in dys], dys[0].shape[1], xs[0].shape[1]
+    Ms, N, K, packs = [d.shape[0] for d in dys], dys[0].shape[1], xs[0].shape[1], _opt(packs, n)
     splits = (ctypes.c_int * n)()
     if dys[0].dtype != torch.bfloat16 or _lib.lib().mtmp_gemm_tn_group_plan(n, _ints(Ms), N, K, splits) != 0:
-        return [gemm_tn(dys[i], xs[i], out=outs[i], defer=defers[i], pack=None if packs is None else packs[i]) for i in range(n)]
+        return [gemm_tn(_live_rows(dys[i], packs[i]), _live_rows(xs[i], packs[i]), out=outs[i], defer=defers[i],
+                        pack=None if isinstance(packs[i], int) else packs[i]) for i in range(n)]
     res, wss = [], []
     for i in range(n):
         if outs[i] is not None:
@@ -2011,48 +2076,64 @@ P_G1, P_B1, P_WQ, P_BQ, P_WK, P_BK, P_WV, P_BV, P_G2, P_B2, P_W1, P_C1, P_W2, P_
 # 7-sequence in this order.
 FusedWeights = namedtuple("FusedWeights", "wqkv bqkv w1 w2 w2t wqkvt w1t")
 
-# What one layer's forward keeps of one stream for its backward; opaque to callers, who hand it to the matching backward.
-#   o, r1     cls_layer_forward: of the CLS rows only ([B,256]); r1 with ffn_rows: the gathered B * R rows the FFN ran on
-#   pack      row_starts() of a PACKED stream;  ffn_rows: layer_forward_grouped(ffn_rows=R)
-#   cls_rows  cls_layer_forward: where the backward adds the CLS rows' residual gradient;  cls_tok: their row within a sample
+# What one layer's forward keeps of one stream for its backward; opaque to callers, who hand it to layer_backward.
+#   r1        the rows the FFN ran on, 2-D: all of them, with ffn_rows the gathered B * R, in the CLS mode the B CLS rows
+#   o         in the CLS mode of the CLS rows only ([B,256])
+#   pack      row_starts() of a PACKED stream;  ffn_rows: layer_forward(ffn_rows=R)
+#   cls_rows  CLS mode: where the backward adds the CLS rows' residual gradient;  cls_tok: their row within a sample
 #   qk_mask   the words of the stream's prefix mask (attn_fwd), or None
 LayerSaved = namedtuple("LayerSaved", "z kv_len g1 g2 wqkvt w1t w2t xn1 st1 qkv o lse r1 xn2 st2 h drop_p seeds hsign "
                                       "pack ffn_rows cls_rows cls_tok qk_mask", defaults=(None,) * 5)
 
 
-def _packed_full(rows2d, B, N):
-    """rows2d [live, C] -> a [B, N, C] buffer whose first `live` rows are rows2d (a PACKED stream buffer; the rest is never read)"""
-    full = torch.empty(B, N, rows2d.shape[1], dtype=rows2d.dtype, device=rows2d.device)
-    full.view(B * N, -1)[:rows2d.shape[0]] = rows2d
-    return full
-
-
-def layer_forward(z, kv_len, P, fused, drop_p, seeds, pack=None, qk_mask=None):
-    """z [B,N,256] contiguous.  P: the 14 parameters; fused: FusedWeights (or its seven tensors in that order).
-    Returns (out [B,N,256], LayerSaved).
-    pack (row_starts(kv_len, N)): z is a PACKED stream buffer (the samples' kv_len rows back to back) and so is `out`.  This
-    single-stream form (the fp32 parity build's) reads the row count on the HOST -- one sync, no hipGraph -- and runs the row
-    kernels on the live rows as dense [live, C] matrices; the attention kernels address the samples through pack exactly as the
-    bf16 grouped launches do (layer_forward_grouped takes the count from the device instead).
-    qk_mask: None or the words of a prefix mask over the stream's first rows and keys (attn_fwd)."""
-    B, N, D = z.shape
-    M = B * N
-    f = FusedWeights._make(fused)
-    live = M if pack is None else int(pack[B])
-    z2 = z.view(M, D)[:live]
-    qkv, xn1, st1, knorm = ln_gemm_qkv(z2, P[P_G1], P[P_B1], f.wqkv, f.bqkv)
-    if pack is None:
-        qkv = qkv.view(B, N, 3 * D)
-        o, r1, lse = attn_fwd(qkv, kv_len, res=z, knorm=knorm, qk_mask=qk_mask)
+def layer_forward(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ffn_rows=None, qk_masks=None, cls_tok=None):
+    """One encoder layer on a list of streams (one entry per stream everywhere): zs [B,N_i,256] contiguous, kv_lens int32[B] | None,
+    Ps the 14 parameters, fuseds FusedWeights (or its seven tensors in that order), seeds (FFN1, FFN2) -> (outs, LayerSaved records).
+    packs: per stream None or the row_starts() tensor of a PACKED stream (its [B, N, 256] buffers then hold the samples' valid
+    rows back to back, and so does its output: every kernel works on pack[B] rows instead of B * N).
+    ffn_rows = R: only rows 0..R-1 of every sample of the OUTPUT are read by anyone (the image / text streams in the last layer
+    they run in: the bottleneck exchange takes rows 0..3 and nothing else follows) -- the FFN half runs on those B * R rows, the
+    other output rows are zeros; the attention half stays dense (the R rows attend to all keys).  Padded streams only.
+    qk_masks: None, or per stream None / the words of its prefix mask (attn_fwd).
+    cls_tok = t: the last layer for a reader of row t of every sample only (one stream, padded or packed): the same idea with one
+    row and the attention of that one query (attn_cls_fwd); the output is out_cls [B,256]."""
+    n = len(zs)
+    packs, qk_masks = _opt(packs, n), _opt(qk_masks, n)
+    B, D, R = zs[0].shape[0], D_MODEL, ffn_rows
+    Ns = [z.shape[1] for z in zs]
+    if (R is not None and (cls_tok is not None or any(pk is not None for pk in packs) or any(N < R for N in Ns))) or \
+            (cls_tok is not None and n != 1):
+        raise ValueError("ffn_rows: padded streams of at least that many rows; cls_tok: one stream")
+    rows = _row_limits(zs, packs)
+    par = lambda k: [P[k] for P in Ps]
+    f = FusedWeights._make(zip(*fuseds))               # every field: the list over the streams
+    qkv, xn1, st1, knorm = ln_gemm_qkv_grouped([z.view(B * N, D) for z, N in zip(zs, Ns)], par(P_G1), par(P_B1), f.wqkv, f.bqkv, rows)
+    qkv = [q.view(B, N, 3 * D) for q, N in zip(qkv, Ns)]
+    # ---- attention, and r1 = z + o on the rows the FFN runs on
+    cls_rows = None
+    if cls_tok is not None:
+        o, r1, lse = ([t] for t in attn_cls_fwd(qkv[0], zs[0], kv_lens[0], packs[0], cls_tok))
+        rows = [None]
+        # the CLS rows of the stream buffer, for the backward's residual add: a packed stream's row starts AS THEY ARE (int32; the
+        # backward adds into the view that begins at row cls_tok -- `pack[:B].long() + cls_tok` was two launches in front of the head)
+        cls_rows = packs[0][:B] if packs[0] is not None else _cls_rows(B, Ns[0], cls_tok, zs[0].device)
     else:
-        qkv = _packed_full(qkv, B, N)
-        (o,), (r1,), (lse,) = attn_fwd_grouped([qkv], [kv_len], [z], [knorm], [pack], [qk_mask])
-    r1_2 = r1.view(M, D)[:live]
-    h, xn2, st2, hsign = ln_gemm(r1_2, P[P_G2], P[P_B2], f.w1, P[P_C1], 4 * D, relu=True, drop_p=drop_p, seed=seeds[0], want_signs=True)
-    out = gemm_nt(h, f.w2, P[P_C2], res2d=r1_2, drop_p=drop_p, seed=seeds[1])
-    saved = LayerSaved(z, kv_len, P[P_G1], P[P_G2], f.wqkvt, f.w1t, f.w2t, xn1, st1, qkv, o, lse, r1, xn2, st2, h, drop_p, seeds, hsign, pack,
-                       qk_mask=qk_mask)
-    return (out.view(B, N, D) if pack is None else _packed_full(out, B, N)), saved
+        o, r1, lse = attn_fwd_grouped(qkv, kv_lens, list(zs), knorm, packs, qk_masks)
+        r1 = [r.view(B * N, D) if R is None else r[:, :R].reshape(B * R, D) for r, N in zip(r1, Ns)]       # (R: a gathered copy)
+    # ---- FFN
+    h, xn2, st2, hsign = ln_gemm_signs_grouped(r1, par(P_G2), par(P_B2), f.w1, par(P_C1), 4 * D, drop_p, [sd[0] for sd in seeds], rows)
+    out = gemm_nt_grouped(h, f.w2, par(P_C2), r1, drop_p, [sd[1] for sd in seeds], rows)
+    if R is not None:
+        # zeros, not empty: when this layer closes a graph segment these buffers become segment boundaries / outputs of the autograd
+        # node; nobody reads the other rows today, and a later reader (a dump, a NaN check) must not meet recycled memory
+        full = [torch.zeros(B, N, D, dtype=zs[0].dtype, device=zs[0].device) for N in Ns]
+        for f_, o_ in zip(full, out):
+            f_[:, :R] = o_.view(B, R, D)
+        out = full
+    saved = [LayerSaved(zs[i], kv_lens[i], Ps[i][P_G1], Ps[i][P_G2], f.wqkvt[i], f.w1t[i], f.w2t[i], xn1[i], st1[i], qkv[i], o[i], lse[i],
+                        r1[i], xn2[i], st2[i], h[i], drop_p, seeds[i], hsign[i], packs[i], R, cls_rows, cls_tok, qk_masks[i])
+             for i in range(n)]
+    return (out if cls_tok is not None else [out[i].view(B, Ns[i], D) for i in range(n)]), saved
 
 
 class GradSink:
@@ -2082,7 +2163,7 @@ class GradSink:
         return self.ok and self.flat.claim(self.idx)
 
 
-# ---- the pieces shared by the three layer backwards
+# ---- where the layer backward's gradients go
 # Where a layer backward's five gradient launches write: slices of the flat gradient -- (dW, db) for gemm_tn, (dgamma | dbeta) for
 # gemm_lnbwd -- or None = a fresh tensor each.
 _GradDst = namedtuple("_GradDst", "w2 w1 gb2 wqkv gb1")
@@ -2096,75 +2177,10 @@ def _grad_dst(sink):
     return sink, _GradDst((sink.w2, sink.c2), (sink.w1, sink.c1), sink.gb2, (sink.wqkv, sink.bqkv), sink.gb1)
 
 
-def _ffn_bwd_head(sv, d_out):
-    """(dH, dY2) of out = drop2(h w2^T + c2) + r1 for d_out [rows,256], the rows the FFN ran on.
-    dH = dY2 W2, gated by h > 0 (which encodes ReLU and drop1's mask) in the GEMM epilogue: from the forward's sign bits
-    (bf16: M N / 8 bytes of gate instead of re-reading h) or, in the fp32 build, from h itself.  With the sign-bit kernel the
-    backward of drop2 (dY2 = dropout_bwd(d_out)) rides on its operand load: one launch and one read of d_out less."""
-    p, seeds, hsign = sv.drop_p, sv.seeds, sv.hsign
-    if hsign is not None and p > 0 and tuning.FOLD_DROPOUT_BWD:
-        return gemm_nt_signs(d_out, sv.w2t, hsign, 1.0 / (1.0 - p), drop_p=p, seed=seeds[1])
-    dy2 = dropout_bwd(d_out, seeds[1], p) if p > 0 else d_out
-    if hsign is not None:
-        return gemm_nt_signs(dy2, sv.w2t, hsign, 1.0 / (1.0 - p)), dy2
-    return gemm_nt(dy2, sv.w2t, gate=sv.h, gate_scale=1.0 / (1.0 - p)), dy2
-
-
 def _param_grads(dg1, db1, dwqkv, dbqkv, dg2, db2, dw1, dc1, dw2, dc2):
     """the 14 gradients in PARAMS order (fp32; weights as 2-D [out,in])"""
     D = D_MODEL
     return (dg1, db1, dwqkv[:D], dbqkv[:D], dwqkv[D:2 * D], dbqkv[D:2 * D], dwqkv[2 * D:], dbqkv[2 * D:], dg2, db2, dw1, dc1, dw2, dc2)
-
-
-def _finish_reductions(red, sinks, late):
-    """The end of a layer backward: `red`, its deferred reductions (None or empty: there are none), and `sinks`, those it wrote
-    through.  late: a list -- the caller issues the reduction launch (and marks the gradients ready) later on this stream, behind
-    the next bottleneck exchange, which needs dz but none of the parameter gradients (FusionStackFn.backward, _flush_late)."""
-    if late is not None and red:
-        late.append((red, sinks))
-        return
-    if red:
-        reduce_batch(red)
-    for sk in sinks:
-        sk.flat.mark_ready(sk.idx)
-
-
-def _flush_late(late):
-    for red, sinks in late:
-        reduce_batch(red)
-        for sk in sinks:
-            sk.flat.mark_ready(sk.idx)
-    del late[:]
-
-
-def layer_backward(saved, d_out, sink=None, late=None):
-    """d_out [B,N,256] contiguous, compute dtype.  Returns (dz [B,N,256], 14 parameter gradients (_param_grads)) -- or (dz, None)
-    when the gradients went straight into the flat gradient buffer through `sink`.  late: see _finish_reductions."""
-    sv = saved
-    B, N, D = sv.z.shape
-    M = B * N
-    pack = sv.pack                                       # (layer_forward's packed single-stream form: rows counted on the host)
-    live = M if pack is None else int(pack[B])
-    d_out = d_out.view(M, D)[:live]
-    sink, dst = _grad_dst(sink)
-    red = [] if tuning.DEFER_REDUCTIONS else None        # this layer's seven gradient reductions, issued as ONE launch at the end
-    # ---- FFN: out = drop2(h w2^T + c2) + r1,  h = drop1(relu(LN2(r1) w1^T + c1))
-    dh, dy2 = _ffn_bwd_head(sv, d_out)
-    dw2, dc2 = gemm_tn(dy2, sv.h, out=dst.w2, defer=red)       # [256,1024], [256]
-    dw1, dc1 = gemm_tn(dh, sv.xn2, out=dst.w1, defer=red)      # [1024,256], [1024]
-    # dXn2 = dH W1 and the backward of LN2 (+ the residual gradient) in one launch; the M x 256 product stays in LDS
-    dr1, dg2, db2 = gemm_lnbwd(dh, sv.w1t, sv.r1.view(M, D)[:live], sv.st2, sv.g2, d_res2d=d_out, gb_out=dst.gb2, defer=red)
-    # ---- attention: r1 = z + o  ->  d_o = dr1
-    if pack is None:
-        dqkv = attn_bwd(sv.qkv, sv.o, dr1.view(B, N, D), sv.lse, sv.kv_len, sv.qk_mask).view(M, 3 * D)
-    else:
-        dqkv = attn_bwd_grouped([sv.qkv], [sv.o], [_packed_full(dr1, B, N)], [sv.lse], [sv.kv_len], [pack],
-                                [sv.qk_mask])[0].view(M, 3 * D)[:live]
-    dwqkv, dbqkv = gemm_tn(dqkv, sv.xn1, out=dst.wqkv, defer=red)   # [768,256], [768]
-    dz, dg1, db1 = gemm_lnbwd(dqkv, sv.wqkvt, sv.z.view(M, D)[:live], sv.st1, sv.g1, d_res2d=dr1, gb_out=dst.gb1, defer=red)
-    _finish_reductions(red, [] if sink is None else [sink], late)
-    dz = dz.view(B, N, D) if pack is None else _packed_full(dz, B, N)
-    return dz, None if sink is not None else _param_grads(dg1, db1, dwqkv, dbqkv, dg2, db2, dw1, dc1, dw2, dc2)
 
 
 # ----------------------------------------------------------------------------- the last layer of a CLS-only reader
@@ -2210,136 +2226,58 @@ def _cls_rows(B, N, cls_tok, dev):
     return _cls_rows_cache[key]
 
 
-def cls_layer_forward(z, kv_len, P, fused, drop_p, seeds, pack, cls_tok):
-    """The last layer for a reader of the CLS row only: z [B,N,256] (padded, or packed with `pack`) -> (out_cls [B,256], LayerSaved)."""
-    B, N, D = z.shape
-    f = FusedWeights._make(fused)
-    z2 = z.view(B * N, D)
-    if pack is not None:                               # (bf16: the grouped form knows the live row count)
-        qkv, xn1, st1 = (t[0] for t in ln_gemm_qkv_grouped([z2], [P[P_G1]], [P[P_B1]], [f.wqkv], [f.bqkv], [pack])[:3])
-    else:
-        qkv, xn1, st1 = ln_gemm(z2, P[P_G1], P[P_B1], f.wqkv, f.bqkv, 3 * D)
-    qkv = qkv.view(B, N, 3 * D)
-    o_cls, r1, lse = attn_cls_fwd(qkv, z, kv_len, pack, cls_tok)
-    h, xn2, st2, hsign = ln_gemm(r1, P[P_G2], P[P_B2], f.w1, P[P_C1], 4 * D, relu=True, drop_p=drop_p, seed=seeds[0], want_signs=True)
-    out = gemm_nt(h, f.w2, P[P_C2], res2d=r1, drop_p=drop_p, seed=seeds[1])
-    # the CLS rows of the stream buffer, for the backward's residual add: a packed stream's row starts AS THEY ARE (int32; the
-    # backward adds into the view that begins at row cls_tok -- `pack[:B].long() + cls_tok` was two launches in front of the head)
-    rows = pack[:B] if pack is not None else _cls_rows(B, N, cls_tok, z.device)
-    return out, LayerSaved(z, kv_len, P[P_G1], P[P_G2], f.wqkvt, f.w1t, f.w2t, xn1, st1, qkv, o_cls, lse, r1, xn2, st2, h, drop_p, seeds,
-                           hsign, pack, cls_rows=rows, cls_tok=cls_tok)
-
-
-def cls_layer_backward(saved, d_cls, sink=None, late=None):
-    """d_cls [B,256] (gradient of cls_layer_forward's output) -> (dz [B,N,256], 14 parameter gradients | None), as layer_backward."""
-    sv = saved
-    B, N, D = sv.z.shape
-    M = B * N
-    pack, cls_tok = sv.pack, sv.cls_tok
-    d_out = _c(d_cls).to(sv.z.dtype)
-    sink, dst = _grad_dst(sink)
-    red = [] if tuning.DEFER_REDUCTIONS else None
-    # ---- FFN of the B CLS rows
-    dh, dy2 = _ffn_bwd_head(sv, d_out)
-    dw2, dc2 = gemm_tn(dy2, sv.h, out=dst.w2, defer=red)
-    dw1, dc1 = gemm_tn(dh, sv.xn2, out=dst.w1, defer=red)
-    dr1, dg2, db2 = gemm_lnbwd(dh, sv.w1t, sv.r1, sv.st2, sv.g2, d_res2d=d_out, gb_out=dst.gb2, defer=red)
-    # ---- attention of the CLS query: dense dK / dV (and a dQ that is zero outside the CLS rows), then the projection's backward
-    dqkv = attn_cls_bwd(sv.qkv, sv.o, dr1, sv.lse, sv.kv_len, pack, cls_tok).view(M, 3 * D)
-    z2 = sv.z.view(M, D)
-    if pack is not None:
-        dwqkv, dbqkv = gemm_tn_grouped([dqkv], [sv.xn1], [dst.wqkv], [red], [pack])[0]
-        dz, dg1, db1 = gemm_lnbwd_grouped([dqkv], [sv.wqkvt], [z2], [sv.st1], [sv.g1], [None], [dst.gb1], [red], [pack])[0]
-    else:
-        dwqkv, dbqkv = gemm_tn(dqkv, sv.xn1, out=dst.wqkv, defer=red)
-        dz, dg1, db1 = gemm_lnbwd(dqkv, sv.wqkvt, z2, sv.st1, sv.g1, d_res2d=None, gb_out=dst.gb1, defer=red)
-    # r1 = z + o: the CLS rows' residual gradient (packed: `cls_rows` are the samples' first rows, the CLS row lies cls_tok behind)
-    (dz[cls_tok:] if pack is not None else dz).index_add_(0, sv.cls_rows, dr1)
-    _finish_reductions(red, [] if sink is None else [sink], late)
-    return dz.view(B, N, D), None if sink is not None else _param_grads(dg1, db1, dwqkv, dbqkv, dg2, db2, dw1, dc1, dw2, dc2)
-
-
-# One launch per layer step over the active streams (bf16): csrc/common.hip.h, Grouped.  The three streams of a fusion layer are
-# 1005 / 54 / 133 tokens long; as three launches on three HIP streams the short ones held whole-CU workgroup slots beside the
-# long one's kernels (round 2: every vital-sign-stream kernel 15-40 % slower in the step than alone, ~1.2 ms per step, ~200
-# launches).  The parity (fp32) build keeps one launch per stream.  (switch: tuning.GROUPED_LAUNCHES)
-
-
-def grouped_ok(z) -> bool:
-    return tuning.GROUPED_LAUNCHES and z.dtype == torch.bfloat16
-
-
-def layer_forward_grouped(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ffn_rows=None, qk_masks=None):
-    """layer_forward for the active streams of one fusion layer with ONE launch per step (lists, one entry per stream).
-    packs: per stream None or the row_starts() tensor of a PACKED stream (its [B, N, 256] buffers then hold the samples' valid
-    rows back to back: every kernel below works on pack[B] rows instead of B * N).
-    ffn_rows = R: only rows 0..R-1 of every sample of the OUTPUT are read by anyone (the image / text streams in the last layer
-    they run in: the bottleneck exchange takes rows 0..3 and nothing else follows) -- the FFN half runs on those B * R rows, the
-    other output rows are left unwritten; the attention half stays dense (the R rows attend to all keys).  Padded streams only.
-    qk_masks: None, or per stream None / the words of its prefix mask (attn_fwd)."""
-    n = len(zs)
-    qk_masks = [None] * n if qk_masks is None else list(qk_masks)
-    B, D = zs[0].shape[0], D_MODEL
-    Ns = [z.shape[1] for z in zs]
-    packs = [None] * n if packs is None else list(packs)
-    par = lambda k: [P[k] for P in Ps]
-    f = FusedWeights._make(zip(*fuseds))               # every field: the list over the streams
-    z2 = [z.view(B * N, D) for z, N in zip(zs, Ns)]
-    qkv, xn1, st1, knorm = ln_gemm_qkv_grouped(z2, par(P_G1), par(P_B1), f.wqkv, f.bqkv, packs)
-    qkv = [q.view(B, N, 3 * D) for q, N in zip(qkv, Ns)]
-    o, r1, lse = attn_fwd_grouped(qkv, kv_lens, list(zs), knorm, packs, qk_masks)
-    R = ffn_rows
-    if R is not None:
-        if any(pk is not None for pk in packs) or any(N < R for N in Ns):
-            raise ValueError("ffn_rows: padded streams of at least that many rows")
-        r1_2 = [r[:, :R].reshape(B * R, D) for r in r1]            # the rows somebody reads, gathered (B * R x 256 each)
-    else:
-        r1_2 = [r.view(B * N, D) for r, N in zip(r1, Ns)]
-    h, xn2, st2, hsign = ln_gemm_signs_grouped(r1_2, par(P_G2), par(P_B2), f.w1, par(P_C1), 4 * D, drop_p, [sd[0] for sd in seeds], packs)
-    out = gemm_nt_grouped(h, f.w2, par(P_C2), r1_2, drop_p, [sd[1] for sd in seeds], packs)
-    if R is not None:
-        # zeros, not empty: when this layer closes a graph segment these buffers become segment boundaries / outputs of the autograd
-        # node; nobody reads the other rows today, and a later reader (a dump, a NaN check) must not meet recycled memory
-        full = [torch.zeros(B, N, D, dtype=zs[0].dtype, device=zs[0].device) for N in Ns]
-        for f_, o_ in zip(full, out):
-            f_[:, :R] = o_.view(B, R, D)
-        out = full
-    saved = [LayerSaved(zs[i], kv_lens[i], Ps[i][P_G1], Ps[i][P_G2], f.wqkvt[i], f.w1t[i], f.w2t[i], xn1[i], st1[i], qkv[i], o[i], lse[i],
-                        r1_2[i] if R is not None else r1[i], xn2[i], st2[i], h[i], drop_p, seeds[i], hsign[i], packs[i], R,
-                        qk_mask=qk_masks[i]) for i in range(n)]
-    return [out[i].view(B, Ns[i], D) for i in range(n)], saved
-
-
-def layer_backward_grouped(saveds, d_outs, sinks, late):
-    """layer_backward for the active streams of one fusion layer, one launch per step.  Returns (list of dz, list of
-    per-stream gradient tuples | None) like layer_backward; the reductions of ALL streams go into `late` as one entry."""
+def layer_backward(saveds, d_outs, sinks=None):
+    """The backward of layer_forward: its saved records and the gradients of its outputs (contiguous, compute dtype; CLS mode:
+    d_cls [B,256]) -> (list of dz [B,N_i,256], per stream the 14 parameter gradients (_param_grads) -- or None where they went
+    straight into the flat gradient buffer through that stream's sink).  The gradient reductions of ALL streams are one launch
+    (mtmp_reduce_batch, eight slabs each) at the end, instead of seven launches of 5-13 us per stream."""
     n = len(d_outs)
     sv = LayerSaved._make(zip(*saveds))                # every field: the tuple over the streams
     B, D = sv.z[0].shape[0], D_MODEL
     Ns = [z.shape[1] for z in sv.z]
     Ms = [B * N for N in Ns]
-    p, R, packs = sv.drop_p[0], sv.ffn_rows[0], list(sv.pack)
-    d_out = [d.view(M, D) for d, M in zip(d_outs, Ms)]
-    sinks, dst = zip(*[_grad_dst(sk) for sk in sinks])
+    p, R, cls_tok, packs = sv.drop_p[0], sv.ffn_rows[0], sv.cls_tok[0], list(sv.pack)
+    rows = _row_limits(sv.z, packs)
+    frows = rows if cls_tok is None else [None] * n    # the FFN half's: the CLS mode ran it on B dense rows
+    sinks, dst = zip(*[_grad_dst(sk) for sk in _opt(sinks, n)])
     reds = [[] for _ in range(n)]
-    if R is not None:                     # the FFN half ran on rows 0..R-1 of every sample: so does its backward
-        d_out = [d.view(B, N, D)[:, :R].reshape(B * R, D) for d, N in zip(d_out, Ns)]
-    dh, dy2 = gemm_nt_signs_drop_grouped(d_out, sv.w2t, sv.hsign, 1.0 / (1.0 - p), p, [sd[1] for sd in sv.seeds], packs)
-    gw2 = gemm_tn_grouped(dy2, sv.h, [d.w2 for d in dst], reds, packs)
-    gw1 = gemm_tn_grouped(dh, sv.xn2, [d.w1 for d in dst], reds, packs)
-    r1_2 = [r.view(-1, D) for r in sv.r1]
-    l2 = gemm_lnbwd_grouped(dh, sv.w1t, r1_2, sv.st2, sv.g2, d_out, [d.gb2 for d in dst], reds, packs)
+    # ---- FFN: out = drop2(h w2^T + c2) + r1,  h = drop1(relu(LN2(r1) w1^T + c1)), on the rows it ran on
+    if cls_tok is not None:
+        d_out = [_c(d).to(z.dtype) for d, z in zip(d_outs, sv.z)]
+    elif R is not None:
+        d_out = [d[:, :R].reshape(B * R, D) for d in d_outs]
+    else:
+        d_out = [d.view(M, D) for d, M in zip(d_outs, Ms)]
+    dh, dy2 = gemm_nt_signs_drop_grouped(d_out, sv.w2t, sv.hsign, 1.0 / (1.0 - p), p, [sd[1] for sd in sv.seeds], frows, gates=sv.h)
+    gw2 = gemm_tn_grouped(dy2, sv.h, [d.w2 for d in dst], reds, frows)         # [256,1024], [256]
+    gw1 = gemm_tn_grouped(dh, sv.xn2, [d.w1 for d in dst], reds, frows)        # [1024,256], [1024]
+    # dXn2 = dH W1 and the backward of LN2 (+ the residual gradient) in one launch; the M x 256 product stays in LDS
+    l2 = gemm_lnbwd_grouped(dh, sv.w1t, sv.r1, sv.st2, sv.g2, d_out, [d.gb2 for d in dst], reds, frows)
     dr1 = [t[0] for t in l2]
-    if R is not None:                     # r1's gradient is zero outside those rows (nothing read the other output rows)
-        dense = [torch.zeros(B, N, D, dtype=d.dtype, device=d.device) for d, N in zip(dr1, Ns)]
-        for f_, d in zip(dense, dr1):
-            f_[:, :R] = d.view(B, R, D)
-        dr1 = [f_.view(-1, D) for f_ in dense]
-    dqkv = attn_bwd_grouped(sv.qkv, sv.o, [d.view(B, N, D) for d, N in zip(dr1, Ns)], sv.lse, sv.kv_len, packs, list(sv.qk_mask))
+    # ---- attention: r1 = z + o  ->  d_o = dr1
+    if cls_tok is not None:
+        # of the CLS query: dense dK / dV and a dQ that is zero outside the CLS rows; their residual gradient is added below
+        dqkv = [attn_cls_bwd(sv.qkv[0], sv.o[0], dr1[0], sv.lse[0], sv.kv_len[0], packs[0], cls_tok)]
+        d_res = [None]
+    else:
+        if R is not None:                 # r1's gradient is zero outside those rows (nothing read the other output rows)
+            dense = [torch.zeros(B, N, D, dtype=d.dtype, device=d.device) for d, N in zip(dr1, Ns)]
+            for f_, d in zip(dense, dr1):
+                f_[:, :R] = d.view(B, R, D)
+            dr1 = [f_.view(-1, D) for f_ in dense]
+        dqkv = attn_bwd_grouped(sv.qkv, sv.o, [d.view(B, N, D) for d, N in zip(dr1, Ns)], sv.lse, sv.kv_len, packs, list(sv.qk_mask))
+        d_res = dr1
+    # ---- the Q/K/V projection
     dqkv = [d.view(M, 3 * D) for d, M in zip(dqkv, Ms)]
-    gwq = gemm_tn_grouped(dqkv, sv.xn1, [d.wqkv for d in dst], reds, packs)
-    l1 = gemm_lnbwd_grouped(dqkv, sv.wqkvt, [t.view(M, D) for t, M in zip(sv.z, Ms)], sv.st1, sv.g1, dr1, [d.gb1 for d in dst], reds, packs)
-    _finish_reductions([e for r_ in reds for e in r_], [sk for sk in sinks if sk is not None], late)
+    gwq = gemm_tn_grouped(dqkv, sv.xn1, [d.wqkv for d in dst], reds, rows)     # [768,256], [768]
+    l1 = gemm_lnbwd_grouped(dqkv, sv.wqkvt, [t.view(M, D) for t, M in zip(sv.z, Ms)], sv.st1, sv.g1, d_res, [d.gb1 for d in dst], reds, rows)
+    if cls_tok is not None:
+        # r1 = z + o on the CLS rows (packed: `cls_rows` are the samples' first rows, the CLS row lies cls_tok behind)
+        (l1[0][0][cls_tok:] if packs[0] is not None else l1[0][0]).index_add_(0, sv.cls_rows[0], dr1[0])
+    reduce_batch([e for r_ in reds for e in r_])
+    for sk in sinks:
+        if sk is not None:
+            sk.flat.mark_ready(sk.idx)
     grads = [None if sinks[i] is not None else _param_grads(*l1[i][1:], *gwq[i], *l2[i][1:], *gw1[i], *gw2[i]) for i in range(n)]
     return [l1[i][0].view(B, Ns[i], D) for i in range(n)], grads
 
@@ -2352,19 +2290,14 @@ class EncoderLayerFn(torch.autograd.Function):
     def forward(ctx, z, kv_len, *rest):
         _gpu(z)
         P, (fused, drop_p, seeds, *opt) = rest[:PARAMS_PER_LAYER], rest[PARAMS_PER_LAYER:]
-        out, saved = layer_forward(_c(z), kv_len, P, fused, drop_p, seeds, qk_mask=opt[0] if opt else None)
-        ctx.saved = saved
+        (out,), ctx.saved = layer_forward([_c(z)], [kv_len], [P], [fused], drop_p, [seeds], qk_masks=[opt[0] if opt else None])
         ctx.n_opt = len(opt)
         ctx.wshapes = (P[P_W1].shape, P[P_W2].shape)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        z = ctx.saved.z
-        d_out = _c(d_out)
-        if d_out.dtype != z.dtype:
-            d_out = d_out.to(z.dtype)
-        dz, g = layer_backward(ctx.saved, d_out)
+        (dz,), (g,) = layer_backward(ctx.saved, [_c(d_out).to(ctx.saved[0].z.dtype)])
         g = list(g)
         g[P_W1], g[P_W2] = g[P_W1].view(ctx.wshapes[0]), g[P_W2].view(ctx.wshapes[1])
         return (dz, None, *g, None, None, None) + (None,) * ctx.n_opt
@@ -2393,7 +2326,7 @@ def _exchange_w(dev):
 
 def launch_groups(ms, streams, z, solo=False):
     """[(stream indices, HIP side stream | None)] for the active streams `ms` of one layer."""
-    mode = "none" if (solo or not grouped_ok(z)) else tuning.GROUP_MODE
+    mode = "none" if (solo or z.dtype != torch.bfloat16) else tuning.GROUP_MODE
     if len(ms) == 1 or streams is None and mode != "all":
         return [([m], None) for m in ms] if mode != "all" else [(list(ms), None)]
     if mode == "all":
@@ -2401,16 +2334,6 @@ def launch_groups(ms, streams, z, solo=False):
     if mode == "small":
         return [([ms[0]], None), (list(ms[1:]), streams[0])]
     return [([m], None if m == ms[0] else streams[(m - 1) % len(streams)]) for m in ms]
-
-
-def stream_of_group(m, streams, z):
-    """the HIP side stream on which the group led by stream m runs its backward (None = the caller's stream)"""
-    if m == 0 or streams is None:
-        return None
-    mode = tuning.GROUP_MODE if grouped_ok(z) else "none"
-    if mode == "all":
-        return None
-    return streams[0] if mode == "small" else streams[(m - 1) % len(streams)]
 
 
 def _each_group(groups, cur):
@@ -2438,23 +2361,6 @@ def _stack_params(params, cfg, li, m):
 
 def _stack_sink(cfg, li, m):
     return cfg["sinks"][li][m] if cfg.get("sinks") else None
-
-
-def _group_forward(z, params, cfg, li, gms, pack_v, ffn_rows):
-    """one launch group of layer li: grouped launches (bf16) or the single-stream form per stream -> (outs, saved records)"""
-    Ps = [_stack_params(params, cfg, li, m) for m in gms]
-    if grouped_ok(z[0]):
-        return layer_forward_grouped([z[m] for m in gms], [cfg["kv"][m] for m in gms], Ps, [cfg["fused"][li][m] for m in gms],
-                                     cfg["drop_p"], [cfg["seeds"][li][m] for m in gms], [pack_v if m == 0 else None for m in gms],
-                                     ffn_rows=ffn_rows)
-    return zip(*[layer_forward(z[m], cfg["kv"][m], P, cfg["fused"][li][m], cfg["drop_p"], cfg["seeds"][li][m]) for m, P in zip(gms, Ps)])
-
-
-def _group_backward(saveds, dzs, sinks, late):
-    """its backward -> (dz per stream, gradient tuple | None per stream)"""
-    if grouped_ok(saveds[0].z):
-        return layer_backward_grouped(saveds, dzs, sinks, late)
-    return zip(*[layer_backward(sv, d, sk, late=late) for sv, d, sk in zip(saveds, dzs, sinks)])
 
 
 class FusionStackFn(torch.autograd.Function):
@@ -2515,7 +2421,7 @@ class FusionStackFn(torch.autograd.Function):
         # the vital-sign stream PACKED (cfg["pack_v"] = row_starts(kv[0], Ns[0]), made by the encoder together with a packed
         # stream input): bf16 grouped kernels only, and only for a caller that reads nothing of stream 0 but its CLS row
         pack_v = cfg.get("pack_v")
-        if pack_v is not None and not (cfg.get("prebuilt") and grouped_ok(z[0]) and cfg["kv"][0] is not None):
+        if pack_v is not None and not (cfg.get("prebuilt") and z[0].dtype == torch.bfloat16 and cfg["kv"][0] is not None):
             raise ValueError("a packed vital-sign stream needs prebuilt bf16 inputs with key lengths (ops.StreamInputFn)")
         prev_bott = bott.expand(B, -1, -1).float().contiguous() if cfg["resbottle"] else None
         for li in range(L):
@@ -2524,28 +2430,28 @@ class FusionStackFn(torch.autograd.Function):
             outs = [None, None, None]
             row = [None, None, None]
             # the layer in front of a last layer that runs stream 0 alone, read by a CLS-only reader (the encoder names it, by its
-            # index in this segment): the image / text outputs of THIS layer feed the bottleneck exchange (rows 0..3) and nothing else
-            exchange_only = li == cfg.get("exchange_only_layer", -1) and tuning.FFN_ROWS_BEFORE_LAST
-            if last and cfg.get("cls_only"):       # the reader takes the CLS row only: ops.cls_layer_forward
-                mark(f"f{li}.g0.s")
-                cls_out, row[0] = cls_layer_forward(z[0], cfg["kv"][0], _stack_params(params, cfg, li, 0), cfg["fused"][li][0],
-                                                    cfg["drop_p"], cfg["seeds"][li][0], pack_v, NB)
-                mark(f"f{li}.g0.e")
-                saved.append(row)
-                active.append(ms)
-                z = [None, None, None]
-                break
+            # index in this segment): the image / text outputs of THIS layer feed the bottleneck exchange (rows 0..3) and nothing
+            # else, so their FFN runs on those rows (bf16; the fp32 parity build keeps the dense FFN)
+            exchange_only = (li == cfg.get("exchange_only_layer", -1) and tuning.FFN_ROWS_BEFORE_LAST
+                             and z[0].dtype == torch.bfloat16)
+            cls_tok = NB if (last and cfg.get("cls_only")) else None       # the reader takes the CLS row only
             # launch groups of this layer: (streams, HIP stream).  Layer 0 keeps one group per stream while the image / text
             # inputs are still being made on the side streams (the vital-sign stream's first layer runs beside the image encoder)
             groups = launch_groups(ms, streams, z[0], solo=(li == 0 and bool(cfg.get("inputs_on_side"))))
             for gms in _each_group(groups, cur):
                 mark(f"f{li}.g{gms[0]}.s")
-                go, gsaved = _group_forward(z, params, cfg, li, gms, pack_v, NB if (exchange_only and 0 not in gms) else None)
+                go, gsaved = layer_forward([z[m] for m in gms], [cfg["kv"][m] for m in gms], [_stack_params(params, cfg, li, m) for m in gms],
+                                           [cfg["fused"][li][m] for m in gms], cfg["drop_p"], [cfg["seeds"][li][m] for m in gms],
+                                           [pack_v if m == 0 else None for m in gms],
+                                           ffn_rows=NB if (exchange_only and 0 not in gms) else None, cls_tok=cls_tok)
                 for i, m in enumerate(gms):
                     outs[m], row[m] = go[i], gsaved[i]
                 mark(f"f{li}.g{gms[0]}.e")
             saved.append(row)
             active.append(ms)
+            if cls_tok is not None:
+                cls_out, z = outs[0], [None, None, None]
+                break
             if last:
                 z = outs
                 break
@@ -2601,18 +2507,14 @@ class FusionStackFn(torch.autograd.Function):
             if m in active[-1] and not ctx.cls_only:
                 dz[m] = torch.zeros(B, Ns[m], D_MODEL, dtype=dt, device=dev) if g is None else _c(g).to(dt).clone()
         pack_v = cfg.get("pack_v")
-        if ctx.cls_only:
-            pass                           # d_cls goes straight into ops.cls_layer_backward below
+        if ctx.cls_only:                   # the last layer's only output is the CLS row
+            dz[0] = d_cls if d_cls is not None else torch.zeros(B, D_MODEL, dtype=dt, device=dev)
         elif d_cls is not None and pack_v is not None:
             dz[0].view(-1, D_MODEL).index_add_(0, ctx.cls_rows, d_cls.to(dt))
         elif d_cls is not None:
             dz[0][:, NB, :] += d_cls.to(dt)
         pgrads = [None] * len(pshapes)
         d_prev_bott = None           # gradient flowing into the previous exchange's output through resbottle
-        # With tuning.LATE_REDUCTIONS a layer's gradient reductions (one mtmp_reduce_batch launch per stream) are issued one layer LATE, on the same stream:
-        # the bottleneck exchange in between needs the streams' dz but none of their parameter gradients, and it is the image /
-        # text streams' last launches that the vital-sign stream waits for there.
-        late = [[], [], []]          # keyed by the first stream of the launch group that produced them
 
         def keep_grads(li, m, g):
             """a layer's returned gradients (None: they went through its sink) into their places of this node's result"""
@@ -2639,34 +2541,18 @@ class FusionStackFn(torch.autograd.Function):
                 bottleneck_exchange_bwd(dz, cfg["missing"], cfg["resbottle"], d_prev_bott, d_out_prev, pack_v)
                 d_prev_bott = d_out_prev
             nxt = [None, None, None]
-            if ctx.cls_only and li == n_run - 1:
-                mark(f"b{li}.g0.s")
-                d1 = d_cls if d_cls is not None else torch.zeros(B, D_MODEL, dtype=dt, device=dev)
-                nxt[0], gg0 = cls_layer_backward(saved[li][0], d1, _stack_sink(cfg, li, 0), late=late[0] if tuning.LATE_REDUCTIONS else None)
-                keep_grads(li, 0, gg0)
-                mark(f"b{li}.g0.e")
-            else:
-                for gms in _each_group(launch_groups(ms, streams, saved[li][ms[0]].z), cur):
-                    mark(f"b{li}.g{gms[0]}.s")
-                    _flush_late(late[gms[0]])           # the layer above's reductions of this group: behind this layer's exchange
-                    gdz, gg = _group_backward([saved[li][m] for m in gms], [dz[m] for m in gms], [_stack_sink(cfg, li, m) for m in gms],
-                                              late[gms[0]] if tuning.LATE_REDUCTIONS else None)
-                    for i, m in enumerate(gms):
-                        nxt[m] = gdz[i]
-                        keep_grads(li, m, gg[i])
-                    mark(f"b{li}.g{gms[0]}.e")
+            for gms in _each_group(launch_groups(ms, streams, saved[li][ms[0]].z), cur):
+                mark(f"b{li}.g{gms[0]}.s")
+                gdz, gg = layer_backward([saved[li][m] for m in gms], [dz[m] for m in gms], [_stack_sink(cfg, li, m) for m in gms])
+                for i, m in enumerate(gms):
+                    nxt[m] = gdz[i]
+                    keep_grads(li, m, gg[i])
+                mark(f"b{li}.g{gms[0]}.e")
             saved[li] = None
             # streams skipped by the vslt-only last layer re-enter here with zero gradient
             if len(ms) == 1 and li > 0:
                 zero_other_streams(nxt)
             dz = nxt
-        for m in range(3):                  # the first layer's reductions, on the stream their group ran on
-            if late[m]:
-                gs = stream_of_group(m, streams, next(t for t in dz if t is not None))
-                with (torch.cuda.stream(gs) if gs is not None else contextlib.nullcontext()):
-                    _flush_late(late[m])
-                if gs is not None:
-                    cur.wait_stream(gs)
         if cfg.get("prebuilt"):            # the bottleneck rows' gradient flows on through the stream-input nodes
             d_bott = None if d_prev_bott is None else d_prev_bott.sum(0, keepdim=True)
             return (dz[0], dz[1], dz[2], d_bott, *pgrads, None)
@@ -2743,8 +2629,8 @@ class BottleneckExchangeMultiFn(torch.autograd.Function):
 
 
 class MultiTokenStackFn(torch.autograd.Function):
-    """All fusion layers of the multi-token encoder as one autograd node on the layer engine (layer_forward[_grouped] /
-    layer_backward[_grouped]): apply(z_v, z_i, z_t, *layer_params, cfg) -> (out_v, out_i, out_t), every buffer [B, 12 + N_m, 256]
+    """All fusion layers of the multi-token encoder as one autograd node on the layer engine (layer_forward /
+    layer_backward): apply(z_v, z_i, z_t, *layer_params, cfg) -> (out_v, out_i, out_t), every buffer [B, 12 + N_m, 256]
     = [prefix | tokens] in the compute dtype.  A layer writes new buffers, the exchange overwrites their prefix rows in place and
     they are the next layer's inputs.  cfg: n_layers, kv (int32[B] | None per stream, prefix included), masks (words | None per
     stream), missing (int64[B]), drop_p, seeds[l][m], fused[l][m] (None for a block that is not run), first_only (the caller reads
@@ -2760,13 +2646,9 @@ class MultiTokenStackFn(torch.autograd.Function):
         for li in range(L):
             ms = [0] if (cfg.get("first_only") and li == L - 1) else [0, 1, 2]
             Ps = [params[(li * 3 + m) * PARAMS_PER_LAYER:(li * 3 + m + 1) * PARAMS_PER_LAYER] for m in ms]
-            if grouped_ok(z[0]):
-                outs, sv = layer_forward_grouped([z[m] for m in ms], [cfg["kv"][m] for m in ms], Ps, [cfg["fused"][li][m] for m in ms],
-                                                 cfg["drop_p"], [cfg["seeds"][li][m] for m in ms], qk_masks=[cfg["masks"][m] for m in ms])
-            else:
-                outs, sv = zip(*[layer_forward(z[m], cfg["kv"][m], P, cfg["fused"][li][m], cfg["drop_p"], cfg["seeds"][li][m],
-                                               qk_mask=cfg["masks"][m]) for m, P in zip(ms, Ps)])
-            saved.append(list(sv))
+            outs, sv = layer_forward([z[m] for m in ms], [cfg["kv"][m] for m in ms], Ps, [cfg["fused"][li][m] for m in ms],
+                                     cfg["drop_p"], [cfg["seeds"][li][m] for m in ms], qk_masks=[cfg["masks"][m] for m in ms])
+            saved.append(sv)
             active.append(ms)
             z = [outs[ms.index(m)] if m in ms else None for m in range(3)]
             if li < L - 1:                 # (the reference exchanges after the last layer too; nothing reads that result)
@@ -2791,11 +2673,7 @@ class MultiTokenStackFn(torch.autograd.Function):
             ms = active[li]
             if li < len(active) - 1:       # this layer's outputs went through an exchange
                 bottleneck_exchange_multi(dz, cfg["missing"], backward=True)
-            sv, dzs = [saved[li][ms.index(m)] for m in ms], [dz[m] for m in ms]
-            if grouped_ok(sv[0].z):
-                gdz, gg = layer_backward_grouped(sv, dzs, [None] * len(ms), None)
-            else:
-                gdz, gg = zip(*[layer_backward(s_, d) for s_, d in zip(sv, dzs)])
+            gdz, gg = layer_backward(saved[li], [dz[m] for m in ms])
             saved[li] = None
             dz = [None, None, None]
             for i, m in enumerate(ms):

@@ -137,7 +137,7 @@ def test_ops_take_the_mask_and_default_to_none():
     import inspect
     from medical_tri_modal_pilot_amd import ops
     for fn, arg in ((ops.attn_fwd, "qk_mask"), (ops.attn_bwd, "qk_mask"), (ops.attn_fwd_grouped, "qk_masks"),
-                    (ops.attn_bwd_grouped, "qk_masks"), (ops.layer_forward, "qk_mask"), (ops.layer_forward_grouped, "qk_masks")):
+                    (ops.attn_bwd_grouped, "qk_masks"), (ops.layer_forward, "qk_masks")):
         assert inspect.signature(fn).parameters[arg].default is None, fn.__name__
     assert "qk_mask" in ops.LayerSaved._fields and ops.LayerSaved._field_defaults["qk_mask"] is None
     assert ops._mask_words(None) == (None, 0)

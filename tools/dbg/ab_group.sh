@@ -5,5 +5,4 @@ for r in $(seq 1 ${1:-2}); do
   for m in none small all; do
     echo -n "GROUP_MODE=$m   "; python tools/dbg/ab_patch.py "$O.GROUP_MODE='$m'" -- $A 2>/dev/null | tail -1 || exit 1
   done
-  echo -n "per-stream kernels (GROUPED_LAUNCHES=False)   "; python tools/dbg/ab_patch.py "$O.GROUPED_LAUNCHES=False" -- $A 2>/dev/null | tail -1 || exit 1
 done

@@ -37,9 +37,9 @@ for B, T, L in cases:
                 kw.update(over)
             return orig(L_, multi, dtype, **kw)
         TG._product_model = patched
-        tuning.GROUPED_LAUNCHES = False
+        tuning.GROUP_MODE = "none"
         lb2, gb2, _ = TG._one_train_step("bf16", B, T, L, batch=bt)
-        print(f"   padded rows, all images encoded, one launch per stream: loss diff {abs(lb2 - lf):.2e} | {stats(gb2, gf)}")
+        print(f"   padded rows, all images encoded, one launch group per stream: loss diff {abs(lb2 - lf):.2e} | {stats(gb2, gf)}")
         print(f"   that variant against the default bf16 path: {stats(gb2, gb)}")
         TG._product_model = orig
-        tuning.GROUPED_LAUNCHES = True
+        tuning.GROUP_MODE = "small"
