@@ -15,6 +15,7 @@ import torch
 
 from . import _lib, tuning
 from ._lib import BF16, F32, call
+from .stack_plan import NB, N_PREFIX, PARAMS_PER_LAYER, StackPlan, keep_grads, zero_streams  # noqa: F401  (ops.NB, ops.N_PREFIX stay)
 
 LN_EPS = 1e-6          # builder/models/src/transformer/module.py:132
 N_HEAD, D_MODEL, D_HEAD = 4, 256, 64
@@ -1891,7 +1892,7 @@ class StreamInputFn(torch.autograd.Function):
     """mbt_encoder.py:697-729 + the [bottleneck | CLS | tokens] concatenation of :745 as one launch each way.
     apply(x [B,N,256] compute dtype, cls [1,1,256], ln_w, ln_b, pe [L,256] | None, bott [1,nb,256] | None, eps, p, seed
           [, pack, kv_len])
-    -> z [B, nb+1+N, 256] (the buffer ops.FusionStackFn reads in place, cfg["prebuilt"]).  pack (row_starts(kv_len, nb+1+N))
+    -> z [B, nb+1+N, 256] (the buffer ops.FusionStackFn reads in place, StackPlan.prebuilt).  pack (row_starts(kv_len, nb+1+N))
     with kv_len: the output is PACKED -- sample b's first kv_len[b] rows at rows pack[b].. of the same allocation."""
 
     @staticmethod
@@ -2067,7 +2068,6 @@ class StreamInputsFn(torch.autograd.Function):
 # remaining dX products fused with the backward of the LayerNorm in front of them (mtmp_gemm_lnbwd).
 # No library GEMM is left on the path.  Activations needed by the backward
 # are kept (HBM is 288 GB; one vslt layer at B=64, T=1000 keeps ~0.4 GB in bf16).
-PARAMS_PER_LAYER = 14
 P_G1, P_B1, P_WQ, P_BQ, P_WK, P_BK, P_WV, P_BV, P_G2, P_B2, P_W1, P_C1, P_W2, P_C2 = range(PARAMS_PER_LAYER)   # their order
 
 
@@ -2304,19 +2304,7 @@ class EncoderLayerFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------- fusion stack engine
-_EXCHANGE_W = torch.tensor([[1 / 3, 1 / 3, 1 / 3], [0.5, 0.5, 0.0], [0.5, 0.0, 0.5], [1.0, 0.0, 0.0]])
-NB = 4   # bottleneck tokens
-_exchange_w_dev = {}
-
-
-def _exchange_w(dev):
-    """Device copy of the exchange table, made once (a pageable H2D copy cannot be captured in a hipGraph)."""
-    k = (dev.type, dev.index)
-    if k not in _exchange_w_dev:
-        _exchange_w_dev[k] = _EXCHANGE_W.to(dev)
-    return _exchange_w_dev[k]
-
-
+# What a node runs is decided in stack_plan.py: StackPlan (the nodes' last argument) and its schedule(), one LayerStep per layer.
 # How a layer's streams are cut into launches (bf16 build; the fp32 build launches per stream whatever the mode):
 #   "all"   -- one launch per step over all active streams, on the caller's stream
 #   "small" -- the vital-sign stream alone on the caller's stream, image + text together on side stream 0
@@ -2353,16 +2341,6 @@ def _each_group(groups, cur):
                 cur.wait_stream(gs)
 
 
-def _stack_params(params, cfg, li, m):
-    """the 14 parameters of layer li, stream m, out of FusionStackFn's flat argument list"""
-    k = (li * cfg.get("n_streams", 3) + m) * PARAMS_PER_LAYER
-    return params[k:k + PARAMS_PER_LAYER]
-
-
-def _stack_sink(cfg, li, m):
-    return cfg["sinks"][li][m] if cfg.get("sinks") else None
-
-
 class FusionStackFn(torch.autograd.Function):
     """All fusion layers of TrimodalTransformerEncoder_MBT (mbt_encoder.py:731-779) as ONE autograd
     node with explicit buffers.  Every stream lives in a [B, 4+N, 256] buffer whose first four rows
@@ -2372,36 +2350,17 @@ class FusionStackFn(torch.autograd.Function):
     of a layer are issued on separate HIP streams (the 54- and 133-token streams cannot fill 256 CUs
     on their own).  The backward replays the stack in reverse with the hand-written layer backward.
 
-    apply(xv, xi, xt, bottlenecks, *layer_params, cfg) -> (out_v, out_i, out_t, cls_v); cfg is a dict:
-      n_layers, vsltonly, resbottle, kv (list of int32[B] | None per stream, bottleneck prefix
-      included), missing (int64[B]), drop_p, seeds[l][m], fused[l][m], dtype, side_streams
-      final (default True): this node holds the LAST fusion layers.  The stack may be cut into several chained nodes
-        (mbt_encoder.py ``graph_segments``; needs prebuilt inputs and resbottle off): a non-final node ends with a
-        bottleneck exchange like every inner layer, returns no CLS vector, and its three output buffers are the next
-        node's prebuilt inputs -- the trainer captures the backward of each node in its own hipGraph so that the
-        gradient all-reduce of the later layers overlaps the backward of the earlier ones (ddp.GradReducer, staged mode).
-      n_streams (default 3): 2 = the two-stream encoder (BimodalTransformerEncoder_MBT, mbt_encoder.py:519-634): xt is
-        None, layer_params hold two blocks per layer, and ``missing`` carries table rows 1 (mean of both) / 3 (stream 0).
-      first_only: the caller reads stream 0's output only (mbt_encoder.py ``first_stream_output_only``): the last layer
-        runs stream 0 alone, exactly like vsltonly == 1 does; the other two outputs are zeros.
-      bott_rows_unused: the caller never reads rows 0..3 of the outputs (mbt_encoder.py slices them off), so with
-        vsltonly == 0 and no gradient for the image / text outputs the last layer's image / text blocks get no
-        backward at all (in the reference their gradient is None, not zero).
-    """
+    apply(xv, xi, xt, bottlenecks, *layer_params, plan) -> (out_v, out_i, out_t, cls_v); plan is a stack_plan.StackPlan: its
+    fields say what the node holds (and refuse the combinations it cannot run), plan.schedule() what every layer runs."""
 
     @staticmethod
     def forward(ctx, xv, xi, xt, bott, *rest):
-        cfg = rest[-1]
-        params = rest[:-1]
-        L, dt = cfg["n_layers"], cfg["dtype"]
-        final = cfg.get("final", True)
-        if not final and (not cfg.get("prebuilt") or cfg["resbottle"]):
-            raise ValueError("a non-final FusionStackFn segment needs prebuilt inputs and resbottle off")
-        n_s = cfg.get("n_streams", 3)
+        plan, params = rest[-1], rest[:-1]
+        dt, final, n_s = plan.dtype, plan.final, plan.n_streams
         xs = [xv, xi, xt][:n_s]
         _gpu(xv)
         B, dev = xv.shape[0], xv.device
-        if cfg.get("prebuilt"):            # xs ARE the [B, 4+N, 256] buffers (ops.StreamInputFn); read, never written
+        if plan.prebuilt:                  # xs ARE the [B, 4+N, 256] buffers (ops.StreamInputFn); read, never written
             Ns = [x.shape[1] for x in xs]
             z = [_c(x) for x in xs]
         else:
@@ -2413,65 +2372,41 @@ class FusionStackFn(torch.autograd.Function):
                 buf[:, :NB] = bott.to(dt)
                 z.append(buf)
         Ns, z = Ns + [0] * (3 - n_s), z + [None] * (3 - n_s)
-        wsel = _exchange_w(dev)
-        streams = cfg.get("side_streams")
+        streams, pack_v = plan.side_streams, plan.pack_v
         cur = torch.cuda.current_stream()
-        saved, active = [], []
-        cls_out = None
-        # the vital-sign stream PACKED (cfg["pack_v"] = row_starts(kv[0], Ns[0]), made by the encoder together with a packed
-        # stream input): bf16 grouped kernels only, and only for a caller that reads nothing of stream 0 but its CLS row
-        pack_v = cfg.get("pack_v")
-        if pack_v is not None and not (cfg.get("prebuilt") and z[0].dtype == torch.bfloat16 and cfg["kv"][0] is not None):
-            raise ValueError("a packed vital-sign stream needs prebuilt bf16 inputs with key lengths (ops.StreamInputFn)")
-        prev_bott = bott.expand(B, -1, -1).float().contiguous() if cfg["resbottle"] else None
-        for li in range(L):
-            last = final and (cfg["vsltonly"] == 1 or cfg.get("first_only")) and li == L - 1
-            ms = [0] if last else list(range(n_s))
+        saved = []
+        prev_bott = bott.expand(B, -1, -1).float().contiguous() if plan.resbottle else None
+        for li, step in enumerate(plan.schedule()):
             outs = [None, None, None]
             row = [None, None, None]
-            # the layer in front of a last layer that runs stream 0 alone, read by a CLS-only reader (the encoder names it, by its
-            # index in this segment): the image / text outputs of THIS layer feed the bottleneck exchange (rows 0..3) and nothing
-            # else, so their FFN runs on those rows (bf16; the fp32 parity build keeps the dense FFN)
-            exchange_only = (li == cfg.get("exchange_only_layer", -1) and tuning.FFN_ROWS_BEFORE_LAST
-                             and z[0].dtype == torch.bfloat16)
-            cls_tok = NB if (last and cfg.get("cls_only")) else None       # the reader takes the CLS row only
             # launch groups of this layer: (streams, HIP stream).  Layer 0 keeps one group per stream while the image / text
             # inputs are still being made on the side streams (the vital-sign stream's first layer runs beside the image encoder)
-            groups = launch_groups(ms, streams, z[0], solo=(li == 0 and bool(cfg.get("inputs_on_side"))))
-            for gms in _each_group(groups, cur):
+            for gms in _each_group(launch_groups(step.streams, streams, z[0], solo=step.solo), cur):
                 mark(f"f{li}.g{gms[0]}.s")
-                go, gsaved = layer_forward([z[m] for m in gms], [cfg["kv"][m] for m in gms], [_stack_params(params, cfg, li, m) for m in gms],
-                                           [cfg["fused"][li][m] for m in gms], cfg["drop_p"], [cfg["seeds"][li][m] for m in gms],
+                go, gsaved = layer_forward([z[m] for m in gms], [plan.kv[m] for m in gms], [params[plan.block(li, m)] for m in gms],
+                                           [plan.fused[li][m] for m in gms], plan.drop_p, [plan.seeds[li][m] for m in gms],
                                            [pack_v if m == 0 else None for m in gms],
-                                           ffn_rows=NB if (exchange_only and 0 not in gms) else None, cls_tok=cls_tok)
+                                           ffn_rows=None if 0 in gms else step.ffn_rows, cls_tok=step.cls_tok)
                 for i, m in enumerate(gms):
                     outs[m], row[m] = go[i], gsaved[i]
                 mark(f"f{li}.g{gms[0]}.e")
             saved.append(row)
-            active.append(ms)
-            if cls_tok is not None:
-                cls_out, z = outs[0], [None, None, None]
-                break
-            if last:
-                z = outs
-                break
-            # bottleneck exchange (:764-779) on the [B,4,256] prefixes, written back in place (one kernel)
-            keep = torch.empty(B, NB, D_MODEL, dtype=torch.float32, device=dev) if cfg["resbottle"] else None
-            bottleneck_exchange_fwd(outs, cfg["missing"], cfg["resbottle"], prev_bott if cfg["resbottle"] else None, keep, pack_v)
-            prev_bott = keep
             z = outs
-        if streams is not None and cfg.get("prebuilt"):
+            if step.exchange:              # (:764-779) on the [B,4,256] prefixes, written back in place (one kernel)
+                keep = torch.empty(B, NB, D_MODEL, dtype=torch.float32, device=dev) if plan.resbottle else None
+                bottleneck_exchange_fwd(outs, plan.missing, plan.resbottle, prev_bott, keep, pack_v)
+                prev_bott = keep
+        if streams is not None and plan.prebuilt:
             for s in streams:              # inputs made on the side streams but never consumed there (single vslt-only layer)
                 cur.wait_stream(s)
-        ctx.saved, ctx.active, ctx.cfg, ctx.wsel = saved, active, cfg, wsel
-        ctx.shapes = (B, Ns, [p.shape for p in params])
+        ctx.saved, ctx.plan = saved, plan
+        ctx.shapes = (B, Ns, [p.shape for p in params], dev)
         ctx.set_materialize_grads(False)
-        ctx.cls_only = cls_out is not None
-        if cls_out is not None:            # nothing but the CLS row exists of the last layer's output: placeholders (one fill, three views)
+        if step.cls_tok is not None:       # nothing but the CLS row exists of the last layer's output: placeholders (one fill, three views)
             ph = torch.zeros(1, NB + 1, D_MODEL, dtype=dt, device=dev)
             outs_full = [ph.expand(B, -1, -1) for _ in range(3)]
             ctx.mark_non_differentiable(*outs_full)
-            return outs_full[0], outs_full[1], outs_full[2], cls_out
+            return outs_full[0], outs_full[1], outs_full[2], outs[0]
         outs_full = [z[m] if z[m] is not None else torch.zeros(B, Ns[m], D_MODEL, dtype=dt, device=dev) for m in range(3)]
         ctx.mark_non_differentiable(*[o for m, o in enumerate(outs_full) if z[m] is None])
         if pack_v is not None:             # row pack_v[b] + NB of the packed buffer
@@ -2483,77 +2418,46 @@ class FusionStackFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_v, d_i, d_t, d_cls):
-        cfg, saved, active, wsel = ctx.cfg, ctx.saved, ctx.active, ctx.wsel
-        B, Ns, pshapes = ctx.shapes
-        L, dt = cfg["n_layers"], cfg["dtype"]
-        dev = wsel.device
-        streams = cfg.get("side_streams")
+        plan, saved = ctx.plan, ctx.saved
+        B, Ns, pshapes, dev = ctx.shapes
+        dt, n_s, streams, pack_v = plan.dtype, plan.n_streams, plan.side_streams, plan.pack_v
         cur = torch.cuda.current_stream()
-        n_run = len(active)             # layers that ran
-        n_s = cfg.get("n_streams", 3)
-        final = cfg.get("final", True)
-        # vsltonly == 0: the last layer ran all three streams, but when nothing downstream read the image / text outputs
-        # (and nobody reads the exchanged bottleneck rows) their blocks have no gradient: run the backward of the last
-        # layer like the vslt-only one (the reference's autograd never reaches those blocks either)
-        if (final and cfg["vsltonly"] != 1 and d_i is None and d_t is None and cfg.get("bott_rows_unused")
-                and not cfg["resbottle"] and len(active[-1]) == n_s):
-            active = active[:-1] + [[0]]
-            skip_last_exchange = True
-        else:
-            skip_last_exchange = False
-        # gradient w.r.t. the last executed layer's outputs
+        steps = plan.backward_schedule(d_i is None and d_t is None)
+        shapes = [(B, N, D_MODEL) for N in Ns]
+        # gradient w.r.t. the last layer's outputs
         dz = [None, None, None]
-        for m, g in enumerate((d_v, d_i, d_t)):
-            if m in active[-1] and not ctx.cls_only:
-                dz[m] = torch.zeros(B, Ns[m], D_MODEL, dtype=dt, device=dev) if g is None else _c(g).to(dt).clone()
-        pack_v = cfg.get("pack_v")
-        if ctx.cls_only:                   # the last layer's only output is the CLS row
+        if steps[-1].cls_tok is not None:  # the last layer's only output is the CLS row
             dz[0] = d_cls if d_cls is not None else torch.zeros(B, D_MODEL, dtype=dt, device=dev)
-        elif d_cls is not None and pack_v is not None:
-            dz[0].view(-1, D_MODEL).index_add_(0, ctx.cls_rows, d_cls.to(dt))
-        elif d_cls is not None:
-            dz[0][:, NB, :] += d_cls.to(dt)
+        else:
+            for m in steps[-1].streams:
+                g = (d_v, d_i, d_t)[m]
+                dz[m] = torch.zeros(shapes[m], dtype=dt, device=dev) if g is None else _c(g).to(dt).clone()
+            if d_cls is not None and pack_v is not None:
+                dz[0].view(-1, D_MODEL).index_add_(0, ctx.cls_rows, d_cls.to(dt))
+            elif d_cls is not None:
+                dz[0][:, NB, :] += d_cls.to(dt)
         pgrads = [None] * len(pshapes)
         d_prev_bott = None           # gradient flowing into the previous exchange's output through resbottle
-
-        def keep_grads(li, m, g):
-            """a layer's returned gradients (None: they went through its sink) into their places of this node's result"""
-            if g is not None:
-                base = (li * n_s + m) * PARAMS_PER_LAYER
-                for k in range(PARAMS_PER_LAYER):
-                    pgrads[base + k] = g[k].view(pshapes[base + k])
-
-        def zero_other_streams(nxt):
-            """zero gradient buffers of the streams a vslt-only layer skipped: ONE fill for both (views of one allocation)"""
-            buf = torch.zeros(B * sum(Ns[m] for m in range(1, n_s)), D_MODEL, dtype=dt, device=dev)
-            r0 = 0
-            for m in range(1, n_s):
-                nxt[m] = buf[r0:r0 + B * Ns[m]].view(B, Ns[m], D_MODEL)
-                r0 += B * Ns[m]
-
-        for li in range(n_run - 1, -1, -1):
-            ms = active[li]
-            if not ((final and (cfg["vsltonly"] == 1 or cfg.get("first_only")) and li == L - 1)
-                    or (skip_last_exchange and li == n_run - 1)):
+        for li, step in reversed(list(enumerate(steps))):
+            if step.exchange:
                 # this layer's outputs went through an exchange before feeding layer li+1: rows 0..3 of the three
                 # gradient buffers are summed and redistributed by the exchange weights, in place (one kernel)
-                d_out_prev = torch.empty(B, NB, D_MODEL, dtype=torch.float32, device=dev) if cfg["resbottle"] else None
-                bottleneck_exchange_bwd(dz, cfg["missing"], cfg["resbottle"], d_prev_bott, d_out_prev, pack_v)
+                d_out_prev = torch.empty(B, NB, D_MODEL, dtype=torch.float32, device=dev) if plan.resbottle else None
+                bottleneck_exchange_bwd(dz, plan.missing, plan.resbottle, d_prev_bott, d_out_prev, pack_v)
                 d_prev_bott = d_out_prev
             nxt = [None, None, None]
-            for gms in _each_group(launch_groups(ms, streams, saved[li][ms[0]].z), cur):
+            for gms in _each_group(launch_groups(step.streams, streams, saved[li][0].z), cur):
                 mark(f"b{li}.g{gms[0]}.s")
-                gdz, gg = layer_backward([saved[li][m] for m in gms], [dz[m] for m in gms], [_stack_sink(cfg, li, m) for m in gms])
+                gdz, gg = layer_backward([saved[li][m] for m in gms], [dz[m] for m in gms], [plan.sink(li, m) for m in gms])
                 for i, m in enumerate(gms):
                     nxt[m] = gdz[i]
-                    keep_grads(li, m, gg[i])
+                    keep_grads(pgrads, pshapes, plan.block(li, m), gg[i])
                 mark(f"b{li}.g{gms[0]}.e")
             saved[li] = None
-            # streams skipped by the vslt-only last layer re-enter here with zero gradient
-            if len(ms) == 1 and li > 0:
-                zero_other_streams(nxt)
+            if len(step.streams) == 1 and li > 0:      # the streams the last layer skipped re-enter here with zero gradient
+                nxt[1:n_s] = zero_streams(shapes[1:n_s], dt, dev)
             dz = nxt
-        if cfg.get("prebuilt"):            # the bottleneck rows' gradient flows on through the stream-input nodes
+        if plan.prebuilt:                  # the bottleneck rows' gradient flows on through the stream-input nodes
             d_bott = None if d_prev_bott is None else d_prev_bott.sum(0, keepdim=True)
             return (dz[0], dz[1], dz[2], d_bott, *pgrads, None)
         d_bott = sum(dz[m][:, :NB].float() for m in range(3) if dz[m] is not None)
@@ -2574,7 +2478,6 @@ MULTI_BOTTLENECKS_MAP = ((0, 1, 2), (0, 1, 3), (0, 2, 3))         # stream -> th
 # set's pattern 3 reads the image stream's rows although both holders are missing -- kept as it is)
 MULTI_B_OUT_MEAN_MAP = (((0, 1, 2), (0, 1), (0, 2), (0,)), ((0, 1), (0, 1), (0,), (0,)), ((0, 1), (0,), (0, 1), (0,)),
                         ((0, 1), (0,), (1,), (0,)))
-N_PREFIX = 12
 
 
 def multi_exchange_weights() -> torch.Tensor:
@@ -2630,30 +2533,28 @@ class BottleneckExchangeMultiFn(torch.autograd.Function):
 
 class MultiTokenStackFn(torch.autograd.Function):
     """All fusion layers of the multi-token encoder as one autograd node on the layer engine (layer_forward /
-    layer_backward): apply(z_v, z_i, z_t, *layer_params, cfg) -> (out_v, out_i, out_t), every buffer [B, 12 + N_m, 256]
+    layer_backward): apply(z_v, z_i, z_t, *layer_params, plan) -> (out_v, out_i, out_t), every buffer [B, 12 + N_m, 256]
     = [prefix | tokens] in the compute dtype.  A layer writes new buffers, the exchange overwrites their prefix rows in place and
-    they are the next layer's inputs.  cfg: n_layers, kv (int32[B] | None per stream, prefix included), masks (words | None per
-    stream), missing (int64[B]), drop_p, seeds[l][m], fused[l][m] (None for a block that is not run), first_only (the caller reads
-    stream 0's output only: the last layer runs that stream alone; the other outputs are zeros without a gradient)."""
+    they are the next layer's inputs.  plan: a stack_plan.StackPlan with ``masks`` and exchange_last off (the reference exchanges
+    after the last layer too; nothing reads that result); of its switches this node knows first_only.  The streams of a layer are
+    one group on the caller's stream, and no gradient goes through a sink."""
 
     @staticmethod
     def forward(ctx, zv, zi, zt, *rest):
-        cfg, params = rest[-1], rest[:-1]
+        plan, params = rest[-1], rest[:-1]
         _gpu(zv)
-        L = cfg["n_layers"]
         z = [_c(t) for t in (zv, zi, zt)]
-        saved, active = [], []
-        for li in range(L):
-            ms = [0] if (cfg.get("first_only") and li == L - 1) else [0, 1, 2]
-            Ps = [params[(li * 3 + m) * PARAMS_PER_LAYER:(li * 3 + m + 1) * PARAMS_PER_LAYER] for m in ms]
-            outs, sv = layer_forward([z[m] for m in ms], [cfg["kv"][m] for m in ms], Ps, [cfg["fused"][li][m] for m in ms],
-                                     cfg["drop_p"], [cfg["seeds"][li][m] for m in ms], qk_masks=[cfg["masks"][m] for m in ms])
+        saved = []
+        for li, step in enumerate(plan.schedule()):
+            ms = step.streams
+            outs, sv = layer_forward([z[m] for m in ms], [plan.kv[m] for m in ms], [params[plan.block(li, m)] for m in ms],
+                                     [plan.fused[li][m] for m in ms], plan.drop_p, [plan.seeds[li][m] for m in ms],
+                                     qk_masks=[plan.masks[m] for m in ms])
             saved.append(sv)
-            active.append(ms)
             z = [outs[ms.index(m)] if m in ms else None for m in range(3)]
-            if li < L - 1:                 # (the reference exchanges after the last layer too; nothing reads that result)
-                bottleneck_exchange_multi(z, cfg["missing"])
-        ctx.saved, ctx.active, ctx.cfg = saved, active, cfg
+            if step.exchange:
+                bottleneck_exchange_multi(z, plan.missing)
+        ctx.saved, ctx.plan = saved, plan
         ctx.shapes = ([t.shape for t in (zv, zi, zt)], [p.shape for p in params], zv.dtype, zv.device)
         ctx.set_materialize_grads(False)
         outs = [t if t is not None else torch.zeros(shp, dtype=zv.dtype, device=zv.device) for t, shp in zip(z, ctx.shapes[0])]
@@ -2662,26 +2563,23 @@ class MultiTokenStackFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_v, d_i, d_t):
-        cfg, saved, active = ctx.cfg, ctx.saved, ctx.active
+        plan, saved = ctx.plan, ctx.saved
         zshapes, pshapes, dt, dev = ctx.shapes
+        steps = plan.schedule()
         pgrads = [None] * len(pshapes)
         dz = [None, None, None]
-        for m, g in enumerate((d_v, d_i, d_t)):
-            if m in active[-1]:
-                dz[m] = torch.zeros(zshapes[m], dtype=dt, device=dev) if g is None else _c(g).to(dt).clone()
-        for li in range(len(active) - 1, -1, -1):
-            ms = active[li]
-            if li < len(active) - 1:       # this layer's outputs went through an exchange
-                bottleneck_exchange_multi(dz, cfg["missing"], backward=True)
-            gdz, gg = layer_backward(saved[li], [dz[m] for m in ms])
+        for m in steps[-1].streams:
+            g = (d_v, d_i, d_t)[m]
+            dz[m] = torch.zeros(zshapes[m], dtype=dt, device=dev) if g is None else _c(g).to(dt).clone()
+        for li, step in reversed(list(enumerate(steps))):
+            if step.exchange:              # this layer's outputs went through an exchange
+                bottleneck_exchange_multi(dz, plan.missing, backward=True)
+            gdz, gg = layer_backward(saved[li], [dz[m] for m in step.streams])
             saved[li] = None
             dz = [None, None, None]
-            for i, m in enumerate(ms):
+            for i, m in enumerate(step.streams):
                 dz[m] = gdz[i]
-                base = (li * 3 + m) * PARAMS_PER_LAYER
-                for k in range(PARAMS_PER_LAYER):
-                    pgrads[base + k] = gg[i][k].view(pshapes[base + k])
-            if len(ms) == 1 and li > 0:    # the streams the last layer skipped re-enter with zero gradient
-                for m in (1, 2):
-                    dz[m] = torch.zeros(zshapes[m], dtype=dt, device=dev)
+                keep_grads(pgrads, pshapes, plan.block(li, m), gg[i])
+            if len(step.streams) == 1 and li > 0:      # the streams the last layer skipped re-enter with zero gradient
+                dz[1:] = zero_streams(zshapes[1:], dt, dev)
         return (dz[0], dz[1], dz[2], *pgrads, None)

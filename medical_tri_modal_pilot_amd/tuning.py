@@ -12,6 +12,9 @@ A switch stays here only while its other setting is worth measuring again.  The 
 backward folded into the dH launch, deferred and late gradient reductions, grouped against per-stream launches) and the two
 stream issue orders nothing read are retired with the code their other setting selected: ops.layer_forward / ops.layer_backward
 are the one engine, and DESIGN.md section 9 keeps their measurements and names the last commit that holds the code.
+
+The two switches of the fusion stack and their one reader each, at call time: GROUP_MODE is read by ops.launch_groups() when a
+layer's launch groups are made, FFN_ROWS_BEFORE_LAST by stack_plan.StackPlan.schedule() when a node's schedule is made.
 """
 
 # How a layer's streams are cut into launches (bf16; the fp32 parity build launches per stream): "small" = the vital-sign stream
