@@ -358,7 +358,9 @@ int mtmp_swin_mlp(int dtype, const void* x, const float* ln_w, const float* ln_b
 /* Shifted-window attention (swin_transformer.py:115-225, V1 branch) on the un-shifted NHWC map:
  * qkv [n,H,W,3C] -> out [n,H,W,C]; window 7x7, head_dim 32, H % 7 == W % 7 == 0.
  * table [4 window types][heads][64][64] in `dtype` = relative-position bias + shift mask
- * (type = 2*(last window row) + (last window col), 0 when shift == 0), -30000 on pad keys. */
+ * (type = 2*(last window row) + (last window col), 0 when shift == 0), -30000 on pad keys.
+ * shift > 0 needs H > 7 and W > 7: the reference does not shift an axis of one window (:155-160), so such a call is refused
+ * (the caller passes shift 0 for a 7x7 map); the same holds for mtmp_swin_window_attn_live / _bwd and mtmp_swin_attn_block. */
 int mtmp_swin_window_attn(int dtype, const void* qkv, const void* table, void* out, int n_img, int H, int W, int C,
                           int heads, int shift, float scale, void* stream);
 
@@ -551,7 +553,7 @@ int mtmp_swin_window_attn_live(int dtype, const void* qkv, const void* table, vo
  * mtmp_gelu_fwd / mtmp_gelu_bwd: nn.GELU of the MLP (:437-439) as its own pass, and dx = dy GELU'(x); n % 8 == 0.
  * mtmp_swin_window_attn_bwd: autograd of mtmp_swin_window_attn (:115-225).  dout [n,H,W,C] -> dqkv [n,H,W,3C] (every element
  *   written once; H, W multiples of 7) and dtab float[4][heads][64][64], the gradient of the additive table, which the caller
- *   ZEROES first (float atomics). */
+ *   ZEROES first (float atomics).  shift > 0 with H == 7 or W == 7 is refused, as in the forward. */
 int mtmp_layernorm_rows_bwd_slab_rows(long long rows, int C);
 int mtmp_layernorm_rows_bwd(int dtype, const void* x, const float* w, const void* dy, void* dx, float* slab, long long rows, int C,
                             float eps, void* stream);
@@ -585,7 +587,8 @@ int mtmp_swin_window_attn_pad_bwd(int dtype, const void* qkv, const float* qkv_b
  * (out != x), C = 96 or 192, heads = C / 32; wqkv [3C][C], wproj [C][C] bf16; ln_w, ln_b [C], bqkv [3C], bproj [C] fp32; table
  * [4 window types][heads][64][64] bf16 as mtmp_swin_window_attn's, but with the KEY columns of every group of 16 keys in
  * accumulator-register order: position 8 h + j (h = 0, 1; j = 0..7) of group g holds key 16 g + (j & 3) + 8 (j >> 2) + 4 h.
- * row_scale: fp32[n_img] (row-mode StochasticDepth) or NULL; rows_live: NULL or the device word of mtmp_image_slots. */
+ * row_scale: fp32[n_img] (row-mode StochasticDepth) or NULL; rows_live: NULL or the device word of mtmp_image_slots.
+ * shift > 0 with H == 7 or W == 7 is refused (an axis of one window is not shifted, :155-160). */
 int mtmp_swin_attn_block(int dtype, const void* x, const float* ln_w, const float* ln_b, float eps, const void* wqkv,
                          const float* bqkv, const void* table, const void* wproj, const float* bproj, const float* row_scale,
                          void* out, int n_img, int H, int W, int C, int heads, int shift, float scale, const int32_t* rows_live,

@@ -879,6 +879,9 @@ extern "C" int mtmp_swin_window_attn_live(int dtype, const void* qkv, const void
     MTMP_CHECK_ARG(qkv && table && out, "mtmp_swin_window_attn: null pointer");
     MTMP_CHECK_ARG(n_img > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0 && heads > 0 && C == heads * DH && shift >= 0 &&
                        shift < WS, "mtmp_swin_window_attn: bad shape n=%d H=%d W=%d C=%d heads=%d shift=%d", n_img, H, W, C, heads, shift);
+    // (swin_transformer.py:155-160 sets shift_size 0 on an axis the window spans; the kernel would roll and mask it)
+    MTMP_CHECK_ARG(shift == 0 || (H > WS && W > WS), "mtmp_swin_window_attn: a side of one window is not shifted (H=%d W=%d shift=%d)", H, W,
+                   shift);
     return launch_swin_wattn<false>("mtmp_swin_window_attn", dtype, qkv, nullptr, table, out, n_img, H, W, C, heads, shift, scale,
                                     rows_live, stream);
 }
@@ -980,6 +983,8 @@ extern "C" int mtmp_swin_attn_block(int dtype, const void* x, const float* ln_w,
                        W % WS == 0 && shift >= 0 && shift < WS,
                    "mtmp_swin_attn_block: bf16 with C = 96 or 192, heads = C / 32, maps that are multiples of 7 only "
                    "(dtype=%d C=%d heads=%d n=%d H=%d W=%d shift=%d)", dtype, C, heads, n_img, H, W, shift);
+    MTMP_CHECK_ARG(shift == 0 || (H > WS && W > WS), "mtmp_swin_attn_block: a side of one window is not shifted (H=%d W=%d shift=%d)", H, W,
+                   shift);
     return launch_swin_attn_block<false>("mtmp_swin_attn_block", (long long)n_img * (H / WS) * (W / WS), x, ln_w, ln_b, eps, wqkv, bqkv,
                                          table, wproj, bproj, row_scale, out, n_img, H, W, C, shift, scale, rows_live, stream);
 }

@@ -516,6 +516,8 @@ extern "C" int mtmp_swin_window_attn_bwd(int dtype, const void* qkv, const void*
     MTMP_CHECK_ARG(qkv && table && dout && dqkv && dtab, "mtmp_swin_window_attn_bwd: null pointer");
     MTMP_CHECK_ARG(n_img > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0 && heads > 0 && C == heads * DH && shift >= 0 && shift < WS,
                    "mtmp_swin_window_attn_bwd: bad shape n=%d H=%d W=%d C=%d heads=%d shift=%d", n_img, H, W, C, heads, shift);
+    MTMP_CHECK_ARG(shift == 0 || (H > WS && W > WS), "mtmp_swin_window_attn_bwd: a side of one window is not shifted (H=%d W=%d shift=%d)", H,
+                   W, shift);
     return launch_swin_wattn_bwd<false>("mtmp_swin_window_attn_bwd", dtype, qkv, nullptr, table, dout, dqkv, dtab, nullptr, n_img, H, W,
                                         C, heads, shift, scale, stream);
 }

@@ -105,8 +105,10 @@ CALLS = {
     "mtmp_swin_stem_fwd_live": ([1, P, P, P, P, P, P, 2, 32, 32, None, None, None], [("null", {1: None}), ("W", {9: 30}), ("dtype7", {0: 7})]),
     "mtmp_layernorm_rows": ([1, P, P, P, P, 100, 96, 1e-5, 0, 0, 0, None], [("null", {4: None}), ("C", {6: 100}), ("dtype7", {0: 7})]),
     "mtmp_layernorm_rows_live": ([1, P, P, P, P, 100, 96, 1e-5, 0, 0, 0, None, None], [("rows", {5: 0}), ("merge", {8: 1, 9: 3, 10: 4}), ("dtype7", {0: 7})]),
-    "mtmp_swin_window_attn": ([1, P, P, P, 2, 14, 14, 96, 3, 0, 0.17, None], [("null", {2: None}), ("H", {5: 15}), ("dtype7", {0: 7})]),
-    "mtmp_swin_window_attn_live": ([1, P, P, P, 2, 14, 14, 96, 3, 0, 0.17, None, None], [("null", {3: None}), ("shift", {9: 7}), ("dtype7", {0: 7})]),
+    "mtmp_swin_window_attn": ([1, P, P, P, 2, 14, 14, 96, 3, 0, 0.17, None], [("null", {2: None}), ("H", {5: 15}), ("dtype7", {0: 7}),
+                               ("one_window_shifted", {5: 7, 6: 7, 9: 3}), ("one_window_side_shifted", {5: 7, 9: 3})]),
+    "mtmp_swin_window_attn_live": ([1, P, P, P, 2, 14, 14, 96, 3, 0, 0.17, None, None], [("null", {3: None}), ("shift", {9: 7}), ("dtype7", {0: 7}),
+                                    ("one_window_shifted", {5: 7, 6: 7, 9: 3}), ("one_window_side_shifted", {6: 7, 9: 3})]),
     "mtmp_swin_window_attn_pad": ([1, P, P, P, P, 2, 16, 16, 96, 3, 0, 0.17, None, None],
                                   [("null", {2: None}), ("C", {8: 100}), ("one_window_shifted", {6: 5, 7: 5, 10: 1}), ("dtype7", {0: 7})]),
     "mtmp_swin_mlp": ([1, P, P, P, P, P, P, P, None, 1, P2, 100, 96, 1e-5, None],
@@ -115,7 +117,8 @@ CALLS = {
     "mtmp_swin_ln_linear": ([1, P, P, P, P, None, P, 100, 96, 288, 1e-5, None], [("null", {6: None}), ("N", {9: 100}), ("fp32", {0: 0})]),
     "mtmp_swin_ln_linear_live": ([1, P, P, P, P, None, P, 100, 96, 288, 1e-5, None, None], [("null", {4: None}), ("C", {8: 128}), ("fp32", {0: 0})]),
     "mtmp_swin_attn_block": ([1, P, P, P, 1e-5, P, P, P, P, P, None, P2, 2, 14, 14, 96, 3, 0, 0.17, None, None],
-                             [("null", {7: None}), ("in_place", {11: P}), ("H", {13: 15}), ("fp32", {0: 0})]),
+                             [("null", {7: None}), ("in_place", {11: P}), ("H", {13: 15}), ("fp32", {0: 0}),
+                              ("one_window_shifted", {13: 7, 14: 7, 17: 3}), ("one_window_side_shifted", {13: 7, 17: 3})]),
     "mtmp_swin_attn_block_pad": ([1, P, P, P, 1e-5, P, P, P, P, P, None, P2, 2, 16, 16, 96, 3, 0, 0.17, None, None],
                                  [("null", {7: None}), ("heads", {16: 4}), ("one_side_single_window", {14: 5}),
                                   ("one_window_shifted", {13: 5, 14: 5, 17: 1}), ("fp32", {0: 0})]),
@@ -123,7 +126,8 @@ CALLS = {
     "mtmp_layernorm_rows_bwd": ([1, P, P, P, P, P, 100, 96, 1e-5, None], [("null", {5: None}), ("C", {7: 100}), ("dtype7", {0: 7})]),
     "mtmp_gelu_fwd": ([1, P, P, 1024, None], [("null", {2: None}), ("n", {3: 1001}), ("dtype7", {0: 7})]),
     "mtmp_gelu_bwd": ([1, P, P, P, 1024, None], [("null", {2: None}), ("n", {4: 1001}), ("dtype7", {0: 7})]),
-    "mtmp_swin_window_attn_bwd": ([1, P, P, P, P, P, 2, 14, 14, 96, 3, 0, 0.17, None], [("null", {5: None}), ("W", {8: 15}), ("dtype7", {0: 7})]),
+    "mtmp_swin_window_attn_bwd": ([1, P, P, P, P, P, 2, 14, 14, 96, 3, 0, 0.17, None], [("null", {5: None}), ("W", {8: 15}), ("dtype7", {0: 7}),
+                                   ("one_window_shifted", {7: 7, 8: 7, 11: 3}), ("one_window_side_shifted", {7: 7, 11: 3})]),
     "mtmp_swin_window_attn_pad_bwd": ([1, P, P, P, P, P, P, P, 2, 16, 16, 96, 3, 0, 0.17, None],
                                       [("null", {7: None}), ("heads", {12: 4}), ("one_window_shifted", {9: 5, 10: 5, 13: 1}), ("dtype7", {0: 7})]),
     # ---- attention.hip
