@@ -877,6 +877,21 @@ long long mtmp_eval_workspace_bytes(long long n);
 int mtmp_eval_metrics(const float* pred, const uint8_t* tgt, long long n, const long long* ctr, const double* loss_sum,
                       void* workspace, long long workspace_bytes, double* out, void* stream);
 
+/* The position-wise FFN block of an encoder layer as ONE launch, for forwards that nobody differentiates (csrc/ffn_infer.hip):
+ *     out[M,256] = x + relu(LN(x) W1^T + c1) W2^T + c2
+ * LN = the custom LayerNorm of builder/models/src/transformer/module.py:138-144 (unbiased std, eps added to the std), W1 [1024,256],
+ * W2 [256,1024] in the compute dtype, gamma / beta / c1 / c2 fp32, no dropout.  The hidden activation never reaches memory: the
+ * kernel writes nothing but out.  ldx / ldo: row strides of x / out in elements (>= 256, multiples of 8); out must not overlap x.
+ * mtmp_ffn_block: fp32 (the parity build) and bf16.  mtmp_ffn_block_grouped: bf16, up to three token streams in one grid; all
+ * pointer / int arrays are HOST arrays of n entries, rows_live as in the grouped row kernels above (may be NULL as a whole or per
+ * entry).  Same kernel, same results as n single calls.  All argument errors return before anything touches a GPU. */
+int mtmp_ffn_block(int dtype, const void* x, int ldx, const float* gamma, const float* beta, const void* w1, const float* c1,
+                   const void* w2, const float* c2, void* out, int ldo, int M, float eps, void* stream);
+int mtmp_ffn_block_grouped(int dtype, int n, const void* const* x, const int* ldx, const float* const* gamma,
+                           const float* const* beta, const void* const* w1, const float* const* c1, const void* const* w2,
+                           const float* const* c2, void* const* out, const int* ldo, const int* M, float eps,
+                           const int32_t* const* rows_live, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

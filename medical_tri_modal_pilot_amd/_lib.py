@@ -152,6 +152,8 @@ SIGNATURES = {
     "mtmp_eval_workspace_bytes": (c_longlong, [c_longlong]),
     "mtmp_eval_metrics": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p]),
     "mtmp_dropout_bwd": (c_int, [c_int, c_void_p, c_void_p, c_longlong, c_uint, c_void_p, c_float, c_void_p]),
+    "mtmp_ffn_block": (c_int, [c_int, c_void_p, c_int] + [c_void_p] * 7 + [c_int, c_int, c_float, c_void_p]),
+    "mtmp_ffn_block_grouped": (c_int, [c_int, c_int] + [c_void_p] * 11 + [c_float, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -129,6 +129,8 @@ class TransformerEncoderLayer(nn.Module):
         if kv_len is not None:
             kv_len = kv_len.to(device=inputs.device, dtype=torch.int32).contiguous()
         p, seeds = self.dropout_args()
+        if ops.infer_active(p):            # (read here, at call time: inside the node grad mode is always off)
+            return ops.EncoderLayerFn.apply(inputs, kv_len, *self.param_list(), self._fused_weights(inputs.dtype), p, seeds, None, True), None
         out = ops.EncoderLayerFn.apply(inputs, kv_len, *self.param_list(), self._fused_weights(inputs.dtype), p, seeds)
         return out, None
 

@@ -224,7 +224,8 @@ class TrimodalTransformerEncoder_MBT(nn.Module):
                              sinks=sinks and sinks[b0:b1], prebuilt=fused_in or b0 > 0, final=final, bott_rows_unused=True,
                              first_only=first_only and final, missing=missing, drop_p=p, seeds=seeds[b0:b1], fused=fused[b0:b1],
                              dtype=dt, side_streams=self._side_streams(dev), inputs_on_side=side_in is not None and b0 == 0,
-                             pack_v=pack_v, cls_only=cls_only and final, exchange_only_layer=g_ex - b0 if b0 <= g_ex < b1 else -1)
+                             pack_v=pack_v, cls_only=cls_only and final, exchange_only_layer=g_ex - b0 if b0 <= g_ex < b1 else -1,
+                             infer=ops.infer_active(p))
             out_v, out_i, out_t, cls_v = ops.FusionStackFn.apply(zs[0], zs[1], zs[2], self.bottlenecks, *params[b0 * per:b1 * per], plan)
             zs = (out_v, out_i, out_t)
             if not final:
@@ -315,7 +316,8 @@ class BimodalTransformerEncoder_MBT(nn.Module):
         fl = list(self.layer_stacks)
         params, fused, seeds, p, sinks = collect_blocks(fl, lambda li, m: False, dt)
         plan = StackPlan(n_layers=len(fl), n_streams=2, kv=kv + [None], sinks=sinks, prebuilt=True, bott_rows_unused=True,
-                         missing=pattern, drop_p=p, seeds=seeds, fused=fused, dtype=dt, side_streams=self._side_streams(dev))
+                         missing=pattern, drop_p=p, seeds=seeds, fused=fused, dtype=dt, side_streams=self._side_streams(dev),
+                         infer=ops.infer_active(p))
         out0, out1, _, _ = ops.FusionStackFn.apply(streams[0], streams[1], None, self.bottlenecks, *params, plan)
         nb = self.bottlenecks_n
         return [out0[:, nb:], out1[:, nb:]], 0
@@ -441,6 +443,6 @@ class TrimodalTransformerEncoder_Multitokens_MBTVSLTMAIN(nn.Module):
         first_only = bool(self.first_stream_output_only)
         params, fused, seeds, p, _ = collect_blocks(fl, lambda li, m: first_only and li == len(fl) - 1 and m > 0, dt, want_sinks=False)
         plan = StackPlan(n_layers=len(fl), kv=kv, masks=self.mask_words(), missing=missing, drop_p=p, seeds=seeds, fused=fused,
-                         dtype=dt, first_only=first_only, exchange_last=False)
+                         dtype=dt, first_only=first_only, exchange_last=False, infer=ops.infer_active(p))
         outs = ops.MultiTokenStackFn.apply(zs[0], zs[1], zs[2], *params, plan)
         return [o[:, self.n_prefix:] for o in outs], 0

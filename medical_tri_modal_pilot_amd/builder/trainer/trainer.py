@@ -437,7 +437,7 @@ def missing_trainer(args, iteration, train_x, static_x, input_lengths, train_y, 
         scheduler.step(iteration)
         logger.log_lr(scheduler.get_lr()[0], iteration)
     else:
-        with torch.no_grad():
+        with torch.no_grad(), ops.inference_forward(bool(int(getattr(args, "infer_forward", 0)))):
             output = eval_logits(args, run_model(), inp.tensors())
             loss = ops.bce_with_logits(criterion, output, final_target)
             output = torch.sigmoid(output)

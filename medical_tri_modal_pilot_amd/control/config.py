@@ -144,6 +144,10 @@ _BUILD_FLAGS = [
                                       help="1: the frozen image encoder runs on the samples that HAVE an image only (the others' "
                                            "features are read by nothing); 0: a zero image goes through the encoder as in the "
                                            "reference")),
+    (("--infer-forward",), dict(type=int, default=0, choices=[0, 1],
+                                help="1: forwards without grad mode and without dropout (validate(), the trainer's 'test' flow) run "
+                                     "the encoder layers as ops.layer_infer -- nothing is kept for a backward, the FFN is one fused "
+                                     "launch; 0: every forward is the training forward")),
     (("--n-images",), dict(type=int, default=3, help="images per sample when --multiimages 1 (reference: 3)")),
     (("--synthetic",), dict(type=int, default=0, choices=[0, 1], help="train on synthetic batches (SURVEY.md §8d)")),
 ]

@@ -97,14 +97,15 @@ def ln_gemm(x2d, gamma, beta, w, bias, n_out, relu=False, drop_p=0.0, seed=0, wa
     return (y, xn, stats, None) if want_signs else (y, xn, stats)
 
 
-def ln_gemm_qkv(x2d, gamma, beta, wqkv, bqkv):
+def ln_gemm_qkv(x2d, gamma, beta, wqkv, bqkv, keep=True):
     """The Q/K/V projection: (qkv[M,768], xn[M,256], stats[M,2], knorm[ceil(M/32),4]) -- ln_gemm plus the key-norm table of
-    the attention forward's bounded body, written from the projection's epilogue (bf16) or by mtmp_key_norms behind it (fp32)."""
+    the attention forward's bounded body, written from the projection's epilogue (bf16) or by mtmp_key_norms behind it (fp32).
+    keep=False: xn and stats (what only a backward reads) are neither allocated nor written, and come back as None."""
     _gpu(x2d, wqkv)
     M = x2d.shape[0]
     y = torch.empty(M, 3 * D_MODEL, dtype=x2d.dtype, device=x2d.device)
-    xn = torch.empty(M, D_MODEL, dtype=x2d.dtype, device=x2d.device)
-    stats = torch.empty(M, 2, dtype=torch.float32, device=x2d.device)
+    xn = torch.empty(M, D_MODEL, dtype=x2d.dtype, device=x2d.device) if keep else None
+    stats = torch.empty(M, 2, dtype=torch.float32, device=x2d.device) if keep else None
     knorm = torch.empty(_lib.lib().mtmp_key_norms_floats(M, N_HEAD), dtype=torch.float32, device=x2d.device)
     call("mtmp_ln_gemm_qkv", _dt(x2d), _p(x2d), _p(gamma), _p(beta), _p(wqkv), _p(bqkv), _p(y), _p(xn), _p(stats), _p(knorm),
          M, x2d.stride(0), LN_EPS, _stream())
@@ -944,17 +945,18 @@ def _uints(vs):
     return (ctypes.c_uint * len(vs))(*[int(v) & 0xFFFFFFFF for v in vs])
 
 
-def ln_gemm_qkv_grouped(xs, gammas, betas, ws, biases, packs=None):
-    """ln_gemm_qkv of a list of streams: lists -> lists (qkv, xn, stats, knorm)."""
+def ln_gemm_qkv_grouped(xs, gammas, betas, ws, biases, packs=None, keep=True):
+    """ln_gemm_qkv of a list of streams: lists -> lists (qkv, xn, stats, knorm).  keep=False: the entry gets NULL for xn and stats
+    (nothing is allocated or written for a backward that will not run) and their lists hold None."""
     _gpu(*xs)
     n, dt, dev = len(xs), xs[0].dtype, xs[0].device
     Ms, packs = [x.shape[0] for x in xs], _opt(packs, n)
     if dt != torch.bfloat16:
-        y, xn, st, kn = zip(*[ln_gemm_qkv(_live_rows(xs[i], packs[i]), gammas[i], betas[i], ws[i], biases[i]) for i in range(n)])
-        return [[_padded(t, M, pk) for t, M, pk in zip(ts, Ms, packs)] for ts in (y, xn, st)] + [list(kn)]
+        y, xn, st, kn = zip(*[ln_gemm_qkv(_live_rows(xs[i], packs[i]), gammas[i], betas[i], ws[i], biases[i], keep) for i in range(n)])
+        return [[None if t is None else _padded(t, M, pk) for t, M, pk in zip(ts, Ms, packs)] for ts in (y, xn, st)] + [list(kn)]
     y = [torch.empty(M, 3 * D_MODEL, dtype=dt, device=dev) for M in Ms]
-    xn = [torch.empty(M, D_MODEL, dtype=dt, device=dev) for M in Ms]
-    st = [torch.empty(M, 2, dtype=torch.float32, device=dev) for M in Ms]
+    xn = [torch.empty(M, D_MODEL, dtype=dt, device=dev) if keep else None for M in Ms]
+    st = [torch.empty(M, 2, dtype=torch.float32, device=dev) if keep else None for M in Ms]
     kn = [torch.empty(_lib.lib().mtmp_key_norms_floats(M, N_HEAD), dtype=torch.float32, device=dev) for M in Ms]
     call("mtmp_ln_gemm_qkv_grouped", _dt(xs[0]), n, _ptrs(xs), _ptrs(gammas), _ptrs(betas), _ptrs(ws), _ptrs(biases), _ptrs(y),
          _ptrs(xn), _ptrs(st), _ptrs(kn), _ints(Ms), _ints([x.stride(0) for x in xs]), LN_EPS, _lives(packs), _stream())
@@ -993,6 +995,33 @@ def gemm_nt_grouped(as_, ws, biases, ress, drop_p, seeds, packs=None):
          _ints([a.stride(0) for a in as_]), _ints([N] * n), _ints([0 if r is None else r.stride(0) for r in ress]), 0, float(drop_p),
          _uints(seeds), _p(_seed_word), _lives(packs), _stream())
     return y
+
+
+def ffn_block(x2d, gamma, beta, w1, c1, w2, c2):
+    """out[M,256] = x + relu(LN(x) w1^T + c1) w2^T + c2 in ONE launch that writes nothing else (csrc/ffn_infer.hip): the FFN half
+    of a layer for a forward nobody differentiates.  x2d: rows of 256 with any row stride that is a multiple of 8."""
+    _gpu(x2d, w1, w2)
+    M = x2d.shape[0]
+    out = torch.empty(M, D_MODEL, dtype=x2d.dtype, device=x2d.device)
+    call("mtmp_ffn_block", _dt(x2d), _p(x2d), x2d.stride(0), _p(gamma), _p(beta), _p(w1), _p(c1), _p(w2), _p(c2), _p(out), D_MODEL, M,
+         LN_EPS, _stream())
+    return out
+
+
+def ffn_block_grouped(xs, gammas, betas, w1s, c1s, w2s, c2s, packs=None):
+    """ffn_block of a list of streams: lists -> list of out."""
+    _gpu(*xs)
+    n, dt, dev = len(xs), xs[0].dtype, xs[0].device
+    Ms, packs = [x.shape[0] for x in xs], _opt(packs, n)
+    if dt != torch.bfloat16:
+        return [_padded(ffn_block(_live_rows(xs[i], packs[i]), gammas[i], betas[i], w1s[i], c1s[i], w2s[i], c2s[i]), Ms[i], packs[i])
+                for i in range(n)]
+    out = [torch.empty(M, D_MODEL, dtype=dt, device=dev) for M in Ms]
+    with kernel_marks("ffn_block", Ms[0]):
+        call("mtmp_ffn_block_grouped", _dt(xs[0]), n, _ptrs(xs), _ints([x.stride(0) for x in xs]), _ptrs(gammas), _ptrs(betas),
+             _ptrs(w1s), _ptrs(c1s), _ptrs(w2s), _ptrs(c2s), _ptrs(out), _ints([D_MODEL] * n), _ints(Ms), LN_EPS, _lives(packs),
+             _stream())
+    return out
 
 
 def gemm_nt_signs_drop_grouped(as_, ws, signs, gate_scale, drop_p, seeds, packs=None, gates=None):
@@ -2086,6 +2115,51 @@ LayerSaved = namedtuple("LayerSaved", "z kv_len g1 g2 wqkvt w1t w2t xn1 st1 qkv 
                                       "pack ffn_rows cls_rows cls_tok qk_mask", defaults=(None,) * 5)
 
 
+def _layer_attention(zs, kv_lens, Ps, fuseds, packs, ffn_rows, qk_masks, cls_tok, keep):
+    """The half of a layer that layer_forward and layer_infer share -- argument checks, the Q/K/V projection and the attention
+    step its mode selects (dense / packed / prefix-masked; the CLS row alone) -- up to r1 = z + o on the rows the FFN runs on.
+    keep: the projection also writes what the backward reads.  -> a namespace of per-stream lists."""
+    n = len(zs)
+    packs, qk_masks = _opt(packs, n), _opt(qk_masks, n)
+    B, D, R = zs[0].shape[0], D_MODEL, ffn_rows
+    Ns = [z.shape[1] for z in zs]
+    if (R is not None and (cls_tok is not None or any(pk is not None for pk in packs) or any(N < R for N in Ns))) or \
+            (cls_tok is not None and n != 1):
+        raise ValueError("ffn_rows: padded streams of at least that many rows; cls_tok: one stream")
+    rows = _row_limits(zs, packs)
+    par = lambda k: [P[k] for P in Ps]
+    f = FusedWeights._make(zip(*fuseds))               # every field: the list over the streams
+    qkv, xn1, st1, knorm = ln_gemm_qkv_grouped([z.view(B * N, D) for z, N in zip(zs, Ns)], par(P_G1), par(P_B1), f.wqkv, f.bqkv, rows,
+                                               keep=keep)
+    qkv = [q.view(B, N, 3 * D) for q, N in zip(qkv, Ns)]
+    # ---- attention, and r1 = z + o on the rows the FFN runs on
+    cls_rows = None
+    if cls_tok is not None:
+        o, r1, lse = ([t] for t in attn_cls_fwd(qkv[0], zs[0], kv_lens[0], packs[0], cls_tok))
+        rows = [None]
+        # the CLS rows of the stream buffer, for the backward's residual add: a packed stream's row starts AS THEY ARE (int32; the
+        # backward adds into the view that begins at row cls_tok -- `pack[:B].long() + cls_tok` was two launches in front of the head)
+        if keep:
+            cls_rows = packs[0][:B] if packs[0] is not None else _cls_rows(B, Ns[0], cls_tok, zs[0].device)
+    else:
+        o, r1, lse = attn_fwd_grouped(qkv, kv_lens, list(zs), knorm, packs, qk_masks)
+        r1 = [r.view(B * N, D) if R is None else r[:, :R].reshape(B * R, D) for r, N in zip(r1, Ns)]       # (R: a gathered copy)
+    return _LayerFront(n, B, Ns, packs, qk_masks, rows, par, f, qkv, xn1, st1, o, lse, r1, cls_rows)
+
+
+_LayerFront = namedtuple("_LayerFront", "n B Ns packs qk_masks rows par f qkv xn1 st1 o lse r1 cls_rows")
+
+
+def _ffn_rows_out(out, a, R, like):
+    """the [B, N, 256] outputs of a layer whose FFN ran on rows 0..R-1 of every sample: the other rows are zeros"""
+    # zeros, not empty: when this layer closes a graph segment these buffers become segment boundaries / outputs of the autograd
+    # node; nobody reads the other rows today, and a later reader (a dump, a NaN check) must not meet recycled memory
+    full = [torch.zeros(a.B, N, D_MODEL, dtype=like.dtype, device=like.device) for N in a.Ns]
+    for f_, o_ in zip(full, out):
+        f_[:, :R] = o_.view(a.B, R, D_MODEL)
+    return full
+
+
 def layer_forward(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ffn_rows=None, qk_masks=None, cls_tok=None):
     """One encoder layer on a list of streams (one entry per stream everywhere): zs [B,N_i,256] contiguous, kv_lens int32[B] | None,
     Ps the 14 parameters, fuseds FusedWeights (or its seven tensors in that order), seeds (FFN1, FFN2) -> (outs, LayerSaved records).
@@ -2097,43 +2171,68 @@ def layer_forward(zs, kv_lens, Ps, fuseds, drop_p, seeds, packs=None, ffn_rows=N
     qk_masks: None, or per stream None / the words of its prefix mask (attn_fwd).
     cls_tok = t: the last layer for a reader of row t of every sample only (one stream, padded or packed): the same idea with one
     row and the attention of that one query (attn_cls_fwd); the output is out_cls [B,256]."""
-    n = len(zs)
-    packs, qk_masks = _opt(packs, n), _opt(qk_masks, n)
-    B, D, R = zs[0].shape[0], D_MODEL, ffn_rows
-    Ns = [z.shape[1] for z in zs]
-    if (R is not None and (cls_tok is not None or any(pk is not None for pk in packs) or any(N < R for N in Ns))) or \
-            (cls_tok is not None and n != 1):
-        raise ValueError("ffn_rows: padded streams of at least that many rows; cls_tok: one stream")
-    rows = _row_limits(zs, packs)
-    par = lambda k: [P[k] for P in Ps]
-    f = FusedWeights._make(zip(*fuseds))               # every field: the list over the streams
-    qkv, xn1, st1, knorm = ln_gemm_qkv_grouped([z.view(B * N, D) for z, N in zip(zs, Ns)], par(P_G1), par(P_B1), f.wqkv, f.bqkv, rows)
-    qkv = [q.view(B, N, 3 * D) for q, N in zip(qkv, Ns)]
-    # ---- attention, and r1 = z + o on the rows the FFN runs on
-    cls_rows = None
-    if cls_tok is not None:
-        o, r1, lse = ([t] for t in attn_cls_fwd(qkv[0], zs[0], kv_lens[0], packs[0], cls_tok))
-        rows = [None]
-        # the CLS rows of the stream buffer, for the backward's residual add: a packed stream's row starts AS THEY ARE (int32; the
-        # backward adds into the view that begins at row cls_tok -- `pack[:B].long() + cls_tok` was two launches in front of the head)
-        cls_rows = packs[0][:B] if packs[0] is not None else _cls_rows(B, Ns[0], cls_tok, zs[0].device)
-    else:
-        o, r1, lse = attn_fwd_grouped(qkv, kv_lens, list(zs), knorm, packs, qk_masks)
-        r1 = [r.view(B * N, D) if R is None else r[:, :R].reshape(B * R, D) for r, N in zip(r1, Ns)]       # (R: a gathered copy)
+    a = _layer_attention(zs, kv_lens, Ps, fuseds, packs, ffn_rows, qk_masks, cls_tok, True)
+    n, B, Ns, D, R, f, par, r1 = a.n, a.B, a.Ns, D_MODEL, ffn_rows, a.f, a.par, a.r1
     # ---- FFN
-    h, xn2, st2, hsign = ln_gemm_signs_grouped(r1, par(P_G2), par(P_B2), f.w1, par(P_C1), 4 * D, drop_p, [sd[0] for sd in seeds], rows)
-    out = gemm_nt_grouped(h, f.w2, par(P_C2), r1, drop_p, [sd[1] for sd in seeds], rows)
+    h, xn2, st2, hsign = ln_gemm_signs_grouped(r1, par(P_G2), par(P_B2), f.w1, par(P_C1), 4 * D, drop_p, [sd[0] for sd in seeds], a.rows)
+    out = gemm_nt_grouped(h, f.w2, par(P_C2), r1, drop_p, [sd[1] for sd in seeds], a.rows)
     if R is not None:
-        # zeros, not empty: when this layer closes a graph segment these buffers become segment boundaries / outputs of the autograd
-        # node; nobody reads the other rows today, and a later reader (a dump, a NaN check) must not meet recycled memory
-        full = [torch.zeros(B, N, D, dtype=zs[0].dtype, device=zs[0].device) for N in Ns]
-        for f_, o_ in zip(full, out):
-            f_[:, :R] = o_.view(B, R, D)
-        out = full
-    saved = [LayerSaved(zs[i], kv_lens[i], Ps[i][P_G1], Ps[i][P_G2], f.wqkvt[i], f.w1t[i], f.w2t[i], xn1[i], st1[i], qkv[i], o[i], lse[i],
-                        r1[i], xn2[i], st2[i], h[i], drop_p, seeds[i], hsign[i], packs[i], R, cls_rows, cls_tok, qk_masks[i])
+        out = _ffn_rows_out(out, a, R, zs[0])
+    saved = [LayerSaved(zs[i], kv_lens[i], Ps[i][P_G1], Ps[i][P_G2], f.wqkvt[i], f.w1t[i], f.w2t[i], a.xn1[i], a.st1[i], a.qkv[i], a.o[i],
+                        a.lse[i], r1[i], xn2[i], st2[i], h[i], drop_p, seeds[i], hsign[i], a.packs[i], R, a.cls_rows, cls_tok,
+                        a.qk_masks[i])
              for i in range(n)]
     return (out if cls_tok is not None else [out[i].view(B, Ns[i], D) for i in range(n)]), saved
+
+
+def layer_infer(zs, kv_lens, Ps, fuseds, packs=None, ffn_rows=None, qk_masks=None, cls_tok=None):
+    """layer_forward for a forward that nobody differentiates: the same arguments without dropout and seeds, the same outputs in
+    every mode, and NO saved record -- nothing of the layer outlives the call but `outs`.  The Q/K/V projection writes neither the
+    normalised rows nor their statistics; the attention launches are layer_forward's (o and lse are written and dropped); the FFN
+    is ONE launch (ffn_block_grouped) that writes nothing but its output -- except for the few-row launches of cls_tok (B rows) and
+    ffn_rows (B * R rows) below tuning.FFN_BLOCK_MIN_ROWS, which keep layer_forward's two launches and drop what they return:
+    their outputs are then layer_forward's bit for bit."""
+    a = _layer_attention(zs, kv_lens, Ps, fuseds, packs, ffn_rows, qk_masks, cls_tok, False)
+    f, par, r1 = a.f, a.par, a.r1
+    few_rows = (cls_tok is not None or ffn_rows is not None) and sum(r.shape[0] for r in r1) < tuning.FFN_BLOCK_MIN_ROWS
+    if not few_rows:
+        out = ffn_block_grouped(r1, par(P_G2), par(P_B2), f.w1, par(P_C1), f.w2, par(P_C2), a.rows)
+    else:
+        h = ln_gemm_signs_grouped(r1, par(P_G2), par(P_B2), f.w1, par(P_C1), 4 * D_MODEL, 0.0, [0] * a.n, a.rows)[0]
+        out = gemm_nt_grouped(h, f.w2, par(P_C2), r1, 0.0, [0] * a.n, a.rows)
+    if ffn_rows is not None:
+        out = _ffn_rows_out(out, a, ffn_rows, zs[0])
+    return out if cls_tok is not None else [out[i].view(a.B, a.Ns[i], D_MODEL) for i in range(a.n)]
+
+
+# ---- the inference switch.  inference_forward(True) only ALLOWS the inference forward: a node takes it when, at call time, the flag
+# is set, autograd is off and no dropout is active (infer_active); otherwise everything runs as before, silently.
+_infer_forward = [False]
+
+
+@contextlib.contextmanager
+def inference_forward(enabled=True):
+    """Inside the context the encoders' forwards that run without grad mode and without dropout (validate(), the trainer's
+    no-grad flows, a prediction loop) walk their layers with layer_infer: no saved activations, the fused FFN block."""
+    prev, _infer_forward[0] = _infer_forward[0], bool(enabled)
+    try:
+        yield
+    finally:
+        _infer_forward[0] = prev
+
+
+def inference_forward_enabled() -> bool:
+    return _infer_forward[0]
+
+
+def infer_active(drop_p=0.0) -> bool:
+    """What the encoders put into StackPlan.infer / hand to EncoderLayerFn, read at call time: the flag is set, grad mode is off
+    and dropout is inactive (drop_p: the probability the call would run with, 0 outside training)."""
+    return _infer_forward[0] and not torch.is_grad_enabled() and not drop_p > 0.0
+
+
+def _infer_backward(*_):
+    raise RuntimeError("this node ran its forward with infer=True (ops.inference_forward): it kept nothing, there is no backward")
 
 
 class GradSink:
@@ -2284,19 +2383,29 @@ def layer_backward(saveds, d_outs, sinks=None):
 
 class EncoderLayerFn(torch.autograd.Function):
     """layer_forward / layer_backward as one autograd node (layer-level API and tests):
-    apply(z, kv_len, *the 14 parameters, fused, drop_p, seeds[, qk_mask])."""
+    apply(z, kv_len, *the 14 parameters, fused, drop_p, seeds[, qk_mask[, infer]]).  infer (ops.infer_active() at the call site:
+    grad mode cannot be read inside a node): the forward is layer_infer, keeps nothing, and there is no backward."""
 
     @staticmethod
     def forward(ctx, z, kv_len, *rest):
         _gpu(z)
         P, (fused, drop_p, seeds, *opt) = rest[:PARAMS_PER_LAYER], rest[PARAMS_PER_LAYER:]
-        (out,), ctx.saved = layer_forward([_c(z)], [kv_len], [P], [fused], drop_p, [seeds], qk_masks=[opt[0] if opt else None])
         ctx.n_opt = len(opt)
+        ctx.infer = len(opt) > 1 and bool(opt[1])
+        if ctx.infer:
+            if drop_p > 0:
+                raise ValueError("EncoderLayerFn: infer runs without dropout")
+            (out,) = layer_infer([_c(z)], [kv_len], [P], [fused], qk_masks=[opt[0]])
+            ctx.mark_non_differentiable(out)
+            return out
+        (out,), ctx.saved = layer_forward([_c(z)], [kv_len], [P], [fused], drop_p, [seeds], qk_masks=[opt[0] if opt else None])
         ctx.wshapes = (P[P_W1].shape, P[P_W2].shape)
         return out
 
     @staticmethod
     def backward(ctx, d_out):
+        if ctx.infer:
+            _infer_backward()
         (dz,), (g,) = layer_backward(ctx.saved, [_c(d_out).to(ctx.saved[0].z.dtype)])
         g = list(g)
         g[P_W1], g[P_W2] = g[P_W1].view(ctx.wshapes[0]), g[P_W2].view(ctx.wshapes[1])
@@ -2383,14 +2492,20 @@ class FusionStackFn(torch.autograd.Function):
             # inputs are still being made on the side streams (the vital-sign stream's first layer runs beside the image encoder)
             for gms in _each_group(launch_groups(step.streams, streams, z[0], solo=step.solo), cur):
                 mark(f"f{li}.g{gms[0]}.s")
-                go, gsaved = layer_forward([z[m] for m in gms], [plan.kv[m] for m in gms], [params[plan.block(li, m)] for m in gms],
-                                           [plan.fused[li][m] for m in gms], plan.drop_p, [plan.seeds[li][m] for m in gms],
-                                           [pack_v if m == 0 else None for m in gms],
-                                           ffn_rows=None if 0 in gms else step.ffn_rows, cls_tok=step.cls_tok)
+                largs = ([z[m] for m in gms], [plan.kv[m] for m in gms], [params[plan.block(li, m)] for m in gms],
+                         [plan.fused[li][m] for m in gms])
+                lmode = dict(packs=[pack_v if m == 0 else None for m in gms], ffn_rows=None if 0 in gms else step.ffn_rows,
+                             cls_tok=step.cls_tok)
+                if plan.infer:             # nothing is kept: a layer's inputs die when the next layer's outputs replace them
+                    go, gsaved = layer_infer(*largs, **lmode), [None] * len(gms)
+                else:
+                    go, gsaved = layer_forward(*largs, plan.drop_p, [plan.seeds[li][m] for m in gms], **lmode)
                 for i, m in enumerate(gms):
                     outs[m], row[m] = go[i], gsaved[i]
                 mark(f"f{li}.g{gms[0]}.e")
-            saved.append(row)
+                del largs
+            if not plan.infer:
+                saved.append(row)
             z = outs
             if step.exchange:              # (:764-779) on the [B,4,256] prefixes, written back in place (one kernel)
                 keep = torch.empty(B, NB, D_MODEL, dtype=torch.float32, device=dev) if plan.resbottle else None
@@ -2405,20 +2520,25 @@ class FusionStackFn(torch.autograd.Function):
         if step.cls_tok is not None:       # nothing but the CLS row exists of the last layer's output: placeholders (one fill, three views)
             ph = torch.zeros(1, NB + 1, D_MODEL, dtype=dt, device=dev)
             outs_full = [ph.expand(B, -1, -1) for _ in range(3)]
-            ctx.mark_non_differentiable(*outs_full)
+            ctx.mark_non_differentiable(*outs_full, *([outs[0]] if plan.infer else []))
             return outs_full[0], outs_full[1], outs_full[2], outs[0]
         outs_full = [z[m] if z[m] is not None else torch.zeros(B, Ns[m], D_MODEL, dtype=dt, device=dev) for m in range(3)]
-        ctx.mark_non_differentiable(*[o for m, o in enumerate(outs_full) if z[m] is None])
         if pack_v is not None:             # row pack_v[b] + NB of the packed buffer
             ctx.cls_rows = pack_v[:B].long() + NB
             cls_v = outs_full[0].view(-1, D_MODEL).index_select(0, ctx.cls_rows) if final else None
         else:
             cls_v = outs_full[0][:, NB, :].clone() if final else None
+        if plan.infer:
+            ctx.mark_non_differentiable(*outs_full, *([cls_v] if cls_v is not None else []))
+        else:
+            ctx.mark_non_differentiable(*[o for m, o in enumerate(outs_full) if z[m] is None])
         return outs_full[0], outs_full[1], outs_full[2], cls_v
 
     @staticmethod
     def backward(ctx, d_v, d_i, d_t, d_cls):
         plan, saved = ctx.plan, ctx.saved
+        if plan.infer:
+            _infer_backward()
         B, Ns, pshapes, dev = ctx.shapes
         dt, n_s, streams, pack_v = plan.dtype, plan.n_streams, plan.side_streams, plan.pack_v
         cur = torch.cuda.current_stream()
@@ -2547,10 +2667,14 @@ class MultiTokenStackFn(torch.autograd.Function):
         saved = []
         for li, step in enumerate(plan.schedule()):
             ms = step.streams
-            outs, sv = layer_forward([z[m] for m in ms], [plan.kv[m] for m in ms], [params[plan.block(li, m)] for m in ms],
-                                     [plan.fused[li][m] for m in ms], plan.drop_p, [plan.seeds[li][m] for m in ms],
-                                     qk_masks=[plan.masks[m] for m in ms])
-            saved.append(sv)
+            largs = ([z[m] for m in ms], [plan.kv[m] for m in ms], [params[plan.block(li, m)] for m in ms],
+                     [plan.fused[li][m] for m in ms])
+            if plan.infer:
+                outs = layer_infer(*largs, qk_masks=[plan.masks[m] for m in ms])
+            else:
+                outs, sv = layer_forward(*largs, plan.drop_p, [plan.seeds[li][m] for m in ms], qk_masks=[plan.masks[m] for m in ms])
+                saved.append(sv)
+            del largs
             z = [outs[ms.index(m)] if m in ms else None for m in range(3)]
             if step.exchange:
                 bottleneck_exchange_multi(z, plan.missing)
@@ -2558,12 +2682,14 @@ class MultiTokenStackFn(torch.autograd.Function):
         ctx.shapes = ([t.shape for t in (zv, zi, zt)], [p.shape for p in params], zv.dtype, zv.device)
         ctx.set_materialize_grads(False)
         outs = [t if t is not None else torch.zeros(shp, dtype=zv.dtype, device=zv.device) for t, shp in zip(z, ctx.shapes[0])]
-        ctx.mark_non_differentiable(*[o for o, t in zip(outs, z) if t is None])
+        ctx.mark_non_differentiable(*[o for o, t in zip(outs, z) if t is None or plan.infer])
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, d_v, d_i, d_t):
         plan, saved = ctx.plan, ctx.saved
+        if plan.infer:
+            _infer_backward()
         zshapes, pshapes, dt, dev = ctx.shapes
         steps = plan.schedule()
         pgrads = [None] * len(pshapes)

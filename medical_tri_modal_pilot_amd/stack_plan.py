@@ -60,8 +60,14 @@ class StackPlan:
     sinks: Optional[list] = None            # sinks[l][m]: a block's ops.GradSink | None; None: no gradient goes through a sink
     masks: Optional[list] = None            # multi-token stack: per stream the words of its prefix mask | None
     exchange_last: bool = True   # an exchange follows a last layer that ran every stream (the multi-token node: nothing reads it)
+    # the forward is one that nobody differentiates (ops.infer_active() at the call site): the node walks the same schedule with
+    # ops.layer_infer, keeps no saved record and no buffer beyond what the next exchange needs, marks its outputs
+    # non-differentiable, and its backward raises.  Off by default; never together with dropout
+    infer: bool = False
 
     def __post_init__(self):
+        if self.infer and self.drop_p > 0:
+            raise ValueError("infer: an inference forward runs without dropout (drop_p must be 0)")
         if not self.final and (not self.prebuilt or self.resbottle):
             raise ValueError("a non-final FusionStackFn segment needs prebuilt inputs and resbottle off")
         if self.pack_v is not None and not (self.prebuilt and self.dtype == torch.bfloat16 and self.kv[0] is not None):

@@ -48,3 +48,10 @@ HIP_HOURLY_EMBED = True
 # -> four means -> gather plus ie_demo.  Like HIP_HOURLY_EMBED, BOTH settings are run by the tests (tests/test_noshnoavgtr_gpu.py):
 # off is the torch chain the reference defines.  profiles/tri_head.txt.
 HIP_TRI_HEAD = True
+# ops.layer_infer: the few-row FFN launches of a CLS-only last layer (B rows) and of the exchange-only layer in front of it (B * R
+# rows) keep the training forward's two launches (mtmp_ln_gemm_signs + mtmp_gemm_nt) below this many rows instead of the fused
+# mtmp_ffn_block: one workgroup of the fused kernel streams the whole megabyte of W1 and W2 for its 128 rows (42-44 us alone),
+# the chain's kernels split the weights over many workgroups (34-35 us for both launches at 64 .. 3712 rows).  The fused launch
+# reaches the chain only at 64 640 rows (115 against 117 us) and is slower at every smaller size measured (8768 rows: 47 against
+# 39 us), so the bound is set above all of them.  tools/bench_kernels.py --only ffn_block; profiles/infer_forward.txt.
+FFN_BLOCK_MIN_ROWS = 16384

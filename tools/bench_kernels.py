@@ -343,6 +343,46 @@ def main():
         x = R(64, 56, 56, 96)
         w, b = torch.ones(96, device=DEV), torch.zeros(96, device=DEV)
         rec("ln_rows[200704,96]", timeit(lambda: ops.layernorm_rows(x, w, b), a.rounds), bytes_=2.0 * x.numel() * 2)
+    # ---- the fused FFN block of the inference forward against the training forward's chain (ln_gemm_signs + gemm_nt): both forms
+    # in this process, warm, alternating window by window; median with min and max.  Small row counts get more calls per window
+    ffn_table = ""
+    if want("ffn_block"):
+        gm, bt = torch.ones(256, device=DEV), torch.zeros(256, device=DEV)
+        w1, w2 = R(1024, 256) * 0.08, R(256, 1024) * 0.03
+        c1, c2 = torch.randn(1024, generator=g, device=DEV) * 0.3, torch.randn(256, generator=g, device=DEV) * 0.3
+        ffn_table = ("# mtmp_ffn_block against mtmp_ln_gemm_signs + mtmp_gemm_nt, bf16, us per call, one process, warm, forms alternating,\n"
+                     "# median (min .. max) over %d windows\n# M        fused                      chain                      chain / fused\n"
+                     % max(a.rounds, 7))
+        for m in (64 * 1010, 64 * 137, 64 * 58, 1024, 512, 256, 64):
+            x = (R(m, 256) + 0.3) * 2
+            inner = 5 if m > 4096 else 40
+
+            def chain():
+                h = ops.ln_gemm_signs_grouped([x], [gm], [bt], [w1], [c1], 1024, 0.0, [0])[0]
+                return ops.gemm_nt_grouped(h, [w2], [c2], [x], 0.0, [0])
+
+            def fused():
+                return ops.ffn_block_grouped([x], [gm], [bt], [w1], [c1], [w2], [c2])
+
+            for _ in range(3):
+                fused()
+                chain()
+            ts = ([], [])
+            for _ in range(max(a.rounds, 7)):
+                for i, fn in enumerate((fused, chain)):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(inner):
+                        fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ts[i].append(1e3 * e0.elapsed_time(e1) / inner)
+            med = [sorted(t)[len(t) // 2] for t in ts]
+            rec(f"ffn_block[{m}].fused", med[0] / 1e3, 2.0 * m * 2 * 256 * 1024)
+            rec(f"ffn_block[{m}].chain", med[1] / 1e3, 2.0 * m * 2 * 256 * 1024)
+            ffn_table += "%-8d %8.1f (%6.1f .. %6.1f)  %8.1f (%6.1f .. %6.1f)  %.2f\n" % (
+                m, med[0], min(ts[0]), max(ts[0]), med[1], min(ts[1]), max(ts[1]), med[1] / med[0])
+        print(ffn_table, flush=True)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "bench_kernels.json"), "w") as fh:
         json.dump(out, fh, indent=1)
@@ -352,6 +392,9 @@ def main():
     if cxr_table:
         with open(os.path.join(os.path.dirname(fh.name), "cxr_input_pipeline_table.txt"), "w") as ft:
             ft.write(cxr_table)
+    if ffn_table:
+        with open(os.path.join(os.path.dirname(fh.name), "ffn_block_table.txt"), "w") as ft:
+            ft.write(ffn_table)
     if table:                        # the encoder-width table, next to the JSON
         with open(os.path.join(os.path.dirname(fh.name), "gemm_tn_encoder_widths.txt"), "w") as ft:
             ft.write(table)

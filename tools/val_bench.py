@@ -1,6 +1,7 @@
 """Times of the validation pass on one MI355X: the figures of profiles/validation_pass.txt.
 
     python tools/val_bench.py [--windows 7] [--window-s 1.0] [--workloads full,ragged] [--out FILE]
+    python tools/val_bench.py --infer-forward 0,1 [...]      validate() replayed under --infer-forward 0 and 1 (below)
 
 At the benchmark's shape (bench.py WORKLOADS: batch 64, TIE-len 1000, 6 layers, bf16; `full` and `ragged`), in ONE process and
 alternating, (a) the existing loop -- ``get_trainer(flow_type="test")`` per batch (eager launches, ``loss.item()`` per batch)
@@ -9,7 +10,13 @@ with ``Evaluator`` -- and (b) ``validate()`` with ``--hip-graph 1`` and ``Device
 lasts at least ``--window-s``; it ends with the pass's metrics (``performance_metric()`` / ``validate``'s own 64-byte copy) and a
 device synchronise, so the ms per batch include 1/K of that.  Reported: median and min .. max over the windows.
 Then ``performance_metric()`` alone at 1e5 and 1e6 stored predictions for both evaluators (Evaluator: a list of batches of 64,
-as the loop leaves it; DeviceEvaluator: the same values in its buffers).  Needs a GPU; no fallback."""
+as the loop leaves it; DeviceEvaluator: the same values in its buffers).
+
+``--infer-forward 0,1`` replaces all of that by ONE comparison: ``validate()`` with ``--hip-graph 1`` under each listed setting of
+``--infer-forward``, in one process on one box, windows alternating between the settings (a model of its own per setting: a flip
+on one model would capture afresh every window).  Reported per workload and setting: ms per validation batch, replayed (median,
+min .. max), and ``torch.cuda.max_memory_allocated`` of one pass of 4 batches above what was allocated before it.
+Needs a GPU; no fallback."""
 import argparse
 import math
 import os
@@ -33,6 +40,7 @@ def main():
     ap.add_argument("--workloads", default="full,ragged")
     ap.add_argument("--metric-reps", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--infer-forward", default=None, help="e.g. 0,1: compare validate() under these settings instead")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("val_bench: needs an MI355X (no CPU fallback)")
@@ -47,6 +55,10 @@ def main():
     say = Lines()
 
     say(f"validation pass on {torch.cuda.get_device_name(0)}: windows of >= {a.window_s} s, {a.windows} per variant, alternating")
+    if a.infer_forward is not None:
+        infer_compare(a, say, dev)
+        say.write(a.out)
+        return
     for wl in a.workloads.split(","):
         B, T, L, multi, n_img, ragged, miss_mode, _ = bench.WORKLOADS[wl]
         args = bench.make_args(wl, "bf16", 0.1, 1, 0, False)
@@ -141,6 +153,65 @@ def main():
             m, lo, hi = stats(tm[name])
             say(f"  {name:16s}: {m:9.3f} ms (min {lo:.3f} .. max {hi:.3f}) -> {[float(v) for v in res[name]]}")
     say.write(a.out)
+
+
+def infer_compare(a, say, dev):
+    import copy
+    import bench
+    from medical_tri_modal_pilot_amd import synthetic
+    from medical_tri_modal_pilot_amd.builder.trainer import validate
+    from medical_tri_modal_pilot_amd.builder.utils.device_evaluator import DeviceEvaluator
+    from medical_tri_modal_pilot_amd.train import build_training
+    settings = [int(v) for v in a.infer_forward.split(",")]
+    for wl in a.workloads.split(","):
+        B, T, L, multi, n_img, ragged, miss_mode, _ = bench.WORKLOADS[wl]
+        bt = synthetic.make_batch(1234, B, T, ragged=ragged, missing_mode=miss_mode, multiimages=multi, n_images=n_img)
+        d = {k: v.to(dev) for k, v in bt.items() if k != "missing"}
+        static = torch.stack([d["gen"], d["age"]], 1)
+        batch = (d["x"], static, d["y"], bt["input_lengths"], d["img"], d["img_time"], d["txt"], d["txt_lengths"], d["txt_time"],
+                 bt["missing"], None, None)
+        runs = {}
+        for s in settings:
+            args = copy.copy(bench.make_args(wl, "bf16", 0.1, 1, 0, False))
+            args.infer_forward = s
+            torch.manual_seed(412)
+            model, _opt, crit = build_training(args, dev, False)
+            model.train()
+            runs[s] = (args, model, crit, DeviceEvaluator(args, dev, 4096 * B))
+
+        def run_pass(s, k):
+            args, model, crit, ev = runs[s]
+            return validate(args, model, (batch for _ in range(k)), dev, crit, ev)["loss"]
+
+        peak, ks, loss = {}, {}, {}
+        for s in settings:
+            run_pass(s, 4)                                   # warm-up step and capture
+            torch.cuda.synchronize()
+            base = torch.cuda.memory_allocated()
+            torch.cuda.reset_peak_memory_stats()
+            run_pass(s, 4)
+            torch.cuda.synchronize()
+            peak[s] = (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+            ms = wall_ms(lambda: run_pass(s, 8)) / 8
+            ks[s] = max(8, math.ceil(a.window_s * 1e3 * 1.15 / ms))
+        times = {s: [] for s in settings}
+        for _ in range(a.windows):
+            for s in settings:
+                out = []
+                times[s].append(wall_ms(lambda: out.append(run_pass(s, ks[s]))) / ks[s])
+                loss[s] = out[0]
+        say(f"[{wl}] batch {B}, TIE-len {T}, {L} layers, bf16, lengths {'ragged' if ragged else 'full'}, missing {miss_mode}; "
+            f"validate() --hip-graph 1, replayed")
+        for s in settings:
+            m, lo, hi = stats(times[s])
+            gs = runs[s][1]._mtmp_graph_eval.stats()
+            say(f"  --infer-forward {s}: {m:8.3f} ms / batch (min {lo:.3f} .. max {hi:.3f}, {ks[s]} batches a window); peak memory of "
+                f"a pass above its start {peak[s]:9.1f} MiB; mean loss {loss[s]:.6f}; {gs['captures']} captures, {gs['replays']} replays")
+        if len(settings) == 2:
+            m0, m1 = stats(times[settings[0]])[0], stats(times[settings[1]])[0]
+            say(f"  ratio {settings[0]} / {settings[1]}: {m0 / m1:.3f}")
+        del runs
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":
