@@ -27,6 +27,10 @@ extern "C" {
 #define MTMP_F32 0
 #define MTMP_BF16 1
 
+/* What mtmp_abi_version() returns.  This header is the one place the interface is written down: the library's sources are
+ * compiled against it, and the Python binding reads its argument types from it. */
+#define MTMP_ABI_VERSION 6
+
 int mtmp_abi_version(void);
 const char* mtmp_last_error(void);
 

@@ -20,6 +20,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+// The public declarations: every extern "C" definition in a .hip is compiled against its declaration, so a parameter list that
+// differs from include/mtmp.h is a compile error (a C-linkage function cannot be overloaded).
+#include "../../include/mtmp.h"
 
 typedef __bf16 bf16;
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));

@@ -2,6 +2,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include "../../include/mtmp.h"
+
 static thread_local char g_err[512] = "";
 
 void mtmp_set_error(const char* fmt, ...) {
@@ -12,4 +14,4 @@ void mtmp_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* mtmp_last_error(void) { return g_err; }
-extern "C" int mtmp_abi_version(void) { return 6; }
+extern "C" int mtmp_abi_version(void) { return MTMP_ABI_VERSION; }

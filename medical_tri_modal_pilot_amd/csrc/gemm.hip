@@ -1992,7 +1992,6 @@ extern "C" int mtmp_ln_gemm(int dtype, const void* x, const float* gamma, const 
 // writes the key-norm table of the attention forward's bounded body: key_norms[ceil(M / 32)][4] = max ||k_h|| per block of 32
 // token rows (mtmp_key_norms_floats(M, 4) floats).  bf16: from the projection's epilogue, no extra pass; fp32: the projection
 // followed by mtmp_key_norms (the parity build keeps the round-1 row-panel kernel).
-extern "C" int mtmp_key_norms(int dtype, const void* k, float* out, long long rows, int H, int ld, void* stream);
 extern "C" int mtmp_ln_gemm_qkv(int dtype, const void* x, const float* gamma, const float* beta, const void* w, const float* bias,
                                 void* y, void* xn, float* stats, float* key_norms, int M, int ldx, float eps, void* stream) {
     const char* who = "mtmp_ln_gemm_qkv";

@@ -4,7 +4,6 @@ the same files, the one-span-per-subsequence decode from the model's sync rows, 
 collate_raw_cxr fed handles against the same call fed the files' bytes.  All comparisons are exact."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import torch
 from medical_tri_modal_pilot_amd.builder.data import cxr_store as CS
 from medical_tri_modal_pilot_amd.builder.data import cxr_transform as CT
 from medical_tri_modal_pilot_amd.builder.data import jpeg as J
+from tests import abi
 from tests import cxr_store_model as M
 from tests import jpeg_cases
 
@@ -189,17 +189,13 @@ def test_collate_mixes_arrays_file_bytes_and_handles():
 def test_new_entry_points_declared_listed_and_exported():
     from medical_tri_modal_pilot_amd import _lib
     from medical_tri_modal_pilot_amd.builder import data
-    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
+    hdr = abi.header_text()
     L = _lib.lib()
     for name, nargs in (("mtmp_jpeg_sync_points", 12), ("mtmp_jpeg_store_entropy", 15)):
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
-        assert m, f"{name} is not declared in include/mtmp.h"
-        args = [a.strip() for a in m.group(1).split(",")]
+        ret, args = abi.declaration(name)
         restype, argtypes = _lib.SIGNATURES[name]
-        assert restype is ctypes.c_int and len(args) == len(argtypes) == nargs
-        for decl, ct in zip(args, argtypes):
-            want = ctypes.c_void_p if "*" in decl else ctypes.c_longlong if decl.startswith("long long") else ctypes.c_int
-            assert ct is want, (name, decl, ct)
+        assert ret == "int" and restype is ctypes.c_int and len(args) == len(argtypes) == nargs
+        assert (restype, argtypes) == abi.ctypes_of(name)
         assert getattr(L, name)
     assert "int32 [n_sync][4]" in hdr and "int64 [n][2]" in hdr
     L.mtmp_abi_version.restype = ctypes.c_int

@@ -114,16 +114,13 @@ NAMES = ("mtmp_eval_append", "mtmp_eval_sort_tile", "mtmp_eval_workspace_bytes",
 
 def test_new_entry_points_declared_listed_and_exported():
     from medical_tri_modal_pilot_amd import _lib, ops
-    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
+    from tests import abi
     for name in NAMES:
-        m = re.search(r"\b(int|long long)\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
-        assert m, f"{name} is not declared in include/mtmp.h"
-        args = [a.strip() for a in m.group(2).split(",") if a.strip() != "void"]
+        ret, args = abi.declaration(name)
         restype, argtypes = _lib.SIGNATURES[name]
-        assert restype is (ctypes.c_int if m.group(1) == "int" else ctypes.c_longlong) and len(args) == len(argtypes)
-        for decl, ct in zip(args, argtypes):
-            want = ctypes.c_void_p if "*" in decl else ctypes.c_longlong if decl.startswith("long long") else ctypes.c_int
-            assert ct is want, (name, decl, ct)
+        assert ret in ("int", "long long")
+        assert restype is (ctypes.c_int if ret == "int" else ctypes.c_longlong) and len(args) == len(argtypes)
+        assert (restype, argtypes) == abi.ctypes_of(name)
     L = _lib.lib()
     assert all(getattr(L, n) for n in NAMES) and L.mtmp_abi_version() == 6
     assert L.mtmp_eval_sort_tile() == ops.EVAL_SORT_TILE and ops.EVAL_SORT_TILE % 256 == 0

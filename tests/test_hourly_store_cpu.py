@@ -3,8 +3,6 @@
 byte for byte against plane 0, the refusals, ``keep_mask``, ``plan`` unchanged by the shared trimming helper, the synthetic
 batches, and the new entry points' declarations and argument errors (the library loads without a GPU)."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,10 +10,10 @@ import torch
 
 from medical_tri_modal_pilot_amd.builder.data import (HourlyWindowBatch, StoreWindowDataset, TieWindowBatch, collate_hourly_windows,
                                                        keep_mask)
+from tests import abi
 from tests import hourly_store_model as H
 from tests import tie_store_model as M
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mtmp_hourly_window_gather", "mtmp_hourly_embed_fwd", "mtmp_hourly_embed_bwd_ws_floats", "mtmp_hourly_embed_bwd")
 
 
@@ -137,17 +135,12 @@ def test_synthetic_carryforward_batches():
 
 def test_new_entry_points_declared_listed_and_exported():
     from medical_tri_modal_pilot_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
+    hdr = abi.header_text()
     for name in NEW:
-        m = re.search(r"\bint\s+%s\s*\(([^;]*?)\)\s*;" % name, hdr, re.S)
-        assert m, f"{name} is not declared in include/mtmp.h"
-        args = [a.strip() for a in m.group(1).split(",")]
+        ret, args = abi.declaration(name)
         restype, argtypes = _lib.SIGNATURES[name]
-        assert restype is ctypes.c_int and len(args) == len(argtypes)
-        for decl, ct in zip(args, argtypes):
-            want = (ctypes.c_void_p if "*" in decl else ctypes.c_longlong if decl.startswith("long long")
-                    else ctypes.c_uint if decl.startswith("unsigned") else ctypes.c_int)
-            assert ct is want, (name, decl, ct)
+        assert ret == "int" and restype is ctypes.c_int and len(args) == len(argtypes)
+        assert (restype, argtypes) == abi.ctypes_of(name)
     L = _lib.lib()
     assert all(getattr(L, n) for n in NEW) and L.mtmp_abi_version() == 6
     assert "additive; ABI stays 6" in hdr[hdr.index("hourly carry-forward windows") - 10:hdr.index("mtmp_hourly_window_gather")]

@@ -2,8 +2,6 @@
 own decodes (tests/golden/jpeg_cases.npz): the parser on every case and on what it must refuse, the model for every
 subsequence length, a truncated stream, and collate_raw_cxr with file bytes in the batch."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
@@ -13,7 +11,6 @@ from medical_tri_modal_pilot_amd.builder.data import cxr_transform as CT
 from medical_tri_modal_pilot_amd.builder.data import jpeg as J
 from tests import jpeg_cases, jpeg_model
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STD_DC = (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0)                 # Annex K.3, luminance
 STD_AC = (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125)
 # restart interval, segments
@@ -162,16 +159,15 @@ def test_collate_of_arrays_is_unchanged():
 
 def test_new_entry_points_declared_listed_and_exported():
     from medical_tri_modal_pilot_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
+    from tests import abi
+    hdr = abi.header_text()
     L = _lib.lib()
     for name, nargs in (("mtmp_jpeg_entropy", 12), ("mtmp_jpeg_idct", 8)):
-        m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", hdr, re.S)
-        assert m, f"{name} is not declared in include/mtmp.h"
-        args = [a.strip() for a in m.group(1).split(",")]
+        ret, args = abi.declaration(name)
         restype, argtypes = _lib.SIGNATURES[name]
-        assert restype is ctypes.c_int and len(args) == len(argtypes) == nargs
-        for decl, ct in zip(args, argtypes):
-            assert ct is (ctypes.c_void_p if "*" in decl else ctypes.c_int), (name, decl, ct)
+        assert ret == "int" and restype is ctypes.c_int and len(args) == len(argtypes) == nargs
+        assert (restype, argtypes) == abi.ctypes_of(name)
+        assert set(argtypes) == {ctypes.c_void_p, ctypes.c_int}
         assert getattr(L, name)
     assert "int32 [n][16]" in hdr and str(J.HUFF_WORDS) in hdr and J.JPG_WORDS == 16
     L.mtmp_abi_version.restype = ctypes.c_int

@@ -1,5 +1,6 @@
-"""include/mtmp.h is the public C interface: it must compile on its own for a C and a C++ consumer (nothing in the package
-includes it -- the kernels do not, and the ABI tests read it as text -- so only a compiler notices a broken guard or type)."""
+"""include/mtmp.h is the public C interface: it must compile on its own for a C and a C++ consumer (the library's sources
+include it behind the HIP runtime's headers and as C++ only, and the binding and the ABI tests read it as text -- so only this
+notices a type that needs another header, or something a C compiler refuses)."""
 import os
 import shutil
 import subprocess

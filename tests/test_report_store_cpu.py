@@ -151,15 +151,12 @@ def test_synthetic_report_store():
 def test_new_entry_point_declared_listed_and_exported():
     from medical_tri_modal_pilot_amd import _lib
     from medical_tri_modal_pilot_amd.builder.data import report_store as RS
-    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
-    m = re.search(r"\bint\s+mtmp_report_gather\s*\(([^;]*?)\)\s*;", hdr, re.S)
-    assert m, "mtmp_report_gather is not declared in include/mtmp.h"
-    args = [a.strip() for a in m.group(1).split(",")]
+    from tests import abi
+    hdr = abi.header_text()
+    ret, args = abi.declaration("mtmp_report_gather")
     restype, argtypes = _lib.SIGNATURES["mtmp_report_gather"]
-    assert restype is ctypes.c_int and len(args) == len(argtypes) == 10
-    for decl, ct in zip(args, argtypes):
-        want = ctypes.c_void_p if "*" in decl else ctypes.c_longlong if decl.startswith("long long") else ctypes.c_int
-        assert ct is want, (decl, ct)
+    assert ret == "int" and restype is ctypes.c_int and len(args) == len(argtypes) == 10
+    assert (restype, argtypes) == abi.ctypes_of("mtmp_report_gather")
     L = _lib.lib()
     assert L.mtmp_report_gather and L.mtmp_abi_version() == 6
     assert "int64 [B][2]" in hdr and RS.DESC_WORDS == 2

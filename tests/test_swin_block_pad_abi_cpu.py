@@ -4,17 +4,12 @@ build makes, reachable through ops and SwinTransformerBlock -- and the ABI versi
 import ctypes
 import inspect
 import os
-import re
+
+from tests import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "medical_tri_modal_pilot_amd", "libmtmp_hip.so")
 NAME = "mtmp_swin_attn_block_pad"
-
-
-def _declaration(hdr, name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, f"{name} is not declared in include/mtmp.h"
-    return [re.sub(r"\s+", " ", a.strip()) for a in m.group(1).split(",")]
 
 
 def _library():
@@ -26,17 +21,15 @@ def _library():
 
 def test_block_pad_entry_declared_listed_and_exported():
     lib = _library()
-    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
-    args = _declaration(hdr, NAME)
-    assert args == _declaration(hdr, "mtmp_swin_attn_block"), args          # the signature of the window-multiple entry
-    assert len(args) == 21 and args[0] == "int dtype" and args[-2] == "const int32_t* rows_live" and args[-1] == "void* stream"
+    ret, args = abi.declaration(NAME)
+    assert (ret, args) == abi.declaration("mtmp_swin_attn_block"), args     # the signature of the window-multiple entry
+    assert ret == "int" and len(args) == 21
+    assert args[0] == "int dtype" and args[-2] == "const int32_t* rows_live" and args[-1] == "void* stream"
     from medical_tri_modal_pilot_amd import _lib
     assert NAME in _lib.SIGNATURES, f"{NAME} missing from _lib.SIGNATURES"
     restype, argtypes = _lib.SIGNATURES[NAME]
     assert restype is ctypes.c_int and len(argtypes) == len(args)
-    for decl, ct in zip(args, argtypes):             # pointers <-> c_void_p, int <-> c_int, float <-> c_float, position by position
-        want = ctypes.c_void_p if "*" in decl else ctypes.c_float if decl.startswith("float") else ctypes.c_int
-        assert ct is want, (decl, ct)
+    assert (restype, argtypes) == abi.ctypes_of(NAME)                       # position by position
     assert (restype, argtypes) == _lib.SIGNATURES["mtmp_swin_attn_block"]
     assert hasattr(lib, NAME), f"{NAME} declared in include/mtmp.h but not exported"
     assert hasattr(lib, "mtmp_swin_attn_block")

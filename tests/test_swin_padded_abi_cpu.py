@@ -4,19 +4,14 @@ and reachable through ops and ShiftedWindowAttention.  No kernel is launched her
 import ctypes
 import inspect
 import os
-import re
 
 import pytest
+
+from tests import abi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "medical_tri_modal_pilot_amd", "libmtmp_hip.so")
 ENTRIES = {"mtmp_swin_window_attn_pad": 14, "mtmp_swin_window_attn_pad_bwd": 16}
-
-
-def _declaration(hdr, name):
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^)]*)\)\s*;", hdr)
-    assert m, f"{name} is not declared in include/mtmp.h"
-    return [a.strip() for a in m.group(1).split(",")]
 
 
 @pytest.mark.parametrize("name", sorted(ENTRIES))
@@ -24,27 +19,22 @@ def test_padded_window_entries_declared_listed_and_exported(name):
     if not os.path.exists(LIB):
         import __graft_entry__ as ge
         ge.build()
-    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
-    args = _declaration(hdr, name)
-    assert len(args) == ENTRIES[name], args
+    ret, args = abi.declaration(name)
+    assert ret == "int" and len(args) == ENTRIES[name], args
     assert args[0] == "int dtype" and args[2] == "const float* qkv_bias" and args[-1] == "void* stream"
     from medical_tri_modal_pilot_amd import _lib
     assert name in _lib.SIGNATURES, f"{name} missing from _lib.SIGNATURES"
     restype, argtypes = _lib.SIGNATURES[name]
     assert restype is ctypes.c_int and len(argtypes) == len(args)
-    # pointers <-> c_void_p, int <-> c_int, float <-> c_float, position by position
-    for decl, ct in zip(args, argtypes):
-        want = ctypes.c_void_p if "*" in decl else ctypes.c_float if decl.startswith("float") else ctypes.c_int
-        assert ct is want, (name, decl, ct)
+    assert (restype, argtypes) == abi.ctypes_of(name)          # position by position
     lib = ctypes.CDLL(LIB)                       # loads without a GPU: HIP initialises lazily
     assert hasattr(lib, name), f"{name} declared in include/mtmp.h but not exported"
 
 
 def test_existing_window_entries_keep_their_signatures():
-    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
-    assert len(_declaration(hdr, "mtmp_swin_window_attn")) == 12
-    assert len(_declaration(hdr, "mtmp_swin_window_attn_live")) == 13
-    assert len(_declaration(hdr, "mtmp_swin_window_attn_bwd")) == 14
+    assert len(abi.declaration("mtmp_swin_window_attn")[1]) == 12
+    assert len(abi.declaration("mtmp_swin_window_attn_live")[1]) == 13
+    assert len(abi.declaration("mtmp_swin_window_attn_bwd")[1]) == 14
 
 
 def test_host_side_reaches_the_padded_entries():

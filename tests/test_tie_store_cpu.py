@@ -165,15 +165,12 @@ def test_store_refuses_non_finite_event_times_and_odd_feature_indices():
 
 def test_new_entry_point_declared_listed_and_exported():
     from medical_tri_modal_pilot_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "mtmp.h")).read()
-    m = re.search(r"\bint\s+mtmp_tie_window_gather\s*\(([^;]*?)\)\s*;", hdr, re.S)
-    assert m, "mtmp_tie_window_gather is not declared in include/mtmp.h"
-    args = [a.strip() for a in m.group(1).split(",")]
+    from tests import abi
+    hdr = abi.header_text()
+    ret, args = abi.declaration("mtmp_tie_window_gather")
     restype, argtypes = _lib.SIGNATURES["mtmp_tie_window_gather"]
-    assert restype is ctypes.c_int and len(args) == len(argtypes) == 20
-    for decl, ct in zip(args, argtypes):
-        want = ctypes.c_void_p if "*" in decl else ctypes.c_longlong if decl.startswith("long long") else ctypes.c_int
-        assert ct is want, (decl, ct)
+    assert ret == "int" and restype is ctypes.c_int and len(args) == len(argtypes) == 20
+    assert (restype, argtypes) == abi.ctypes_of("mtmp_tie_window_gather")
     L = _lib.lib()
     assert L.mtmp_tie_window_gather and L.mtmp_abi_version() == 6
     from medical_tri_modal_pilot_amd.builder.data import tie_store as TS

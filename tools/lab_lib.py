@@ -22,6 +22,8 @@ def build():
     variants = dict(VARIANTS)
     variants.setdefault("base", [])
     procs = []
+    os.makedirs(os.path.join(LAB, "include"), exist_ok=True)            # the copies' ../../include/mtmp.h (common.hip.h, Makefile)
+    shutil.copy(os.path.join(ROOT, "include", "mtmp.h"), os.path.join(LAB, "include"))
     for name, reps in variants.items():
         d = os.path.join(LAB, name, "csrc")
         shutil.rmtree(os.path.join(LAB, name), ignore_errors=True)
