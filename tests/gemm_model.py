@@ -42,6 +42,11 @@ purpose -- read from gemm.hip, not fitted to what the kernels return:
     B1  dxn = T(dy Wt^T): the finished tile is parked in LDS as the compute type before the LayerNorm backward reads it; dz, dgamma
         and dbeta all come from that rounded tile, in fp32, with the VALUES of `stats` (row_kernels_model.ln_bwd_model)
   gemm_tn: no rounding point (fp32 accumulators, fp32 slabs).
+  dropout (keep = tests/dropout_model.Keep: the replayed mask and the one fp32 value keep_scale; None = off, nothing changes)
+    D1  epilogues of ln_gemm and gemm_nt: v = act(acc + bias) in fp32, then keep ? v * keep_scale : 0, then the rounding of the store
+        / of the parked tile (N1), then gate, row scale and residual as above.  The sign bits are "positive and kept"
+    D2  dropout_bwd_kernel and the operand drop of the gated dH launch: T(float32(g) * keep_scale) or 0 -- one fp32 product and one
+        rounding, both reproduced exactly (dropout_bwd_model); the product of the dH launch takes that ROUNDED operand
 
 The final store of an output to bf16 is NOT part of the chain: that is the 2^-8 of the bound.
 No element is left out of any check: ReLU and GELU are continuous, and the one discontinuous step -- the gate of dH -- takes the
@@ -96,6 +101,17 @@ def gelu_model(x, dt, ft):
     return 0.5 * x * (1.0 + torch.erf(x * (1.0 / math.sqrt(2.0))))
 
 
+def _drop(v, keep, fault=None):
+    """D1 on an fp32 / float64 tensor; fault (tests/dropout_model.MODEL_FAULTS): "no_scale", or "scale_after_round" = the value is
+    rounded to bf16 BEFORE the scale"""
+    if keep is None:
+        return v
+    if fault == "scale_after_round":
+        v = v.to(BF16).to(v.dtype)
+    kept = v if fault == "no_scale" else v * keep.scale
+    return torch.where(keep.mask.to(v.device), kept, torch.zeros_like(v))
+
+
 def _act(v, act, dt, ft):
     if act == "relu":
         return torch.relu(v)
@@ -115,8 +131,9 @@ def knorm_model(y):
     return torch.cat([nrm, pad]).reshape(nblk, 32, 4).max(1).values
 
 
-def ln_gemm_model(x, gamma, beta, w, bias, act=None, *, dt, ft):
-    """module.py:138-144 (unbiased std, eps added to the std) in front of y = act(xn W^T + b): x [M,256], w [N,256], bias [N] | None.
+def ln_gemm_model(x, gamma, beta, w, bias, act=None, keep=None, fault=None, *, dt, ft):
+    """module.py:138-144 (unbiased std, eps added to the std) in front of y = drop(act(xn W^T + b)): x [M,256], w [N,256], bias [N] |
+    None, keep: the dropout of D1 over the [M,N] output.
     -> y, xn, mean, rstd (the two columns of `stats`), and for N = 768 the key-norm table knorm."""
     r = _rounder(dt, ft)
     xf = x.to(ft)
@@ -125,7 +142,7 @@ def ln_gemm_model(x, gamma, beta, w, bias, act=None, *, dt, ft):
     rs = 1.0 / ((d * d).sum(-1, keepdim=True) / (D - 1)).sqrt().add(LN_EPS)                                   # L1
     xn = gamma.to(ft) * (d * rs) + beta.to(ft)                                                                # L2
     v = _mm(r(xn), w, bias, dt, ft)                                                                           # P1, P2
-    out = dict(y=_act(v, act, dt, ft), xn=xn, mean=mean[:, 0], rstd=rs[:, 0])
+    out = dict(y=_drop(_act(v, act, dt, ft), keep, fault), xn=xn, mean=mean[:, 0], rstd=rs[:, 0])                    # D1
     if w.shape[0] == 3 * D:
         out["knorm"] = knorm_model(v)                                                                         # L3
     return out
@@ -137,14 +154,30 @@ def gated_model(a, w, gate, gate_scale, *, dt, ft):
     return dict(y=torch.where(gate, v, torch.zeros_like(v)))
 
 
+def dropout_bwd_model(g, keep, *, dt):
+    """D2, exact: g (values of the compute type) -> the values of T(float32(g) * keep_scale) where kept, 0 elsewhere, as fp32"""
+    v = (g.to(F32) * keep.scale).to(dt).to(F32)
+    return dict(y=torch.where(keep.mask.to(g.device), v, torch.zeros_like(v)))
+
+
+def operand_drop_model(a, keep, w, gate, gate_scale, *, dt, ft):
+    """the gated dH launch with the backward of a dropout folded onto its operand: a' = dropout_bwd_model(a), dH = gated_model(a')"""
+    ad = dropout_bwd_model(a, keep, dt=dt)["y"]
+    return dict(a=ad, y=gated_model(ad, w, gate, gate_scale, dt=dt, ft=ft)["y"])
+
+
 # ------------------------------------------------------------------------------------------ the generic NT product
-def gemm_nt_model(a, w, bias=None, res=None, act=None, gate=None, gate_scale=1.0, row_scale=None, rows_per_scale=1, *, dt, ft):
-    """y = act(a W^T + b) [gate > 0 ? * gate_scale : 0] [* row_scale[row // rows_per_scale]] [+ res], in the order of epilogue()"""
+def gemm_nt_model(a, w, bias=None, res=None, act=None, gate=None, gate_scale=1.0, row_scale=None, rows_per_scale=1, keep=None,
+                  fault=None, *, dt, ft):
+    """y = drop(act(a W^T + b)) [gate > 0 ? * gate_scale : 0] [* row_scale[row // rows_per_scale]] [+ res], in the order of epilogue()"""
     r = _rounder(dt, ft)
     v = _mm(a, w, None, dt, ft)
     if bias is not None:
         v = v + bias.to(ft)
     v = _act(v, act, dt, ft)
+    if fault == "behind_residual":                                       # (the fault: drop(v + res) for drop(v) + res)
+        return dict(y=_drop(r(v) + res.to(ft), keep))
+    v = _drop(v, keep, fault)                                                                                 # D1
     if gate is None and row_scale is None and res is None:
         return dict(y=v)
     v = r(v)                                                                                                  # N1

@@ -97,10 +97,14 @@ def sinusoid_table(length, d_model=D):
     return pe
 
 
-def stream_input_model(x, cls, gamma, beta, pe, bott, w, kv_len=None, *, dt, ft):
-    """mbt_encoder.py:697-729 and the concatenation of :745: z[b] = [bott | LN(cat(CLS.to(dt), x[b])) + pe], nn.LayerNorm (biased
+def stream_input_model(x, cls, gamma, beta, pe, bott, w, kv_len=None, keep=None, keep_bwd=None, keep_bott=None, *, dt, ft):
+    """mbt_encoder.py:697-729 and the concatenation of :745: z[b] = [bott | drop(LN(cat(CLS.to(dt), x[b])) + pe)], nn.LayerNorm (biased
     variance, eps 1e-5 inside the root).  kv_len (packed form): only the first kv_len[b] rows of sample b exist -- the others carry no
-    gradient.  Returns the padded z, the live mask and the gradients of loss = sum(z * w) over live rows."""
+    gradient.  keep (tests/dropout_model.Keep over the [B, N + 1, 256] LayerNorm rows; None = off): y = keep ? y * keep_scale : 0 behind
+    LN + PE, in front of the store's one rounding; the bottleneck rows are never masked; autograd gives the backward its g = keep ?
+    g * keep_scale : 0 in front of the LayerNorm backward.  keep_bwd / keep_bott exist for the seeded faults only: a backward that
+    applies another mask than the forward, and a mask [B, nb, 256] over the bottleneck rows.
+    Returns the padded z, the live mask and the gradients of loss = sum(z * w) over live rows."""
     B, N, _ = x.shape
     nb = 0 if bott is None else bott.shape[-2]
     xr, cr, gr, br = _leaf(x, ft), _leaf(cls, ft), _leaf(gamma, ft), _leaf(beta, ft)
@@ -110,7 +114,13 @@ def stream_input_model(x, cls, gamma, beta, pe, bott, w, kv_len=None, *, dt, ft)
     y = F.layer_norm(torch.cat([c.expand(B, 1, D), xr], 1), (D,), gr, br, 1e-5)
     if pe is not None:
         y = y + pe[None, :N + 1].to(ft)
-    z = y if tr is None else torch.cat([tr.view(1, nb, D).expand(B, nb, D), y], 1)
+    if keep is not None:
+        mult = lambda k: torch.where(k.mask, torch.full((), k.scale, dtype=ft), torch.zeros((), dtype=ft))
+        y = y * mult(keep) if keep_bwd is None else y * mult(keep_bwd) + (y * mult(keep) - y * mult(keep_bwd)).detach()
+    tb = None if tr is None else tr.view(1, nb, D).expand(B, nb, D)
+    if keep_bott is not None:
+        tb = tb * torch.where(keep_bott.mask, torch.full((), keep_bott.scale, dtype=ft), torch.zeros((), dtype=ft))
+    z = y if tb is None else torch.cat([tb, y], 1)
     R = nb + 1 + N
     live = torch.ones(B, R, dtype=torch.bool) if kv_len is None else torch.arange(R)[None, :] < kv_len.long().cpu()[:, None]
     (z * w.to(ft) * live[..., None]).sum().backward()
