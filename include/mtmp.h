@@ -309,6 +309,39 @@ int mtmp_head3_bwd(int cls_dtype, const float* d_out, const void* const* cls, co
                    const float* gender, const void* const* params, int n_sets, const float* ws_fwd, void* const* dcls,
                    float* const* dst, float* ws_bwd, int B, float ln_eps, void* stream);
 
+/* The same head on R rows, 1 <= R <= 4 (csrc/headr.hip), whose inputs are BLOCKS: blocks[s] (s < n_blocks <= 3) is a strided view
+ * [B][block_rows[s]][256] in `dtype` (0 fp32, 1 bf16; one for all blocks) at blocks[s] + b * block_ld[s] + row * row_ld[s] in
+ * elements (16-byte aligned base, 1 .. 4 rows, both strides >= 256 and multiples of 4).  Head row m reads n_src[m] in {1, 2, 3}
+ * sources (block, row) = (src[2 * (3 m + i)], src[2 * (3 m + i) + 1]) for i < n_src[m] (src: int[R][3][2]; blocks, block_ld,
+ * row_ld, block_rows, n_src and src are host arrays) and takes the LayerNorm of their fp32 mean ((a + b) + c) / n.  A (block, row)
+ * pair may feed at most one head row; anything else is refused by message.  params: as mtmp_head3_fwd, n_sets in {1, R} (one set
+ * shared by the R rows, or set m for row m).  out float[R][B].  ws_fwd: mtmp_headr_ws_floats(R, B) floats, written by the
+ * forward, read by the backward.
+ * backward: d_out float[R][B]; dblocks[s]: [B][block_rows[s]][256] contiguous, in `dtype`, EVERY row written: a source row gets
+ * d(head row) / n_src, a row that is no source exact zeros.  dst: one destination per entry of params (overwritten) -- a shared
+ * set and the first six get the rows' contributions, each finished on its own, added in the order m = 0 .. R-1.
+ * ws_bwd: mtmp_headr_bwd_ws_floats(R, B) floats.  1 <= B <= 256.  Three launches forward, four backward, no float atomics. */
+int mtmp_headr_ws_floats(int R, int B);
+int mtmp_headr_bwd_ws_floats(int R, int B);
+int mtmp_headr_fwd(int dtype, int n_blocks, const void* const* blocks, const long long* block_ld, const long long* row_ld,
+                   const int* block_rows, int R, const int* n_src, const int* src, const float* age, const float* gender,
+                   const void* const* params, int n_sets, float* out, float* ws, int B, float ln_eps, void* stream);
+int mtmp_headr_bwd(int dtype, const float* d_out, int n_blocks, const void* const* blocks, const long long* block_ld,
+                   const long long* row_ld, const int* block_rows, int R, const int* n_src, const int* src, const float* age,
+                   const float* gender, const void* const* params, int n_sets, const float* ws_fwd, void* const* dblocks,
+                   float* const* dst, float* ws_bwd, int B, float ln_eps, void* stream);
+
+/* Learned weighting of R <= 4 logits over the modalities present (tri_mbt_vflexible.py:276-286, bitxt_ / biimg_mbt_vflexible1.py):
+ * p[m][b] = softmax over the present rows of temperature * a[m], exactly 0 on absent rows; out[b] = sum_m p[m][b] o[m][b].
+ * o / d_o float[R][B], a / d_a float[R], out / d_out float[B], missing_num int64[B] (read as id & 3: nothing is indexed by it);
+ * table: bit 4 * pattern + row set = row `row` is present under that pattern id.  backward: d_o[m][b] = p[m][b] d_out[b],
+ * d_a[m] = temperature * sum_b p[m][b] d_out[b] (o[m][b] - out[b]), summed over the batch in a fixed order (one workgroup, no
+ * atomics).  One launch each way, any B > 0, no host synchronisation. */
+int mtmp_flex_combine_fwd(const float* o, const float* a, float temperature, const long long* missing_num, unsigned table,
+                          float* out, int R, int B, void* stream);
+int mtmp_flex_combine_bwd(const float* d_out, const float* o, const float* a, float temperature, const long long* missing_num,
+                          unsigned table, float* d_o, float* d_a, int R, int B, void* stream);
+
 /* Mean of the three logits over the modalities present under the pattern id missing_num[b] (trainer.py:68-77,224-229;
  * tri_mbt_v1.py:272-281): S(0) = {0,1,2}, S(1) = {0,1}, S(2) = {0,2}, S(3) = {0}; o / d_o float[3][B], out / d_out float[B],
  * missing_num int64[B] (read as id & 3: nothing is indexed by it).  d_o[m][b] = d_out[b] / |S| inside the set, 0 outside. */

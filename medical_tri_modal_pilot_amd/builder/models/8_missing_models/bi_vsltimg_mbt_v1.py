@@ -98,7 +98,7 @@ class BI_VSLTIMG_MBT_V1(nn.Module):
         dt = self.compute_dtype
         B = x.size(0)
         age, gen = age.float(), gen.float()
-        demo_embedding = self.ie_demo(torch.stack([age, gen], dim=1))                       # [B,256] fp32 (:178-179)
+        demo_embedding = self._demo_embedding(age, gen)                                     # [B,256] fp32 (:178-179)
         vslt_embedding = ops.TieEmbed.apply(x.float(), self.ie_vslt[0].weight, self.ie_vslt[0].bias, self.ie_vslt[1].weight,
                                             self.ie_vslt[1].bias, self.ie_time[0].weight, self.ie_time[0].bias,
                                             self.ie_time[1].weight, self.ie_time[1].bias, self.ie_feat.weight, dt)
@@ -120,6 +120,10 @@ class BI_VSLTIMG_MBT_V1(nn.Module):
             enc_outputs=[vslt_embedding, img_embedding], fixed_lengths=[vslt_embedding.size(1), img_embedding.size(1)],
             varying_lengths=[input_lengths, img_embedding.size(1)], fusion_idx=None, missing=missing)
         return self._head(outputs, demo_embedding, missing)
+
+    def _demo_embedding(self, age, gen):
+        """ie_demo(age, gender), which feeds nothing but the head -- a hook: a sibling whose head kernels compute it returns None"""
+        return self.ie_demo(torch.stack([age, gen], dim=1))
 
     def _head(self, outputs, demo_embedding, missing):
         """The classifier on the two CLS rows -- a hook: sibling models weight them differently."""

@@ -9,7 +9,8 @@ TRI_MBT_VMULTIVSLT with three differences:
     the image stream's row 1, head 2 the mean of the vital-sign stream's row 2 and the text stream's row 1, head 3 the vital-sign
     stream's row 3.  Rows 1 of the image and text streams are TOKEN rows there (those streams carry no CLS rows); kept as it is.
 ``rmse_layer`` exists (:120) and is used only with an rmse auxiliary loss, which this path refuses like the reference's trainer
-does for these models.  The heads are torch ops, as in the vflexible models.
+does for these models.  The heads are ops.RowHeadFn on three blocks under tuning.HIP_ROW_HEAD (the source means are taken inside
+its first kernel), the torch chain otherwise.
 """
 import torch
 import torch.nn as nn
@@ -22,6 +23,12 @@ class TRI_MBT_VMULTI2(TRI_MBT_VMULTIVSLT):
     TRAINS_ENCODER_IN_REFERENCE = True
     MASKS = [True, True, True]
     FIRST_STREAM_ONLY = False
+    # blocks v[:, :4], i[:, :2], t[:, :2]; head 0 = mean(v0, i0, t0), head 1 = mean(v1, i1), head 2 = mean(v2, t1), head 3 = v3
+    HEAD_TABLE = (((0, 0), (1, 0), (2, 0)), ((0, 1), (1, 1)), ((0, 2), (2, 1)), ((0, 3),))
+
+    def _head_blocks(self, outputs):
+        v, i, t = outputs
+        return [v[:, :4, :], i[:, :2, :], t[:, :2, :]]
 
     def _make_heads(self):
         self.rmse_layer = nn.Linear(self.model_dim * 2, 1, bias=True)

@@ -1916,6 +1916,147 @@ def bce_rows_masked_mean(criterion, logits, target, missing_num, table=MULTI_LOS
     return criterion(logits[mask], yr[mask])
 
 
+# ----------------------------------------------------------------------------- R-row head, flexible combine (csrc/headr.hip)
+def _head_block(t: torch.Tensor) -> torch.Tensor:
+    """A [B, P, 256] view the row-head kernels read in place (fp32 | bf16, unit column stride, sample and row strides multiples
+    of 4 and >= 256, 16-byte aligned base), else a copy."""
+    t = t.detach()
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        t = t.float()
+    if (t.stride(2) != 1 or any(t.stride(i) % 4 or t.stride(i) < D_MODEL for i in (0, 1)) or t.data_ptr() % 16):
+        t = t.contiguous()
+    return t
+
+
+def _row_table(table, blocks):
+    """(R, n_src int[R], src int[R][3][2]) of a source table ``table[m] = ((block, row), ...)`` -- 1 .. 3 sources per head row,
+    every (block, row) pair in at most one head row -- checked against the blocks' shapes."""
+    R = len(table)
+    if not 1 <= R <= 4:
+        raise ValueError(f"RowHeadFn: 1 .. 4 head rows, got {R}")
+    n_src, src, seen = [], [0] * (6 * R), set()
+    for m, row in enumerate(table):
+        if not 1 <= len(row) <= 3:
+            raise ValueError(f"RowHeadFn: head row {m} reads {len(row)} sources (1 .. 3)")
+        n_src.append(len(row))
+        for i, (s, r) in enumerate(row):
+            if not (0 <= s < len(blocks) and 0 <= r < blocks[s].shape[1]):
+                raise ValueError(f"RowHeadFn: head row {m} names (block {s}, row {r}), which is not among the blocks")
+            if (s, r) in seen:
+                raise ValueError(f"RowHeadFn: (block {s}, row {r}) feeds more than one head row: a source row may feed at most one")
+            seen.add((s, r))
+            src[2 * (3 * m + i)], src[2 * (3 * m + i) + 1] = int(s), int(r)
+    return R, n_src, src
+
+
+class RowHeadFn(torch.autograd.Function):
+    """The LayerNorm head of TriHeadFn on R <= 4 head rows whose inputs are BLOCKS (csrc/headr.hip):
+    apply(block_0 [B, P_0, 256] .. (up to three, P <= 4, fp32 | bf16; views such as ``outputs[0][:, :4, :]`` are read in place),
+    age [B], gender [B], table, *parameters) -> logits [R, B] fp32.  ``table[m]`` = the 1 .. 3 ``(block, row)`` sources whose fp32
+    mean head row m normalises; a pair may feed one head row only.  Parameters: the six shared ones of TriHeadFn, then ONE head's
+    six (shared by the R rows) or R heads'.  Every block gets ONE gradient [B, P, 256] in its own type (a row that is no source:
+    zeros), so autograd runs one slice-backward per block.  Three launches forward, four backward; the parameter gradients go to
+    their slices of the flat gradient buffer when they can be overwritten (_sink_dsts), to autograd otherwise."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        k = next((i for i, a in enumerate(args) if not torch.is_tensor(a)), None)
+        if k is None or not 3 <= k <= 5:
+            raise ValueError("RowHeadFn.apply(block_0 .. (1 to 3 blocks), age, gender, table, *parameters)")
+        blocks, age, gender, table, prm = list(args[:k - 2]), args[k - 2], args[k - 1], args[k], list(args[k + 1:])
+        _gpu(*blocks)
+        B = blocks[0].shape[0]
+        if B > HEAD_MAX_B:
+            raise ValueError(f"RowHeadFn handles up to {HEAD_MAX_B} rows per rank (got {B})")
+        if any(t.dim() != 3 or t.shape[0] != B or t.shape[2] != D_MODEL or not 1 <= t.shape[1] <= 4 for t in blocks):
+            raise ValueError(f"RowHeadFn: blocks [B, 1 .. 4, {D_MODEL}], got {[tuple(t.shape) for t in blocks]}")
+        R, n_src, src = _row_table(table, blocks)
+        if len(prm) not in (12, 6 + 6 * R):
+            raise ValueError(f"RowHeadFn takes 12 (one shared head) or {6 + 6 * R} ({R} heads) parameters, got {len(prm)}")
+        blk = [_head_block(t) for t in blocks]
+        if any(t.dtype != blk[0].dtype for t in blk):
+            blk = [t.float().contiguous() for t in blk]
+        age, gender = _c(age.detach().float()), _c(gender.detach().float())
+        P = _head_params(prm)
+        dev = blk[0].device
+        out = torch.empty(R, B, dtype=torch.float32, device=dev)
+        ws = torch.empty(_lib.lib().mtmp_headr_ws_floats(R, B), dtype=torch.float32, device=dev)
+        ctx.desc = (len(blk), (ctypes.c_longlong * len(blk))(*[t.stride(0) for t in blk]),
+                    (ctypes.c_longlong * len(blk))(*[t.stride(1) for t in blk]), _ints([t.shape[1] for t in blk]), R, _ints(n_src),
+                    _ints(src))
+        n, ld, rld, rows, _, ns, sr = ctx.desc
+        call("mtmp_headr_fwd", _dt(blk[0]), n, _ptrs(blk), ld, rld, rows, R, ns, sr, _p(age), _p(gender), _ptrs(P),
+             (len(P) - 6) // 6, _p(out), _p(ws), B, 1e-5, _stream())
+        ctx.save_for_backward(age, gender, ws, *blk, *P)
+        ctx.prm = prm
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        n, ld, rld, rows, R, ns, sr = ctx.desc
+        age, gender, ws, *rest = ctx.saved_tensors
+        blk, P = rest[:n], rest[n:]
+        B, dev = blk[0].shape[0], blk[0].device
+        d_out = _c(d_out.float())
+        dblk = [torch.empty(B, t.shape[1], D_MODEL, dtype=t.dtype, device=dev) for t in blk]
+        wsb = torch.empty(_lib.lib().mtmp_headr_bwd_ws_floats(R, B), dtype=torch.float32, device=dev)
+        grads = _head_param_grads(ctx.prm, lambda dsts: call(
+            "mtmp_headr_bwd", _dt(blk[0]), _p(d_out), n, _ptrs(blk), ld, rld, rows, R, ns, sr, _p(age), _p(gender), _ptrs(P),
+            (len(P) - 6) // 6, _p(ws), _ptrs(dblk), _ptrs(dsts), _p(wsb), B, 1e-5, _stream()))
+        return tuple(dblk) + (None, None, None) + grads
+
+
+# present[pattern][row] of the flexible models: the tri-modal ones (trainer.py:68-77: 0 = all, 1 = report missing, 2 = image
+# missing, 3 = both missing; rows vslt, image, text) and the two-stream ones (0 = both, 1 = vital signs alone; their loaders know no
+# other id, ids 2 and 3 are read as vital signs alone)
+FLEX_TRI_TABLE = ((True, True, True), (True, True, False), (True, False, True), (True, False, False))
+FLEX_BI_TABLE = ((True, True), (True, False), (True, False), (True, False))
+
+
+class FlexCombineFn(torch.autograd.Function):
+    """The flexible models' learned weighting (tri_mbt_vflexible.py:276-286): apply(o [R, B] fp32, a [R] or [R, 1], temperature,
+    missing_num [B], table bits (_table_bits: the rows PRESENT under each pattern id)) -> [B]: sum_m p[m][b] o[m][b] with
+    p = softmax over the present rows of temperature * a, exactly 0 on the absent ones.  One launch each way; d a is summed over
+    the batch in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, o, a, temperature, missing_num, bits):
+        _gpu(o, a)
+        if o.dim() != 2 or not 1 <= o.shape[0] <= 4 or a.numel() != o.shape[0] or missing_num.numel() != o.shape[1]:
+            raise ValueError(f"FlexCombineFn: logits [R <= 4, B], weights [R], missing_num [B]; got {tuple(o.shape)}, "
+                             f"{tuple(a.shape)}, {tuple(missing_num.shape)}")
+        o, a32 = _c(o.detach().float()), _c(a.detach().float().reshape(-1))
+        ids = _ids64(missing_num, o.device)
+        out = torch.empty(o.shape[1], dtype=torch.float32, device=o.device)
+        call("mtmp_flex_combine_fwd", _p(o), _p(a32), float(temperature), _p(ids), int(bits), _p(out), o.shape[0], o.shape[1], _stream())
+        ctx.save_for_backward(o, a32, ids)
+        ctx.t, ctx.bits, ctx.a_shape, ctx.a_dtype = float(temperature), int(bits), a.shape, a.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        o, a32, ids = ctx.saved_tensors
+        d_out = _c(d_out.float().reshape(-1))
+        d_o, d_a = torch.empty_like(o), torch.empty_like(a32)
+        call("mtmp_flex_combine_bwd", _p(d_out), _p(o), _p(a32), ctx.t, _p(ids), ctx.bits, _p(d_o), _p(d_a), o.shape[0], o.shape[1],
+             _stream())
+        return d_o, d_a.view(ctx.a_shape).to(ctx.a_dtype), None, None, None
+
+
+def flex_combine(o, a, temperature, missing_num, table):
+    """FlexCombineFn on the GPU, the reference's masked_fill / softmax / candidate sums / gather form elsewhere.
+    o [R, B], a [R] or [R, 1], table[pattern][row] = present."""
+    R, B = o.shape
+    if o.is_cuda and o.dtype == torch.float32:
+        return FlexCombineFn.apply(o, a, temperature, missing_num, _table_bits(table, R))
+    miss = missing_num.to(o.device).long()
+    present = torch.tensor([[bool(table[p][r]) for r in range(R)] for p in range(len(table))], device=o.device)
+    w = a.reshape(R, 1).to(o.dtype).repeat(1, B).masked_fill(~present[miss].permute(1, 0), -1e9)
+    po = o * torch.softmax(w * temperature, dim=0)
+    cands = torch.stack([(po * present[p].to(o.dtype).unsqueeze(1)).sum(0) for p in range(len(table))])
+    return cands[miss, torch.arange(B, device=o.device)]
+
+
 # ----------------------------------------------------------------------------- stream input (K4)
 class StreamInputFn(torch.autograd.Function):
     """mbt_encoder.py:697-729 + the [bottleneck | CLS | tokens] concatenation of :745 as one launch each way.

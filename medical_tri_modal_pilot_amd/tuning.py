@@ -2,7 +2,7 @@
 
 Each switch chooses the order in which independent launches are issued, or which of two launch sequences meant to be equivalent
 runs.  The defaults below are what the tests and bench.py run, and the only settings they run: no test reads or sets one of these
-attributes (HIP_HOURLY_EMBED and HIP_TRI_HEAD excepted: their other setting is the reference's own torch chain, and a test runs both).  The other
+attributes (HIP_HOURLY_EMBED, HIP_TRI_HEAD and HIP_ROW_HEAD excepted: their other setting is the reference's own torch chain, and a test runs both).  The other
 settings are exercised only through ``tools/dbg/ab_patch.py`` (and the tools/dbg probes that flip one), so treat a non-default setting as unverified until such a run has compared it.  Each default is the faster setting as measured on
 MI355X -- the measurement is named beside it and lives in DESIGN.md section 9 ("Built, measured, not kept").  They are module
 attributes so that ab_patch.py can flip one and measure both settings on one machine in one session (machines differ by up to
@@ -48,6 +48,13 @@ HIP_HOURLY_EMBED = True
 # -> four means -> gather plus ie_demo.  Like HIP_HOURLY_EMBED, BOTH settings are run by the tests (tests/test_noshnoavgtr_gpu.py):
 # off is the torch chain the reference defines.  profiles/tri_head.txt.
 HIP_TRI_HEAD = True
+# tri_mbt_vflexible / 2 / 3, bitxt_ / biimg_mbt_vflexible1, tri_mbt_vmultivslt, tri_mbt_vmulti2: the LayerNorm head on two to four
+# rows as ops.RowHeadFn (csrc/headr.hip: blocks of stream rows and a source table; ops.TriHeadFn for the three tri-modal flexible
+# models) and the flexible models' softmax weighting over the present modalities as ops.FlexCombineFn (one launch each way)
+# instead of the torch chain stack -> LayerNorm -> cat -> Linear -> LayerNorm -> ReLU -> Linear (-> masked_fill -> softmax -> four
+# sums -> gather) plus ie_demo.  Like HIP_TRI_HEAD, BOTH settings are run by the tests (tests/test_flex_models_gpu.py): off is the
+# torch chain the reference defines.  A model class opts out with ``hip_row_head = False``.  profiles/row_head.txt.
+HIP_ROW_HEAD = True
 # ops.layer_infer: the few-row FFN launches of a CLS-only last layer (B rows) and of the exchange-only layer in front of it (B * R
 # rows) keep the training forward's two launches (mtmp_ln_gemm_signs + mtmp_gemm_nt) below this many rows instead of the fused
 # mtmp_ffn_block: one workgroup of the fused kernel streams the whole megabyte of W1 and W2 for its 128 rows (42-44 us alone),
