@@ -286,6 +286,36 @@ int mtmp_head_bwd_scatter(int cls_dtype, const float* d_out, const void* cls, co
                           const void* const* params, const float* ws_fwd, void* dcls, float* const* dst, float* ws_bwd, int B,
                           float ln_eps, int training, void* stream);
 
+/* The same head with --vslt-type QIE (tri_mbt_vsltcls.py:148-151, 248-250; csrc/headq.hip): nothing is concatenated, the head reads
+ * the 256 columns of LN(cls): out[b] = fc3(ReLU(BatchNorm1d(fc0(LN(cls[b]))))).  mtmp_head_fwd_t / mtmp_head_bwd_scatter without
+ * age, gender and the four ie_demo parameters.  params: 10 device pointers (float): layer_norms_after_concat.{weight,bias},
+ * fc_list.0.{weight[256][256],bias}, fc_list.1.{weight,bias,running_mean,running_var}, fc_list.3.{weight[256],bias[1]}.
+ * dst[8]: the gradients of the eight trained ones in that order (overwritten).  ws_fwd: mtmp_headq_ws_floats(B) floats, written by
+ * the forward and read by the backward; ws_bwd: B*256*8 floats.  1 <= B <= 256, B > 1 in training mode. */
+int mtmp_headq_ws_floats(int B);
+int mtmp_headq_fwd_t(int cls_dtype, const void* cls, const void* const* params, float* out, float* ws, int B, float ln_eps,
+                     float bn_eps, float momentum, int training, long long* num_batches_tracked, void* stream);
+int mtmp_headq_bwd_scatter(int cls_dtype, const float* d_out, const void* cls, const void* const* params, const float* ws_fwd,
+                           void* dcls, float* const* dst, float* ws_bwd, int B, float ln_eps, int training, void* stream);
+
+/* The QIE input (tri_mbt_vsltcls.py:191-198, 216-221; csrc/qie.hip): demo[b] = ReLU(LN(ie_demo.0(age[b], gender[b]))) in fp32 is
+ * added to every token of the three streams.  Forward, one launch: add_v[b] = demo[b], add_i[b] = it[b] + demo[b], add_t[b] =
+ * tt[b] + demo[b], all [B][256] in `dtype` (what mtmp_stream_input_fwd_add takes as `add`, add_L = the stream's token count); it /
+ * tt are NULL together (--imgtxt-time 0): add_i / add_t are then left alone.  params: 4 device pointers (float):
+ * ie_demo.0.weight[256][2], ie_demo.0.bias, ie_demo.1.{weight,bias}.
+ * Backward, two launches, no float atomics, bit-identical between runs: dx_v [B][N_v][256], dx_i [B][N_i][256], dx_t [B][N_t][256]
+ * in `dtype` are the stream inputs' gradients as mtmp_stream_input_bwd_grouped leaves them (dx_i / dx_t / d_it / d_tt NULL together);
+ * kv_len (device int32[B], may be NULL) with kv_off: sample b's dx_v rows from max(kv_len[b] - kv_off, 0) on are zeros (a packed
+ * stream's pad rows) and are skipped.  d_it[b] = sum_j dx_i[b][j], d_tt[b] = sum_j dx_t[b][j] in `dtype` (mtmp_token_sums' values);
+ * dst[4]: the gradients of the four parameters (overwritten) from d_demo[b] = sum_t dx_v + sum_j dx_i + sum_j dx_t, kept in fp32.
+ * ws: mtmp_qie_adds_bwd_ws_floats(B, N_v, dx_i != NULL) floats. */
+int mtmp_qie_adds_fwd(int dtype, const float* age, const float* gender, const void* const* params, const void* it, const void* tt,
+                      void* add_v, void* add_i, void* add_t, int B, float ln_eps, void* stream);
+long long mtmp_qie_adds_bwd_ws_floats(int B, int N_v, int with_time);
+int mtmp_qie_adds_bwd(int dtype, const void* dx_v, const void* dx_i, const void* dx_t, const int32_t* kv_len, int kv_off,
+                      const float* age, const float* gender, const void* const* params, void* d_it, void* d_tt, float* const* dst,
+                      float* ws, int B, int N_v, int N_i, int N_t, float ln_eps, void* stream);
+
 /* BCEWithLogitsLoss(reduction="mean") (2_train.py:76, trainer.py:128): loss[0] = mean_b [max(o,0) - o t + log1p(exp(-|o|))],
  * dlogit[b] = (sigmoid(o_b) - t_b) / n; logits / target / dlogit float[n]. */
 int mtmp_bce_logits_mean(const float* logits, const float* target, float* loss, float* dlogit, int n, void* stream);

@@ -119,6 +119,9 @@ class TRI_MBT_VSLTCLS(nn.Module):
         # number of images per sample: the reference hard-codes 3 (:161-162,226-231); generalised to K.
         self.n_images = int(getattr(args, "n_images", 3)) if self.args.multiimages == 1 else 1
 
+    # --vslt-type QIE on HIP kernels (tuning.HIP_QIE: ops.QieAddsFn, ops.StreamInputsQieFn, ops.QieHeadFn).  Opt-in PER CLASS: forward()
+    # asks the class's own dict, so a sibling that inherits forward() keeps the torch chain until it is pinned to goldens of its own.
+    hip_qie = True
     head_fusable = True        # ie_demo = Linear -> LayerNorm -> ReLU: what ops.HeadFn fuses (a sibling may differ)
     head_min_train_batch = 2   # BatchNorm1d needs two rows in training mode (a sibling with a LayerNorm head: 1)
     # forward accepts a PackedTie in place of the padded x.  The trainer asks before it hands windows of the event store over
@@ -157,7 +160,7 @@ class TRI_MBT_VSLTCLS(nn.Module):
     def _time_embeddings(self, img_time, txt_time, demo_embedding, dt):
         """(it [n_img,256], tt [B,256]): ie_time(t) + ie_feat[18 | 19] of every image / report time (:216-224)."""
         feat_tab = self.ie_feat.weight
-        if self.args.vslt_type == "QIE" or not img_time.is_cuda:
+        if (self.args.vslt_type == "QIE" and not getattr(self, "_qie_hip", False)) or not img_time.is_cuda:
             it = self.ie_time(img_time.unsqueeze(1)) + feat_tab[18]
             tt = self.ie_time(txt_time.unsqueeze(1)) + feat_tab[19]
             if self.args.vslt_type == "QIE":
@@ -178,8 +181,8 @@ class TRI_MBT_VSLTCLS(nn.Module):
     def _joint_embeddings(self, x, img_time, txt_time, dt):
         """(vslt [B,T,256], it, tt) from ONE autograd node (ops.TieTimeEmbed) when the event embedding and the two time
         embeddings share ie_time / ie_feat and run as HIP kernels; None: the caller takes the two separate nodes."""
-        if (not self.joint_embeddings or self.args.vslt_type != "TIE" or isinstance(x, PackedTie) or not img_time.is_cuda
-                or not x.is_cuda):
+        if (not self.joint_embeddings or not (self.args.vslt_type == "TIE" or getattr(self, "_qie_hip", False))
+                or isinstance(x, PackedTie) or not img_time.is_cuda or not x.is_cuda):
             return None
         n_it = img_time.numel()
         ev = self._time_events(n_it, txt_time.numel(), img_time.device)
@@ -267,7 +270,17 @@ class TRI_MBT_VSLTCLS(nn.Module):
             self._warned_torch_head = True
             warnings.warn(f"{type(self).__name__}: batch of {B} is outside the fused head kernels' range ({self.head_min_train_batch} <= B <= {ops.HEAD_MAX_B} in "
                           "training): the classifier head runs as torch ops (same results, ~60 more small launches per step)")
-        if not fused_head:
+        # --vslt-type QIE on its HIP nodes (class attribute hip_qie above; tuning.HIP_QIE): one image per sample, a batch the head
+        # kernels take, the fused stream-input node in the encoder.  Anything else is the torch chain below, as before.
+        enc_ = self.fusion_transformer
+        qie_hip = self._qie_hip = bool(
+            self.args.vslt_type == "QIE" and tuning.HIP_QIE and vars(type(self)).get("hip_qie", False) and age.is_cuda
+            and self.n_images == 1 and B <= ops.HEAD_MAX_B and (B > 1 or not self.training)
+            and "rmse" not in self.args.auxiliary_loss_type and tuning.FUSED_INPUT_TAIL and self.defer_time_adds
+            and min(max(enc_.fusion_idx, 0), enc_.n_layers) == 0 and enc_.n_layers > 0 and getattr(enc_, "n_modality", 0) == 3
+            and (isinstance(x, PackedTie) or x.is_cuda) and img_time.is_cuda and txt_time.is_cuda)
+        demo_embedding = None
+        if not fused_head and not qie_hip:
             demographic = torch.stack([age, gen], dim=1)
             demo_embedding = self.ie_demo(demographic)                                        # [B,256] fp32
         # The image and text input chains (projection, time embedding add, and -- inside the encoder -- the stream
@@ -366,11 +379,11 @@ class TRI_MBT_VSLTCLS(nn.Module):
                 vslt_embedding, it, tt = joint
             else:
                 vslt_embedding = self._vslt_embedding(x, dt)
-            if self.args.vslt_type == "QIE":
+            if self.args.vslt_type == "QIE" and not qie_hip:
                 vslt_embedding = vslt_embedding + demo_embedding.unsqueeze(1).to(dt)
         if self.args.imgtxt_time == 1:                                                        # (:216-224)
             if it is None:
-                it, tt = self._time_embeddings(img_time, txt_time, demo_embedding if not fused_head else None, dt)
+                it, tt = self._time_embeddings(img_time, txt_time, demo_embedding, dt)
             if side is not None:
                 for s_ in side:
                     s_.wait_stream(cur)              # the time embeddings were made on the main stream
@@ -391,6 +404,19 @@ class TRI_MBT_VSLTCLS(nn.Module):
             img_len = img_embedding.size(1)
         self.fusion_transformer.inputs_on_side_streams = side is not None
         self.fusion_transformer.time_adds = (it, tt) if (self.args.imgtxt_time == 1 and defer_add) else None
+        if qie_hip:
+            # demo, it + demo, tt + demo as ONE launch (ops.QieAddsFn), added to every token inside the stream-input node, whose backward
+            # leaves its input gradients in ``handoff`` for that node's two backward launches (:191-198, 216-221)
+            if self.args.imgtxt_time == 1 and not defer_add:
+                raise RuntimeError("QIE on the HIP path adds the time embeddings inside the stream-input node")
+            dm, handoff = self.ie_demo, {}
+            adds = ops.QieAddsFn.apply(age, gen, it if self.args.imgtxt_time == 1 else None, tt if self.args.imgtxt_time == 1 else None,
+                                       dt, handoff, dm[0].weight, dm[0].bias, dm[1].weight, dm[1].bias)
+            if side is not None:
+                for s_ in side:
+                    s_.wait_stream(cur)              # the add rows were made on the main stream
+            self.fusion_transformer.time_adds = None
+            self.fusion_transformer.qie_adds = (*adds, handoff)
         ops.mark("inputs.e")
         outputs, _ = self.fusion_transformer(
             enc_outputs=[vslt_embedding, img_embedding, txt_embedding],
@@ -398,7 +424,7 @@ class TRI_MBT_VSLTCLS(nn.Module):
             varying_lengths=[input_lengths, img_len, txt_lengths + 2], fusion_idx=None, missing=missing)
         if side is not None and not trained:
             cur.wait_stream(self._swin_stream)            # joins the encoder's stream to the caller's (its work ended long ago)
-        return self._head(outputs, demo_embedding if not fused_head else None, age, gen, missing, fused_head)
+        return self._head(outputs, demo_embedding, age, gen, missing, fused_head)
 
     def _head(self, outputs, demo_embedding, age, gen, missing, fused_head):
         """The classifier on the encoder's result (:248-255), fp32 -- a hook: sibling models read other rows."""
@@ -417,6 +443,18 @@ class TRI_MBT_VSLTCLS(nn.Module):
                                        bn.running_mean, bn.running_var, nbt, dm[0].weight, dm[0].bias, dm[1].weight, dm[1].bias,
                                        ln.weight, ln.bias, self.fc_list[0].weight, self.fc_list[0].bias, bn.weight, bn.bias,
                                        self.fc_list[3].weight, self.fc_list[3].bias)
+            return output1, None, None
+        if getattr(self, "_qie_hip", False) and vars(type(self)).get("hip_qie", False):
+            # the 256-wide BatchNorm head (ops.QieHeadFn): HeadFn's forms without the ie_demo half
+            bn, ln = self.fc_list[1], self.layer_norms_after_concat
+            nbt = bn.num_batches_tracked if (bn.training and bn.track_running_stats) else None
+            if nbt is not None and not nbt.is_cuda:
+                nbt.add_(1)
+                nbt = None
+            use_batch = bn.training or not bn.track_running_stats
+            output1 = ops.QieHeadFn.apply(cls, use_batch, 0.1 if bn.momentum is None else bn.momentum, bn.eps, bn.running_mean,
+                                          bn.running_var, nbt, ln.weight, ln.bias, self.fc_list[0].weight, self.fc_list[0].bias,
+                                          bn.weight, bn.bias, self.fc_list[3].weight, self.fc_list[3].bias)
             return output1, None, None
         cls = cls.float()
         class_input = self.layer_norms_after_concat(cls)

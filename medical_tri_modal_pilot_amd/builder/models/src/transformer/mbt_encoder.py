@@ -30,6 +30,7 @@ def _declare_switches(enc):
     enc.pack_rows = False                    # model: such a reader takes the vital-sign stream PACKED where forward() can
     enc.inputs_on_side_streams = False       # model, per call: it made the image / text embeddings on the two side streams
     enc.time_adds = None                     # model, for ONE call: (it, tt) time embeddings still to be added to their tokens
+    enc.qie_adds = None                      # model, for ONE call: (add_v, add_i, add_t, handoff) of ops.QieAddsFn (--vslt-type QIE)
     enc.cls_only_last_layer = True           # a CLS-row reader's last layer computes that one row only
     enc.graph_segments = None                # trainer: layer counts at which to cut the fusion stack into chained nodes
     enc.overlap_streams = True               # tests: off = no side streams
@@ -151,6 +152,12 @@ class TrimodalTransformerEncoder_MBT(nn.Module):
         # ``time_adds`` (set by the model for ONE call): the image / report time embeddings (it [n_i, 256], tt [n_t, 256]) still to be
         # added to every token of their group -- inside ops.StreamInputsFn when that node runs, here through torch otherwise
         time_adds, self.time_adds = self.time_adds, None
+        # ``qie_adds`` (set by the model for ONE call): ops.QieAddsFn's rows for the three streams and the hand-off dict its backward
+        # reads; they exist only for ops.StreamInputsQieFn, so a call that cannot run that node is refused
+        qie_adds, self.qie_adds = getattr(self, "qie_adds", None), None
+        if qie_adds is not None and (time_adds is not None or not (fused_in and tuning.FUSED_INPUT_TAIL and self.bottlenecks is not None)):
+            raise RuntimeError("qie_adds need the fused stream-input node (fusion from layer 0, GPU tensors in the compute dtype) "
+                               "and carry the time embeddings themselves")
         if time_adds is not None and not (fused_in and tuning.FUSED_INPUT_TAIL and self.bottlenecks is not None):
             enc_outputs = list(enc_outputs)
             for m, t in ((1, time_adds[0]), (2, time_adds[1])):
@@ -171,8 +178,14 @@ class TrimodalTransformerEncoder_MBT(nn.Module):
                 prm = [t for m in range(3) for t in (self.cls_token_per_modality[m], lns[m].weight, lns[m].bias)]
                 add_i, add_t = time_adds if time_adds is not None else (None, None)
                 time_adds = None                       # (added inside the node)
-                streams = list(ops.StreamInputsFn.apply(enc_outputs[0], enc_outputs[1], enc_outputs[2], self.bottlenecks, add_i, add_t,
-                                                        lns[0].eps, lns[1].eps, lns[2].eps, pdrop, meta, *prm))
+                if qie_adds is not None:
+                    meta["qie"] = qie_adds[3]
+                    streams = list(ops.StreamInputsQieFn.apply(enc_outputs[0], enc_outputs[1], enc_outputs[2], self.bottlenecks,
+                                                               qie_adds[0], qie_adds[1], qie_adds[2], lns[0].eps, lns[1].eps,
+                                                               lns[2].eps, pdrop, meta, *prm))
+                else:
+                    streams = list(ops.StreamInputsFn.apply(enc_outputs[0], enc_outputs[1], enc_outputs[2], self.bottlenecks, add_i,
+                                                            add_t, lns[0].eps, lns[1].eps, lns[2].eps, pdrop, meta, *prm))
             else:
                 made = {}
                 # one node per stream, the vital-sign stream's created LAST: autograd runs the three (ready together, behind the

@@ -1684,6 +1684,103 @@ class HeadFn(torch.autograd.Function):
         return (dcls, None, None, None, None, None, None, None, None) + grads
 
 
+class QieHeadFn(torch.autograd.Function):
+    """The same head with --vslt-type QIE (tri_mbt_vsltcls.py:148-151, 248-250; csrc/headq.hip): nothing is concatenated, fc_list.0 is
+    [256,256].  apply(cls [B,256] fp32 | bf16, training, momentum, bn_eps, run_mean, run_var, num_batches_tracked | None, *8
+    parameters: layer_norms_after_concat.{weight,bias}, fc_list.0 / .1 / .3 {weight,bias}) -> logits [B,1].  HeadFn's forms: the CLS
+    rows in the stack's type, the batch counter on the device, the eight gradients written to their destinations."""
+
+    @staticmethod
+    def forward(ctx, cls, training, momentum, bn_eps, run_mean, run_var, nbt, *prm):
+        _gpu(cls)
+        B = cls.shape[0]
+        if B > HEAD_MAX_B:
+            raise ValueError(f"QieHeadFn handles up to {HEAD_MAX_B} rows per rank (got {B})")
+        if len(prm) != 8 or tuple(prm[2].shape) != (D_MODEL, D_MODEL):
+            raise ValueError("QieHeadFn: eight parameters, fc_list.0.weight [256,256]")
+        cls = _c(cls.detach() if cls.dtype in (torch.float32, torch.bfloat16) else cls.detach().float())
+        P = _head_params(prm)
+        # order of include/mtmp.h: ln_g, ln_b, w1, b1, bn_g, bn_b, run_mean, run_var, w2, b2
+        table = _ptrs(P[:6] + [run_mean, run_var] + P[6:])
+        out = torch.empty(B, 1, dtype=torch.float32, device=cls.device)
+        ws = torch.empty(_lib.lib().mtmp_headq_ws_floats(B), dtype=torch.float32, device=cls.device)
+        if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
+            raise TypeError("QieHeadFn: num_batches_tracked must be an int64 device tensor")
+        call("mtmp_headq_fwd_t", _dt(cls), _p(cls), table, _p(out), _p(ws), B, 1e-5, float(bn_eps), float(momentum),
+             int(bool(training)), _p(nbt), _stream())
+        ctx.save_for_backward(cls, ws, run_mean, run_var, *P)
+        ctx.training = bool(training)
+        ctx.prm = list(prm)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        cls, ws, run_mean, run_var, *P = ctx.saved_tensors
+        B, dev = cls.shape[0], cls.device
+        table = _ptrs(P[:6] + [run_mean, run_var] + P[6:])
+        d_out = _c(d_out.float().view(-1))
+        dcls = torch.empty(B, D_MODEL, dtype=cls.dtype, device=dev)
+        wsb = torch.empty(B * D_MODEL * 8, dtype=torch.float32, device=dev)
+        grads = _head_param_grads(ctx.prm, lambda dsts: call(
+            "mtmp_headq_bwd_scatter", _dt(cls), _p(d_out), _p(cls), table, _p(ws), _p(dcls), _ptrs(dsts), _p(wsb), B, 1e-5,
+            int(ctx.training), _stream()))
+        return (dcls, None, None, None, None, None, None) + grads
+
+
+class QieAddsFn(torch.autograd.Function):
+    """The QIE input (tri_mbt_vsltcls.py:191-198, 216-221; csrc/qie.hip): apply(age [B], gender [B], it [B,256] | None, tt [B,256] |
+    None, dtype, handoff, *4 ie_demo parameters) -> (add_v, add_i, add_t) [B,256] in `dtype`: demo, it + demo, tt + demo with demo =
+    ReLU(LN(ie_demo.0(age, gender))) in fp32 (add_i / add_t None without it / tt) -- the rows ops.StreamInputsQieFn adds to every
+    token of the three streams.  One launch.
+    The BACKWARD does not take the add rows' gradients from autograd: StreamInputsQieFn, given the same ``handoff`` dict in its
+    meta, leaves its three input gradients there (and returns a placeholder for add_v so that this node runs behind it) and this node's two launches sum them over the token axis -- d it, d tt for the time-embedding node, and
+    d demo in fp32 for the ie_demo backward, whose four gradients go to their destinations (flat buffer or scratch)."""
+
+    @staticmethod
+    def forward(ctx, age, gender, it, tt, dtype, handoff, *prm):
+        _gpu(age)
+        if (it is None) != (tt is None) or len(prm) != 4:
+            raise ValueError("QieAddsFn: it and tt are given together; four ie_demo parameters")
+        B, dev = age.shape[0], age.device
+        age, gender = _c(age.detach().float()), _c(gender.detach().float())
+        P = _head_params(prm)
+        if it is not None:
+            if tuple(it.shape) != (B, D_MODEL) or tuple(tt.shape) != (B, D_MODEL):
+                raise ValueError("QieAddsFn: one image and one report time embedding per sample")
+            it, tt = _c(it.detach().to(dtype)), _c(tt.detach().to(dtype))
+        adds = [torch.empty(B, D_MODEL, dtype=dtype, device=dev) for _ in range(1 if it is None else 3)]
+        call("mtmp_qie_adds_fwd", _dt(adds[0]), _p(age), _p(gender), _ptrs(P), _p(it), _p(tt), _p(adds[0]),
+             _p(adds[1] if it is not None else None), _p(adds[2] if it is not None else None), B, 1e-5, _stream())
+        ctx.save_for_backward(age, gender, *P)
+        ctx.prm, ctx.with_time, ctx.dtype = list(prm), it is not None, dtype
+        ctx.handoff = handoff                  # filled by StreamInputsQieFn.backward: dxs, kv_len, kv_off
+        ctx.set_materialize_grads(False)
+        return (adds[0], adds[1], adds[2]) if it is not None else (adds[0], None, None)
+
+    @staticmethod
+    def backward(ctx, g_v, g_i, g_t):
+        age, gender, *P = ctx.saved_tensors
+        h = ctx.handoff
+        if "dxs" not in h:
+            raise RuntimeError("QieAddsFn.backward: the add rows' consumer is ops.StreamInputsQieFn, which hands its input gradients over")
+        dx_v, dx_i, dx_t = h.pop("dxs")
+        kv_len, kv_off = h.pop("kv_len", None), h.pop("kv_off", 0)
+        B, dev = age.shape[0], age.device
+        if ctx.with_time != (dx_i is not None) or ctx.with_time != (dx_t is not None):
+            raise RuntimeError("QieAddsFn.backward: image / text gradients do not match the forward's time embeddings")
+        d_it = d_tt = None
+        if ctx.with_time:
+            d_it = torch.empty(B, D_MODEL, dtype=dx_i.dtype, device=dev)
+            d_tt = torch.empty(B, D_MODEL, dtype=dx_t.dtype, device=dev)
+        N_v = dx_v.shape[1]
+        N_i, N_t = (dx_i.shape[1], dx_t.shape[1]) if ctx.with_time else (0, 0)
+        ws = torch.empty(_lib.lib().mtmp_qie_adds_bwd_ws_floats(B, N_v, int(ctx.with_time)), dtype=torch.float32, device=dev)
+        grads = _head_param_grads(ctx.prm, lambda dsts: call(
+            "mtmp_qie_adds_bwd", _dt(dx_v), _p(dx_v), _p(dx_i), _p(dx_t), _p(kv_len), int(kv_off), _p(age), _p(gender), _ptrs(P),
+            _p(d_it), _p(d_tt), _ptrs(dsts), _p(ws), B, N_v, N_i, N_t, 1e-5, _stream()))
+        return (None, None, d_it, d_tt, None, None) + grads
+
+
 class BceLogitsMean(torch.autograd.Function):
     """torch.nn.BCEWithLogitsLoss(reduction="mean") on fp32 logits (2_train.py:76): one launch forward, one scale backward."""
 
@@ -2133,99 +2230,142 @@ class StreamInputsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x_v, x_i, x_t, bott, add_i, add_t, eps_v, eps_i, eps_t, p, meta, *prm):
-        xs, epss, adds = [x_v, x_i, x_t], [eps_v, eps_i, eps_t], [None, add_i, add_t]
-        _gpu(*xs)
-        nb = bott.shape[-2]
-        bott_f = _c(bott.detach().float().view(nb, D_MODEL))
-        streams = meta.get("streams") or [None, None, None]
-        outs, saved, geo = [], [], []
-        for m in range(3):
-            cls, ln_w, ln_b = prm[3 * m:3 * m + 3]
-            with (torch.cuda.stream(streams[m]) if streams[m] is not None else contextlib.nullcontext()):
-                x = xs[m]
-                B, N, _ = x.shape
-                n_add, add = 0, None
-                if adds[m] is not None:                 # added to the tokens inside the kernels (both ways): no launch, no second copy
-                    n_add = adds[m].shape[0]
-                    if n_add % B or N % (n_add // B):
-                        raise ValueError("StreamInputsFn: the time embeddings do not divide the stream's tokens")
-                    add = _c(adds[m].detach().to(x.dtype))
-                x = _c(x)
-                cls_f, g_f, b_f = _c(cls.detach().float().view(-1)), _c(ln_w.detach().float()), _c(ln_b.detach().float())
-                pe = meta["pe"][m]
-                pe_f = None if pe is None else _c(pe.float().view(-1, D_MODEL))
-                if pe_f is not None and pe_f.shape[0] < N + 1:
-                    raise ValueError("positional table shorter than the stream")
-                pack, kv = meta["pack"] if (m == 0 and meta.get("pack") is not None) else (None, None)
-                out = torch.empty(B, nb + 1 + N, D_MODEL, dtype=x.dtype, device=x.device)
-                stats = torch.empty(B * (N + 1), 2, dtype=torch.float32, device=x.device)
-                seed = int(meta["seeds"][m]) & 0xFFFFFFFF
-                call("mtmp_stream_input_fwd_add", _dt(x), _p(x), _p(cls_f), _p(g_f), _p(b_f), _p(pe_f), _p(bott_f), _p(out), _p(stats),
-                     B, N, nb, float(epss[m]), float(p), seed, _p(_seed_word), _p(pack), _p(kv), _p(add),
-                     B * N // n_add if n_add else 1, _stream())
-            outs.append(out)
-            saved += [x, cls_f, g_f, stats]
-            geo.append((B, N, seed, pack, kv, n_add, add))
-        ctx.save_for_backward(*saved)
-        ctx.meta = (nb, float(p), geo, bott.shape, [t.shape for t in prm])
-        ctx.prm = list(prm) + [bott]
-        ctx.set_materialize_grads(False)
-        return tuple(outs)
+        return _stream_inputs_forward(ctx, [x_v, x_i, x_t], bott, [None, add_i, add_t], [eps_v, eps_i, eps_t], p, meta, prm)
 
     @staticmethod
     def backward(ctx, *dzs):
+        r = _stream_inputs_backward(ctx, dzs, 4)
+        return (None,) * (11 + 9) if r is None else (*r[0], r[1], r[2][1], r[2][2], None, None, None, None, None, *r[3])
+
+
+class StreamInputsQieFn(torch.autograd.Function):
+    """StreamInputsFn with an add for the vital-sign stream too (--vslt-type QIE, tri_mbt_vsltcls.py:191-198): apply(x_v, x_i, x_t,
+    bott, add_v, add_i, add_t, eps_v, eps_i, eps_t, p, meta, *the same nine parameters) -> (z_v, z_i, z_t); add_v [B, 256] is added to
+    every token of its sample (add_L = N_v), add_i / add_t as there, or None.  The adds are the three outputs of ops.QieAddsFn, and
+    meta["qie"] is the hand-off dict that node was given: the backward -- the same grouped launch and reduce_scatter -- runs no
+    mtmp_token_sums but leaves dx_v / dx_i / dx_t (and the packed stream's key lengths) in the dict for QieAddsFn.backward, which sums
+    them over the token axis itself; add_v's "gradient" is an unwritten placeholder that only orders that node behind this one."""
+
+    @staticmethod
+    def forward(ctx, x_v, x_i, x_t, bott, add_v, add_i, add_t, eps_v, eps_i, eps_t, p, meta, *prm):
+        if add_v is None or tuple(add_v.shape) != (x_v.shape[0], D_MODEL) or (add_i is None) != (add_t is None):
+            raise ValueError("StreamInputsQieFn: add_v [B, 256]; add_i and add_t are given together")
+        ctx.qie = meta["qie"]
+        return _stream_inputs_forward(ctx, [x_v, x_i, x_t], bott, [add_v, add_i, add_t], [eps_v, eps_i, eps_t], p, meta, prm)
+
+    @staticmethod
+    def backward(ctx, *dzs):
+        r = _stream_inputs_backward(ctx, dzs, None)
+        if r is None:
+            return (None,) * (12 + 9)
+        dxs, d_bott, _, pg = r
+        nb, _, geo, _, _ = ctx.meta
         sv = ctx.saved_tensors
-        nb, p, geo, bott_shape, pshapes = ctx.meta
-        lib = _lib.lib()
-        live = [m for m in range(3) if dzs[m] is not None]
-        if not live:
-            return (None,) * (11 + 9)
-        dev = sv[0].device
-        xs = [sv[4 * m] for m in range(3)]
-        dxs = [torch.empty_like(xs[m]) if m in live else None for m in range(3)]
-        rows = [lib.mtmp_stream_input_slab_rows(geo[m][0] * (nb + 1 + geo[m][1])) for m in live]
-        ws = torch.empty(sum(rows), 7 * D_MODEL, dtype=torch.float32, device=dev)
-        dz = [_c(dzs[m]) for m in live]
-        n = len(live)
-        PV, IV, FV, UV = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_float * n, ctypes.c_uint * n
-        call("mtmp_stream_input_bwd_grouped", _dt(xs[live[0]]), n, PV(*[t.data_ptr() for t in dz]), PV(*[xs[m].data_ptr() for m in live]),
-             PV(*[sv[4 * m + 1].data_ptr() for m in live]), PV(*[sv[4 * m + 2].data_ptr() for m in live]),
-             PV(*[sv[4 * m + 3].data_ptr() for m in live]), PV(*[dxs[m].data_ptr() for m in live]), _p(ws),
-             IV(*[geo[m][0] for m in live]), IV(*[geo[m][1] for m in live]), IV(*([nb] * n)), FV(*([p] * n)),
-             UV(*[geo[m][2] for m in live]), _p(_seed_word), PV(*[None if geo[m][3] is None else geo[m][3].data_ptr() for m in live]),
-             PV(*[None if geo[m][4] is None else geo[m][4].data_ptr() for m in live]),
-             PV(*[None if geo[m][6] is None else geo[m][6].data_ptr() for m in live]),
-             IV(*[geo[m][0] * geo[m][1] // geo[m][5] if geo[m][5] else 1 for m in live]), _stream())
-        # the time embeddings' gradient: sums over each group's tokens (both tensors in one launch), for the embedding node behind
-        d_add = [None, None, None]
-        ts = [m for m in live if geo[m][5] > 0 and ctx.needs_input_grad[3 + m]]
-        if ts:
-            for m in ts:
-                d_add[m] = torch.empty(geo[m][5], D_MODEL, dtype=xs[m].dtype, device=dev)
-            k = len(ts)
-            call("mtmp_token_sums", _dt(xs[ts[0]]), k, (ctypes.c_void_p * k)(*[dxs[m].data_ptr() for m in ts]),
-                 (ctypes.c_void_p * k)(*[d_add[m].data_ptr() for m in ts]), (ctypes.c_int * k)(*[geo[m][5] for m in ts]),
-                 (ctypes.c_int * k)(*[geo[m][0] * geo[m][1] // geo[m][5] for m in ts]), _stream())
-        sk = _sink_dsts(ctx.prm) if n == 3 else None
-        if sk is not None:
-            dsts = sk[2]
-        else:                                        # gradients for autograd (a plain optimizer, or slices that cannot be overwritten)
-            dsts = [torch.zeros(t.numel(), dtype=torch.float32, device=dev) for t in ctx.prm]
-        ent, r0 = [], 0
-        for k, m in enumerate(live):
-            sl = ws[r0:r0 + rows[k]]
-            r0 += rows[k]
-            ent += [(sl, rows[k], 0, D_MODEL, dsts[3 * m + 1]), (sl, rows[k], D_MODEL, D_MODEL, dsts[3 * m + 2]),
-                    (sl, rows[k], 2 * D_MODEL, D_MODEL, dsts[3 * m])]
-        ent.append((ws, ws.shape[0], 3 * D_MODEL, nb * D_MODEL, dsts[9]))
-        reduce_scatter(ent)
-        if sk is not None:
-            sk[0].mark_ready(sk[1])
-            pg, d_bott = [None] * 9, None
-        else:
-            pg = [dsts[i].view(pshapes[i]) if (i // 3) in live else None for i in range(9)]
-            d_bott = dsts[9].view(bott_shape)
-        return (dxs[0], dxs[1], dxs[2], d_bott, d_add[1], d_add[2], None, None, None, None, None, *pg)
+        with_time = geo[1][5] > 0
+        # a stream without a gradient (no layer reads it) adds nothing: zeros, so that QieAddsFn sees the three tensors it expects
+        full = [dxs[m] if dxs[m] is not None else torch.zeros_like(sv[4 * m]) for m in range(3)]
+        ctx.qie.update(dxs=(full[0], full[1] if with_time else None, full[2] if with_time else None), kv_len=geo[0][4], kv_off=nb + 1)
+        token = torch.empty(geo[0][0], D_MODEL, dtype=sv[0].dtype, device=sv[0].device)
+        return (*dxs, d_bott, token, None, None, None, None, None, None, None, *pg)
+
+
+def _stream_inputs_forward(ctx, xs, bott, adds, epss, p, meta, prm):
+    """the three launches of StreamInputsFn / StreamInputsQieFn (adds[m]: the rows added to stream m's tokens, or None)"""
+    _gpu(*xs)
+    nb = bott.shape[-2]
+    bott_f = _c(bott.detach().float().view(nb, D_MODEL))
+    streams = meta.get("streams") or [None, None, None]
+    outs, saved, geo = [], [], []
+    for m in range(3):
+        cls, ln_w, ln_b = prm[3 * m:3 * m + 3]
+        with (torch.cuda.stream(streams[m]) if streams[m] is not None else contextlib.nullcontext()):
+            x = xs[m]
+            B, N, _ = x.shape
+            n_add, add = 0, None
+            if adds[m] is not None:                 # added to the tokens inside the kernels (both ways): no launch, no second copy
+                n_add = adds[m].shape[0]
+                if n_add % B or N % (n_add // B):
+                    raise ValueError("StreamInputsFn: the time embeddings do not divide the stream's tokens")
+                add = _c(adds[m].detach().to(x.dtype))
+            x = _c(x)
+            cls_f, g_f, b_f = _c(cls.detach().float().view(-1)), _c(ln_w.detach().float()), _c(ln_b.detach().float())
+            pe = meta["pe"][m]
+            pe_f = None if pe is None else _c(pe.float().view(-1, D_MODEL))
+            if pe_f is not None and pe_f.shape[0] < N + 1:
+                raise ValueError("positional table shorter than the stream")
+            pack, kv = meta["pack"] if (m == 0 and meta.get("pack") is not None) else (None, None)
+            out = torch.empty(B, nb + 1 + N, D_MODEL, dtype=x.dtype, device=x.device)
+            stats = torch.empty(B * (N + 1), 2, dtype=torch.float32, device=x.device)
+            seed = int(meta["seeds"][m]) & 0xFFFFFFFF
+            call("mtmp_stream_input_fwd_add", _dt(x), _p(x), _p(cls_f), _p(g_f), _p(b_f), _p(pe_f), _p(bott_f), _p(out), _p(stats),
+                 B, N, nb, float(epss[m]), float(p), seed, _p(_seed_word), _p(pack), _p(kv), _p(add),
+                 B * N // n_add if n_add else 1, _stream())
+        outs.append(out)
+        saved += [x, cls_f, g_f, stats]
+        geo.append((B, N, seed, pack, kv, n_add, add))
+    ctx.save_for_backward(*saved)
+    ctx.meta = (nb, float(p), geo, bott.shape, [t.shape for t in prm])
+    ctx.prm = list(prm) + [bott]
+    ctx.set_materialize_grads(False)
+    return tuple(outs)
+
+
+def _stream_inputs_backward(ctx, dzs, sums_from):
+    """the backward of StreamInputsFn / StreamInputsQieFn -> (dxs, d_bott, d_add, parameter gradients), or None without any incoming
+    gradient.  sums_from: index of the first add among the node's inputs (mtmp_token_sums for the adds that want a gradient), or
+    None: no token sums (the QIE node hands the dxs over instead)."""
+    sv = ctx.saved_tensors
+    nb, p, geo, bott_shape, pshapes = ctx.meta
+    lib = _lib.lib()
+    live = [m for m in range(3) if dzs[m] is not None]
+    if not live:
+        return None
+    dev = sv[0].device
+    xs = [sv[4 * m] for m in range(3)]
+    dxs = [torch.empty_like(xs[m]) if m in live else None for m in range(3)]
+    rows = [lib.mtmp_stream_input_slab_rows(geo[m][0] * (nb + 1 + geo[m][1])) for m in live]
+    ws = torch.empty(sum(rows), 7 * D_MODEL, dtype=torch.float32, device=dev)
+    dz = [_c(dzs[m]) for m in live]
+    n = len(live)
+    PV, IV, FV, UV = ctypes.c_void_p * n, ctypes.c_int * n, ctypes.c_float * n, ctypes.c_uint * n
+    call("mtmp_stream_input_bwd_grouped", _dt(xs[live[0]]), n, PV(*[t.data_ptr() for t in dz]), PV(*[xs[m].data_ptr() for m in live]),
+         PV(*[sv[4 * m + 1].data_ptr() for m in live]), PV(*[sv[4 * m + 2].data_ptr() for m in live]),
+         PV(*[sv[4 * m + 3].data_ptr() for m in live]), PV(*[dxs[m].data_ptr() for m in live]), _p(ws),
+         IV(*[geo[m][0] for m in live]), IV(*[geo[m][1] for m in live]), IV(*([nb] * n)), FV(*([p] * n)),
+         UV(*[geo[m][2] for m in live]), _p(_seed_word), PV(*[None if geo[m][3] is None else geo[m][3].data_ptr() for m in live]),
+         PV(*[None if geo[m][4] is None else geo[m][4].data_ptr() for m in live]),
+         PV(*[None if geo[m][6] is None else geo[m][6].data_ptr() for m in live]),
+         IV(*[geo[m][0] * geo[m][1] // geo[m][5] if geo[m][5] else 1 for m in live]), _stream())
+    # the time embeddings' gradient: sums over each group's tokens (both tensors in one launch), for the embedding node behind
+    d_add = [None, None, None]
+    ts = [] if sums_from is None else [m for m in live if geo[m][5] > 0 and ctx.needs_input_grad[sums_from + m - 1]]
+    if ts:
+        for m in ts:
+            d_add[m] = torch.empty(geo[m][5], D_MODEL, dtype=xs[m].dtype, device=dev)
+        k = len(ts)
+        call("mtmp_token_sums", _dt(xs[ts[0]]), k, (ctypes.c_void_p * k)(*[dxs[m].data_ptr() for m in ts]),
+             (ctypes.c_void_p * k)(*[d_add[m].data_ptr() for m in ts]), (ctypes.c_int * k)(*[geo[m][5] for m in ts]),
+             (ctypes.c_int * k)(*[geo[m][0] * geo[m][1] // geo[m][5] for m in ts]), _stream())
+    sk = _sink_dsts(ctx.prm) if n == 3 else None
+    if sk is not None:
+        dsts = sk[2]
+    else:                                        # gradients for autograd (a plain optimizer, or slices that cannot be overwritten)
+        dsts = [torch.zeros(t.numel(), dtype=torch.float32, device=dev) for t in ctx.prm]
+    ent, r0 = [], 0
+    for k, m in enumerate(live):
+        sl = ws[r0:r0 + rows[k]]
+        r0 += rows[k]
+        ent += [(sl, rows[k], 0, D_MODEL, dsts[3 * m + 1]), (sl, rows[k], D_MODEL, D_MODEL, dsts[3 * m + 2]),
+                (sl, rows[k], 2 * D_MODEL, D_MODEL, dsts[3 * m])]
+    ent.append((ws, ws.shape[0], 3 * D_MODEL, nb * D_MODEL, dsts[9]))
+    reduce_scatter(ent)
+    if sk is not None:
+        sk[0].mark_ready(sk[1])
+        pg, d_bott = [None] * 9, None
+    else:
+        pg = [dsts[i].view(pshapes[i]) if (i // 3) in live else None for i in range(9)]
+        d_bott = dsts[9].view(bott_shape)
+    return dxs, d_bott, d_add, pg
 
 
 # ----------------------------------------------------------------------------- encoder layer

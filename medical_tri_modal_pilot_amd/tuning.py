@@ -2,7 +2,7 @@
 
 Each switch chooses the order in which independent launches are issued, or which of two launch sequences meant to be equivalent
 runs.  The defaults below are what the tests and bench.py run, and the only settings they run: no test reads or sets one of these
-attributes (HIP_HOURLY_EMBED, HIP_TRI_HEAD and HIP_ROW_HEAD excepted: their other setting is the reference's own torch chain, and a test runs both).  The other
+attributes (HIP_HOURLY_EMBED, HIP_TRI_HEAD, HIP_ROW_HEAD and HIP_QIE excepted: their other setting is the reference's own torch chain, and a test runs both).  The other
 settings are exercised only through ``tools/dbg/ab_patch.py`` (and the tools/dbg probes that flip one), so treat a non-default setting as unverified until such a run has compared it.  Each default is the faster setting as measured on
 MI355X -- the measurement is named beside it and lives in DESIGN.md section 9 ("Built, measured, not kept").  They are module
 attributes so that ab_patch.py can flip one and measure both settings on one machine in one session (machines differ by up to
@@ -55,6 +55,14 @@ HIP_TRI_HEAD = True
 # sums -> gather) plus ie_demo.  Like HIP_TRI_HEAD, BOTH settings are run by the tests (tests/test_flex_models_gpu.py): off is the
 # torch chain the reference defines.  A model class opts out with ``hip_row_head = False``.  profiles/row_head.txt.
 HIP_ROW_HEAD = True
+# tri_mbt_vsltcls (--vslt-type QIE): the demographic rows of the three streams as ops.QieAddsFn (csrc/qie.hip: one launch forward,
+# two backward), added inside the stream-input node (ops.StreamInputsQieFn), and the 256-wide BatchNorm head as ops.QieHeadFn
+# (csrc/headq.hip) -- with them the joint embedding node of TIE -- instead of the ie_demo torch chain, a [B,T,256] broadcast add with
+# its summing backward, torch time embeddings and the torch head.  Like HIP_HOURLY_EMBED, BOTH settings are run by the tests
+# (tests/test_qie_model_gpu.py): off is the torch chain the reference defines.  A model class opts in with ``hip_qie = True``.
+# Step at B 64, TIE-len 1000, 6 layers, bf16, replayed: 8.95 ms (8.82-9.02) on against 9.51 ms (9.37-9.53) off, eight alternating
+# windows in one process (tools/qie_bench.py; profiles/qie.txt).
+HIP_QIE = True
 # ops.layer_infer: the few-row FFN launches of a CLS-only last layer (B rows) and of the exchange-only layer in front of it (B * R
 # rows) keep the training forward's two launches (mtmp_ln_gemm_signs + mtmp_gemm_nt) below this many rows instead of the fused
 # mtmp_ffn_block: one workgroup of the fused kernel streams the whole megabyte of W1 and W2 for its 128 rows (42-44 us alone),
