@@ -286,8 +286,8 @@ int mtmp_head_bwd_scatter(int cls_dtype, const float* d_out, const void* cls, co
                           const void* const* params, const float* ws_fwd, void* dcls, float* const* dst, float* ws_bwd, int B,
                           float ln_eps, int training, void* stream);
 
-/* The same head with --vslt-type QIE (tri_mbt_vsltcls.py:148-151, 248-250; csrc/headq.hip): nothing is concatenated, the head reads
- * the 256 columns of LN(cls): out[b] = fc3(ReLU(BatchNorm1d(fc0(LN(cls[b]))))).  mtmp_head_fwd_t / mtmp_head_bwd_scatter without
+/* The same head with --vslt-type QIE (tri_mbt_vsltcls.py:148-151, 248-250; csrc/head.hip at width 256): nothing is concatenated, the
+ * head reads the 256 columns of LN(cls): out[b] = fc3(ReLU(BatchNorm1d(fc0(LN(cls[b]))))).  mtmp_head_fwd_t / mtmp_head_bwd_scatter without
  * age, gender and the four ie_demo parameters.  params: 10 device pointers (float): layer_norms_after_concat.{weight,bias},
  * fc_list.0.{weight[256][256],bias}, fc_list.1.{weight,bias,running_mean,running_var}, fc_list.3.{weight[256],bias[1]}.
  * dst[8]: the gradients of the eight trained ones in that order (overwritten).  ws_fwd: mtmp_headq_ws_floats(B) floats, written by

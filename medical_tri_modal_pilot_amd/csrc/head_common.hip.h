@@ -1,4 +1,5 @@
-// What the classification heads share (head.hip: the BatchNorm head of TRI_MBT_VSLTCLS; head3.hip: the three-row LayerNorm head):
+// What the classification heads share (head.hip: the BatchNorm head of TRI_MBT_VSLTCLS, 512 or 256 columns wide; head3.hip: the
+// three-row LayerNorm head; headr.hip: the row head):
 // the `ie_demo` chain and layer_norms_after_concat on 256-wide rows, the dW1 and dx loops, the `ie_demo` backward,
 // and the slab reduction that writes the row-summed gradients to their destinations.
 // Blocks, not kernels: the BatchNorm head reduces over the samples inside a wave, the LayerNorm head over the features, so each
@@ -62,14 +63,14 @@ MTMP_DEV f32x4 demo_row_fwd(float a, float g, const Shared3& p, int c, float eps
 }
 
 // ---- feature-parallel kernels: a workgroup owns FPW features, a wave one of them x all rows, R = 1, 2 or 4 rows per lane ----
-// (The 512 -> 256 product on the transposed 64-column tile is NOT a block here: it stands, loop for loop, in head_fc_kernel and
-//  head3_fc_kernel.  As an inlined function -- whole, or split into the tile load and the fma loop -- the compiler unrolls its loops
+// (The 512 -> 256 product on the transposed 64-column tile is NOT a block here: it stands, loop for loop, in head_fc_kernel,
+//  head3_fc_kernel and headr_fc_kernel.  As an inlined function -- whole, or split into the tile load and the fma loop -- the compiler unrolls its loops
 //  in another way (head_fc_kernel<2>: 1809 -> 454 instructions, 44 -> 54 VGPRs), the bits stay, and the replayed three-row head at
 //  B = 256 measured 1 us slower than the parent, outside the parent's own spread (profiles/head_shared.txt).  A change to one copy
-//  goes into the other.)
+//  goes into the others.)
 
 // dW1[j][k] = sum_b dh[b][j] x[b][k] for the workgroup's four features (dhs[f][b], zero past B): thread t owns columns t (s0) and
-// t + 256 (s1) of those four rows of W1
+// t + 256 (s1) of those four rows of W1.  (Rows of 512: the 256-wide head.hip keeps the one-half loop in its kernel.)
 template <int NB>
 MTMP_DEV void dw1_rows(const float (&dhs)[FPW][NB], const float* x, int B, float (&s0)[FPW], float (&s1)[FPW]) {
     const int tid = threadIdx.x;
@@ -93,11 +94,11 @@ MTMP_DEV void dx_row(const float* dhr, const float* w1, int k, float& dxc, float
     }
 }
 
-// (The LayerNorm(cls) backward between dx_row and demo_row_bwd is NOT a block here: it stands, equal, in head_x_bwd_kernel and
-//  head3_x_bwd_kernel.  Under -ffp-contract=fast the compiler takes gy = dxc * ln_g into the first step of block_sum(gy) as one fma
+// (The LayerNorm(cls) backward between dx_row and demo_row_bwd is NOT a block here: it stands, equal, in head_x_bwd_kernel,
+//  head3_x_bwd_kernel and headr_x_bwd_kernel.  Under -ffp-contract=fast the compiler takes gy = dxc * ln_g into the first step of block_sum(gy) as one fma
 //  where the code stands in the kernel, and as a rounded product plus an add where it is an inlined function: d cls then differs in
 //  the last bit, and a bf16 training run drifts away from what it computed before (profiles/head_shared.txt).  A change to one
-//  copy goes into the other.)
+//  copy goes into the others.)
 
 // ie_demo backward at column k (dxd = the gradient of the demo half of x), written to blocks 2 .. 6 of the slab row
 //     [dln_g | dln_b | ddemo_g | ddemo_be | ddemo_w0 | ddemo_w1 | ddemo_b] = 7 x 256

@@ -1639,6 +1639,45 @@ def _saved_grad_once(ctx, g):
     return (d * g).view(ctx.shape)
 
 
+def _head_forward(ctx, who, entries, cls, demo, training, momentum, bn_eps, run_mean, run_var, nbt, prm, split):
+    """the forward of HeadFn / QieHeadFn (csrc/head.hip at width 512 / 256).  entries: the (workspace size, forward, backward) entry
+    names; demo: (age, gender) or (); split: how many of ``prm`` stand in front of the two running statistics in the parameter
+    table of include/mtmp.h."""
+    _gpu(cls)
+    B = cls.shape[0]
+    if B > HEAD_MAX_B:
+        raise ValueError(f"{who} handles up to {HEAD_MAX_B} rows per rank (got {B})")
+    cls = _c(cls.detach() if cls.dtype in (torch.float32, torch.bfloat16) else cls.detach().float())
+    demo = [_c(t.detach().float()) for t in demo]
+    P = _head_params(prm)
+    table = _ptrs(P[:split] + [run_mean, run_var] + P[split:])
+    out = torch.empty(B, 1, dtype=torch.float32, device=cls.device)
+    ws = torch.empty(getattr(_lib.lib(), entries[0])(B), dtype=torch.float32, device=cls.device)
+    if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
+        raise TypeError(f"{who}: num_batches_tracked must be an int64 device tensor")
+    call(entries[1], _dt(cls), _p(cls), *map(_p, demo), table, _p(out), _p(ws), B, 1e-5, float(bn_eps), float(momentum),
+         int(bool(training)), _p(nbt), _stream())
+    ctx.save_for_backward(cls, ws, run_mean, run_var, *demo, *P)
+    ctx.training, ctx.prm, ctx.head = bool(training), list(prm), (entries[2], len(demo), split)
+    return out
+
+
+def _head_backward(ctx, d_out):
+    """the backward of HeadFn / QieHeadFn -> (d cls, the parameter gradients in the order of the node's parameters)"""
+    entry, n_demo, split = ctx.head
+    cls, ws, run_mean, run_var, *rest = ctx.saved_tensors
+    demo, P = rest[:n_demo], rest[n_demo:]
+    B, dev = cls.shape[0], cls.device
+    table = _ptrs(P[:split] + [run_mean, run_var] + P[split:])
+    d_out = _c(d_out.float().view(-1))
+    dcls = torch.empty(B, D_MODEL, dtype=cls.dtype, device=dev)
+    wsb = torch.empty(B * D_MODEL * 8, dtype=torch.float32, device=dev)
+    grads = _head_param_grads(ctx.prm, lambda dsts: call(
+        entry, _dt(cls), _p(d_out), _p(cls), *map(_p, demo), table, _p(ws), _p(dcls), _ptrs(dsts), _p(wsb), B, 1e-5,
+        int(ctx.training), _stream()))
+    return dcls, grads
+
+
 class HeadFn(torch.autograd.Function):
     """tri_mbt_vsltcls.py:248-255 with the ie_demo chain of :59-76: logits [B,1] from the vital-sign CLS vector and
     (age, gender).  apply(cls [B,256] fp32 | bf16, age [B], gender [B], training, momentum, bn_eps, run_mean, run_var,
@@ -1650,80 +1689,33 @@ class HeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cls, age, gender, training, momentum, bn_eps, run_mean, run_var, nbt, *prm):
-        _gpu(cls)
-        B = cls.shape[0]
-        if B > HEAD_MAX_B:
-            raise ValueError(f"HeadFn handles up to {HEAD_MAX_B} rows per rank (got {B})")
-        cls = _c(cls.detach() if cls.dtype in (torch.float32, torch.bfloat16) else cls.detach().float())
-        age, gender = _c(age.detach().float()), _c(gender.detach().float())
-        P = _head_params(prm)
         # order of include/mtmp.h: demo_w, demo_b, demo_g, demo_be, ln_g, ln_b, w1, b1, bn_g, bn_b, run_mean, run_var, w2, b2
-        table = _ptrs(P[:10] + [run_mean, run_var] + P[10:])
-        out = torch.empty(B, 1, dtype=torch.float32, device=cls.device)
-        ws = torch.empty(_lib.lib().mtmp_head_ws_floats(B), dtype=torch.float32, device=cls.device)
-        if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
-            raise TypeError("HeadFn: num_batches_tracked must be an int64 device tensor")
-        call("mtmp_head_fwd_t", _dt(cls), _p(cls), _p(age), _p(gender), table, _p(out), _p(ws), B, 1e-5,
-             float(bn_eps), float(momentum), int(bool(training)), _p(nbt), _stream())
-        ctx.save_for_backward(cls, age, gender, ws, run_mean, run_var, *P)
-        ctx.training = bool(training)
-        ctx.prm = list(prm)
-        return out
+        return _head_forward(ctx, "HeadFn", ("mtmp_head_ws_floats", "mtmp_head_fwd_t", "mtmp_head_bwd_scatter"), cls, (age, gender),
+                             training, momentum, bn_eps, run_mean, run_var, nbt, prm, 10)
 
     @staticmethod
     def backward(ctx, d_out):
-        cls, age, gender, ws, run_mean, run_var, *P = ctx.saved_tensors
-        B, dev = cls.shape[0], cls.device
-        table = _ptrs(P[:10] + [run_mean, run_var] + P[10:])
-        d_out = _c(d_out.float().view(-1))
-        dcls = torch.empty(B, D_MODEL, dtype=cls.dtype, device=dev)
-        wsb = torch.empty(B * D_MODEL * 8, dtype=torch.float32, device=dev)
-        grads = _head_param_grads(ctx.prm, lambda dsts: call(
-            "mtmp_head_bwd_scatter", _dt(cls), _p(d_out), _p(cls), _p(age), _p(gender), table, _p(ws),
-            _p(dcls), _ptrs(dsts), _p(wsb), B, 1e-5, int(ctx.training), _stream()))
+        dcls, grads = _head_backward(ctx, d_out)
         return (dcls, None, None, None, None, None, None, None, None) + grads
 
 
 class QieHeadFn(torch.autograd.Function):
-    """The same head with --vslt-type QIE (tri_mbt_vsltcls.py:148-151, 248-250; csrc/headq.hip): nothing is concatenated, fc_list.0 is
-    [256,256].  apply(cls [B,256] fp32 | bf16, training, momentum, bn_eps, run_mean, run_var, num_batches_tracked | None, *8
+    """The same head with --vslt-type QIE (tri_mbt_vsltcls.py:148-151, 248-250; csrc/head.hip at width 256): nothing is concatenated,
+    fc_list.0 is [256,256].  apply(cls [B,256] fp32 | bf16, training, momentum, bn_eps, run_mean, run_var, num_batches_tracked | None, *8
     parameters: layer_norms_after_concat.{weight,bias}, fc_list.0 / .1 / .3 {weight,bias}) -> logits [B,1].  HeadFn's forms: the CLS
     rows in the stack's type, the batch counter on the device, the eight gradients written to their destinations."""
 
     @staticmethod
     def forward(ctx, cls, training, momentum, bn_eps, run_mean, run_var, nbt, *prm):
-        _gpu(cls)
-        B = cls.shape[0]
-        if B > HEAD_MAX_B:
-            raise ValueError(f"QieHeadFn handles up to {HEAD_MAX_B} rows per rank (got {B})")
         if len(prm) != 8 or tuple(prm[2].shape) != (D_MODEL, D_MODEL):
             raise ValueError("QieHeadFn: eight parameters, fc_list.0.weight [256,256]")
-        cls = _c(cls.detach() if cls.dtype in (torch.float32, torch.bfloat16) else cls.detach().float())
-        P = _head_params(prm)
         # order of include/mtmp.h: ln_g, ln_b, w1, b1, bn_g, bn_b, run_mean, run_var, w2, b2
-        table = _ptrs(P[:6] + [run_mean, run_var] + P[6:])
-        out = torch.empty(B, 1, dtype=torch.float32, device=cls.device)
-        ws = torch.empty(_lib.lib().mtmp_headq_ws_floats(B), dtype=torch.float32, device=cls.device)
-        if nbt is not None and (nbt.dtype != torch.int64 or not nbt.is_cuda):
-            raise TypeError("QieHeadFn: num_batches_tracked must be an int64 device tensor")
-        call("mtmp_headq_fwd_t", _dt(cls), _p(cls), table, _p(out), _p(ws), B, 1e-5, float(bn_eps), float(momentum),
-             int(bool(training)), _p(nbt), _stream())
-        ctx.save_for_backward(cls, ws, run_mean, run_var, *P)
-        ctx.training = bool(training)
-        ctx.prm = list(prm)
-        return out
+        return _head_forward(ctx, "QieHeadFn", ("mtmp_headq_ws_floats", "mtmp_headq_fwd_t", "mtmp_headq_bwd_scatter"), cls, (), training,
+                             momentum, bn_eps, run_mean, run_var, nbt, prm, 6)
 
     @staticmethod
     def backward(ctx, d_out):
-        cls, ws, run_mean, run_var, *P = ctx.saved_tensors
-        B, dev = cls.shape[0], cls.device
-        table = _ptrs(P[:6] + [run_mean, run_var] + P[6:])
-        d_out = _c(d_out.float().view(-1))
-        dcls = torch.empty(B, D_MODEL, dtype=cls.dtype, device=dev)
-        wsb = torch.empty(B * D_MODEL * 8, dtype=torch.float32, device=dev)
-        grads = _head_param_grads(ctx.prm, lambda dsts: call(
-            "mtmp_headq_bwd_scatter", _dt(cls), _p(d_out), _p(cls), table, _p(ws), _p(dcls), _ptrs(dsts), _p(wsb), B, 1e-5,
-            int(ctx.training), _stream()))
+        dcls, grads = _head_backward(ctx, d_out)
         return (dcls, None, None, None, None, None, None) + grads
 
 

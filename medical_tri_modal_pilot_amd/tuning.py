@@ -57,7 +57,7 @@ HIP_TRI_HEAD = True
 HIP_ROW_HEAD = True
 # tri_mbt_vsltcls (--vslt-type QIE): the demographic rows of the three streams as ops.QieAddsFn (csrc/qie.hip: one launch forward,
 # two backward), added inside the stream-input node (ops.StreamInputsQieFn), and the 256-wide BatchNorm head as ops.QieHeadFn
-# (csrc/headq.hip) -- with them the joint embedding node of TIE -- instead of the ie_demo torch chain, a [B,T,256] broadcast add with
+# (csrc/head.hip at width 256) -- with them the joint embedding node of TIE -- instead of the ie_demo torch chain, a [B,T,256] broadcast add with
 # its summing backward, torch time embeddings and the torch head.  Like HIP_HOURLY_EMBED, BOTH settings are run by the tests
 # (tests/test_qie_model_gpu.py): off is the torch chain the reference defines.  A model class opts in with ``hip_qie = True``.
 # Step at B 64, TIE-len 1000, 6 layers, bf16, replayed: 8.95 ms (8.82-9.02) on against 9.51 ms (9.37-9.53) off, eight alternating

@@ -12,7 +12,7 @@ The adds (csrc/qie.hip: ops.QieAddsFn, mtmp_qie_adds_fwd / mtmp_qie_adds_bwd):
 dx_v / dx_i / dx_t are the stream-input node's input gradients: DATA here (values of the streams' type).  Where the rows go --
 x[b,t] + add[b] for every token t in FRONT of the stream's LayerNorm, the CLS row without it -- is `stream_rows`.
 
-The 256-wide head (csrc/headq.hip: ops.QieHeadFn):
+The 256-wide head (csrc/head.hip at width 256: ops.QieHeadFn):
     x = LN(cls) ;  h = x W1^T + b1, W1 [256,256] ;  y = BatchNorm1d(h) ;  a = ReLU(y) ;  o = a W2^T + b2
 tests/head_model.py's chain without the ie_demo half of x; its constants (LayerNorm eps 1e-5, BatchNorm eps 1e-3, momentum 0.25:
 different on purpose), its batch sizes and its rule for the two sums BatchNorm makes cancel in training mode (db1, dln_b: held to the

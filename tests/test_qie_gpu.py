@@ -1,5 +1,5 @@
-"""-m gpu: the kernels of ``--vslt-type QIE`` -- ops.QieAddsFn (csrc/qie.hip), ops.QieHeadFn (csrc/headq.hip) and the vital-sign add of
-the stream-input node (ops.StreamInputsQieFn) -- against the float64 models of tests/qie_model.py, element by element.
+"""-m gpu: the kernels of ``--vslt-type QIE`` -- ops.QieAddsFn (csrc/qie.hip), ops.QieHeadFn (csrc/head.hip, width 256) and the vital-sign add
+of the stream-input node (ops.StreamInputsQieFn) -- against the float64 models of tests/qie_model.py, element by element.
 Metric and bound: qie_model.py -- every bound is max(8 e_torch, 16 * 2^-24) (+ 2^-8 for a bf16 output) with e_torch the error of the same
 chain in fp32 on the CPU, bit equality, or the absolute-sum rule for the head's two cancelling gradients.  Every case asserts its ReLU
 gate margin from the float64 reference before it compares, and no element is left out.

@@ -3,7 +3,7 @@
     python tools/qie_bench.py [--batch 64] [--tie-len 1000] [--layers 6] [--rounds 8] [--steps 20] [--out FILE]
 
 train.py-style steps of tri_mbt_vsltcls --vslt-type QIE at the benchmark's shape (B 64, TIE-len 1000, 6 layers, bf16), replayed from a
-hipGraph, with tuning.HIP_QIE on (ops.QieAddsFn, ops.StreamInputsQieFn, ops.QieHeadFn: csrc/qie.hip, csrc/headq.hip) and off (the
+hipGraph, with tuning.HIP_QIE on (ops.QieAddsFn, ops.StreamInputsQieFn, ops.QieHeadFn: csrc/qie.hip, csrc/head.hip) and off (the
 torch chain: the launch sequence this model had before the switch existed).  Two models in ONE process, one per setting -- the switch is
 read by forward() and frozen into the graph at its capture --, ``--rounds`` alternating windows of ``--steps`` replayed steps each, every
 window by the host clock around a window that ends in a device synchronise.  Reported: median and min .. max over the windows, and the
